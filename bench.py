@@ -35,6 +35,7 @@ FLOP_PER_IMAGE = 13.81e9          # SURVEY 8(d) / BASELINE.md 3: algorithmic Sta
 MFMA_PEAK_TFLOPS = 2500.0         # dense fp16/bf16 MFMA peak, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0             # HBM3E peak, MI355X_MICROARCH.md
 NBATCH = 8                        # synthetic batches the timed steps rotate through
+DUMP_BYTES = 64 * 10**6           # --dump-outputs: every .npy file together, headers included
 
 
 def host_cores() -> int:
@@ -393,6 +394,83 @@ def hbm_rows(dev, B):
     return out
 
 
+def _carried(st):
+    """What a step object carries from one step to the next: its device tensors (gate flags, latent scales, scalar block,
+    hyper-parameters), its sub-networks (FlatGroup masters, gradients, BatchNorm buffers) and its optimizers (moments,
+    step counts)."""
+    nets = [v for v in vars(st).values() if hasattr(v, "all_bns") and hasattr(v, "group")]
+    opts = [v for v in vars(st).values() if hasattr(v, "s1") and hasattr(v, "t_dev")]
+    ts = [v for v in vars(st).values() if torch.is_tensor(v)]
+    for n in nets:
+        ts += [n.group.data, n.group.grad, *n.group.bufs.values()]
+    for o in opts:
+        ts += [t for t in (o.s1, o.s2, o.t_dev) if t is not None]
+    return nets, opts, ts
+
+
+def snapshot(st):
+    nets, opts, ts = _carried(st)
+    for n in nets:
+        for h in n.group.flush_hooks:          # lazily kept BatchNorm running statistics -> the group's buffers
+            h()
+    return [(t, t.clone()) for t in ts], [o.t for o in opts]
+
+
+def restore(st, snap):
+    """Write a snapshot back IN PLACE (recorded HIP graphs keep reading the same memory), then rebuild what the
+    sub-networks derive from their masters (fp16 GEMM copies, permuted BatchNorm vectors) before the next launch."""
+    from fmri_hip import ops
+    from fmri_hip.nets import refresh_net
+    ops.join_side()
+    pairs, t_host = snap
+    for t, v in pairs:
+        t.copy_(v)
+    nets, opts, _ = _carried(st)
+    for o, t in zip(opts, t_host):
+        o.t = t
+    for n in nets:
+        n.group.version += 1
+        n.group.buf_version += 1
+        refresh_net(n)
+    torch.cuda.synchronize()
+
+
+def dump_outputs(st, logs, path):
+    """``--dump-outputs``: what a caller of step ``st`` holds after it, one ``path/<name>.npy`` per array --
+    the logged losses and gate flags (``log.<key>``, float64 scalars), the forward outputs of that step (``out.<key>``,
+    ``step.outputs()``) and the updated parameters and BatchNorm buffers (``param.<key>``, ``step.state_dict()``), float32
+    (integer counters float64).  The files stay within DUMP_BYTES: the largest arrays are cut first, each to its fair share
+    of what the smaller ones leave, and a cut array is the 1-D sample of its flattened elements at fixed seeded indices
+    (the same indices for the same shape in every run).  Returns the summary for the result line."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"log.{k}": np.asarray(float(v), np.float64) for k, v in logs.items()}
+    tensors = {f"out.{k}": v for k, v in st.outputs().items()}
+    tensors.update((f"param.{k}", v) for k, v in st.state_dict().items())
+    width = {k: 4 if t.is_floating_point() else 8 for k, t in tensors.items()}
+    # bytes left after the scalars and one .npy header (at most 256 bytes) per file
+    left = DUMP_BYTES - 8 * len(arrays) - 256 * (len(arrays) + len(tensors))
+    keep = {}
+    order = sorted(tensors, key=lambda k: (tensors[k].numel() * width[k], k))
+    for j, k in enumerate(order):
+        keep[k] = min(tensors[k].numel(), left // (len(order) - j) // width[k])
+        left -= keep[k] * width[k]
+    sampled = {}
+    for k, t in tensors.items():
+        t = t.detach()
+        if keep[k] < t.numel():
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), keep[k], replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            sampled[k] = {"shape": list(tensors[k].shape), "kept": keep[k]}
+        arrays[k] = t.cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+    nbytes = 0
+    for k, v in arrays.items():
+        f = os.path.join(path, k + ".npy")
+        np.save(f, v)
+        nbytes += os.path.getsize(f)
+    assert nbytes <= DUMP_BYTES, nbytes
+    return {"dir": os.path.abspath(path), "files": len(arrays), "bytes": nbytes, "sampled": sampled}
+
+
 def _launch_ranks(n: int, json_fd: int) -> int:
     """Run this script under ``python -m torch.distributed.run`` with ``n`` ranks on 127.0.0.1 as a child process (never
     an exec: the launcher must stay a child of a process that owns no GPU state), pass the child's stdout -- rank 0's one
@@ -416,7 +494,7 @@ def _launch_ranks(n: int, json_fd: int) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="stage1")
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU (weak scaling); 0 = the workload's own")
@@ -438,7 +516,14 @@ def main():
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python (no graph capture)")
     ap.add_argument("--graph", action="store_true", help="always replay the captured graph(s) (default: whichever of "
                     "eager / graph replay probes faster on this host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, reset the timed step object to its seeded state, run one more step "
+                         "of the timed path (same launch mode and kernels) on the last timed step's batch and write "
+                         "what it computed to DIR/<name>.npy (rank 0; see dump_outputs).  dumps/<name> is ignored by "
+                         "git")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # stdout must carry exactly one JSON line: native libraries (the RCCL version banner at communicator creation)
     # print to file descriptor 1, so fd 1 is pointed at stderr for the run and the result goes to the saved descriptor
@@ -489,6 +574,7 @@ def main():
     has_gate = hasattr(st, "gate_skip")
     if has_gate:
         st.gate_skip = False
+    seeded = snapshot(st) if a.dump_outputs else None
 
     def barrier():
         if world > 1:
@@ -527,6 +613,7 @@ def main():
         if single or a.graph:
             try:
                 g = st.capture(*sbuf)
+                fw_graph = st.fw          # the forward tensors a replay writes (an eager step rebinds st.fw)
                 modes["graph"] = staged(g)
                 modes["graph"](0)
                 log("step captured into HIP graph(s)")
@@ -578,6 +665,25 @@ def main():
     dt = time.perf_counter() - t0
     log(f"timed region done: {1e3 * dt / a.steps:.2f} ms/step ({mode})")
     logs = st.logs()
+    dump = None
+    if a.dump_outputs:
+        # The state the timed steps reach is no function of the arguments (unordered atomic weight-gradient sums, amplified
+        # by the GAN trajectory), so the dump is one more step of the timed path -- this step object, the launch mode
+        # `run` of the probe, the same kernels -- on the last timed step's batch, from the seeded state every run starts
+        # from.  Every rank takes it (collectives); the timed state is put back afterwards for the passes below.
+        # the engine's own count of the steps so far: the first BatchNorm counter in state-dict order
+        counter = next([k, int(v)] for k, v in st.state_dict().items() if k.endswith("num_batches_tracked"))
+        timed = snapshot(st)
+        restore(st, seeded)
+        run(a.steps - 1)
+        barrier()
+        if mode == "graph":
+            st.fw = fw_graph
+        if rank == 0:
+            dump = dump_outputs(st, st.logs(), a.dump_outputs)
+            dump.update(batch=(a.steps - 1) % NBATCH, launch=mode, bn_counter_before_reset=counter)
+        restore(st, timed)
+        del timed
 
     def require_finite(what, lg):
         """A step whose losses are not finite is not a measurement: no `value` is printed and the run fails."""
@@ -715,6 +821,8 @@ def main():
         }
         if gate_out is not None:
             out["gate_skip"] = gate_out
+        if dump is not None:
+            out["dump_outputs"] = dump
         if world == 1 and not a.no_hbm_rows:
             out["hbm_bound_kernels"] = dict(peak_gb_s=HBM_PEAK_GBS, rows=hbm_rows(dev, 256))
         if world == 1 and not a.no_cpu_baseline and a.workload == "stage1":
