@@ -336,6 +336,22 @@ int fmri_gan_head_bwd_parts(const float* logit, int ldl, int B, void* dlogit, in
                             int parts, void* stream);
 int fmri_wae_logloss(const float* logit, int ldl, int n, int one_minus, float w, float* total, float* prob,
                      void* dlogit, int ldg, float gscale, void* stream);
+/* ---- MMD latent penalty with the inverse-multiquadratic kernel (the second WAE penalty of Tolstikhin et al., ICLR 2018;
+ * the reference only has the adversarial one).  q: encoder latents [n][ldq], p: prior / target samples [n][ldp], fp32,
+ * n >= 2 the GLOBAL batch, d = latent size (a multiple of 64, <= 1024, else FMRI_E_UNSUPPORTED); rows 16-byte aligned
+ * (ldq, ldp multiples of 4).  Scales s (host array of 1..8 values; NULL -> {0.1, 0.2, 0.5, 1, 2, 5, 10}),
+ * C_s = 2 d sigma2 s, k(a,b) = sum_s C_s / (C_s + |a-b|^2), kappa'(r) = -sum_s C_s / (C_s + r)^2:
+ *     MMD_u = [ sum_{i!=j} k(p_i,p_j) + sum_{i!=j} k(q_i,q_j) ] / (n(n-1))  -  2/n^2 sum_{i,j} k(q_i,p_j)
+ *     dMMD_u/dq_i = 4/(n(n-1)) sum_{j!=i} kappa'(r^qq_ij)(q_i-q_j)  -  4/n^2 sum_j kappa'(r^qp_ij)(q_i-p_j)
+ * (the diagonal excluded by index; |a-b|^2 = |a|^2 + |b|^2 - 2 a.b from an fp32-input MFMA Gram tile, clamped at 0).
+ * *total += w * MMD_u (total may be NULL); dq [n][ldd] fp32 = gscale * w * dMMD_u/dq (may be NULL: value only); p gets
+ * no gradient.  ws: fmri_mmd_imq_ws_bytes(n, d) bytes of device workspace (< 0: unsupported geometry).  No atomics: the
+ * column range is split over blocks whose partial sums a second pass adds in a fixed order, the statistic in fp64 --
+ * two calls are bit-identical in either deterministic mode.  No allocation, no host sync: graph-capturable. */
+int64_t fmri_mmd_imq_ws_bytes(int n, int d);
+int fmri_mmd_imq(const float* q, int ldq, const float* p, int ldp, int n, int d, float sigma2, const float* scales,
+                 int nscales, float w, float* total, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
+                 void* stream);
 /* ---- the WAE latent discriminator (models/vae_gan.py:499-529: Linear(z,H) ReLU [Linear(H,H) ReLU] x 3 Linear(H,1),
  * sigmoid left to fmri_wae_logloss) as one launch forward and one for the backward chain (H = 512, Zp a multiple of 64
  * <= 256; anything else: FMRI_E_UNSUPPORTED, use fmri_igemm layer by layer).

@@ -979,6 +979,23 @@ int fmri_wae_logloss(const float* logit, int ldl, int n, int one_minus, float w,
     if (!logit) return FMRI_E_BADARG;
     return wae_logloss_launch(logit, ldl, n, one_minus, w, total, prob, (half_t*)dlogit, ldg, gscale, S(stream));
 }
+int64_t fmri_mmd_imq_ws_bytes(int n, int d) { return mmd_imq_ws_bytes(n, d); }
+int fmri_mmd_imq(const float* q, int ldq, const float* p, int ldp, int n, int d, float sigma2, const float* scales,
+                 int nscales, float w, float* total, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
+                 void* stream) {
+    static const float kScales[7] = {0.1f, 0.2f, 0.5f, 1.f, 2.f, 5.f, 10.f};
+    if (!scales) { scales = kScales; nscales = 7; }
+    if (!q || !p || !ws || n < 2 || d < 1 || ldq < d || ldp < d || !(sigma2 > 0.f) || nscales < 1 || nscales > 8)
+        return FMRI_E_BADARG;
+    for (int s = 0; s < nscales; ++s)
+        if (!(scales[s] > 0.f)) return FMRI_E_BADARG;
+    if (dq && ldd < d) return FMRI_E_BADARG;
+    if (d % 64 || d > 1024) return FMRI_E_UNSUPPORTED;
+    // float4 loads of the q / p rows
+    if (((uintptr_t)q | (uintptr_t)p) % 16 || ldq % 4 || ldp % 4) return FMRI_E_BADARG;
+    return mmd_imq_launch(q, ldq, p, ldp, n, d, sigma2, scales, nscales, w, total, dq, ldd, gscale, ws, ws_bytes,
+                          S(stream));
+}
 int fmri_mlp_fwd(const void* z16, int M, int Zp, int H, const void* const* w5, const int* kp5, const float* const* bias5,
                  void* const* hs4, float* logit, void* stream) {
     if (!z16 || !w5 || !kp5 || !bias5 || !hs4 || !logit || M < 1) return FMRI_E_BADARG;

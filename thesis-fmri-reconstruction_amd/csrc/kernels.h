@@ -177,6 +177,10 @@ int gan_head_bwd_launch(const float* logit, int ldl, int B, half_t* dlogit, int 
                         int parts, hipStream_t st);
 int wae_logloss_launch(const float* logit, int ldl, int n, int one_minus, float w, float* total, float* prob,
                        half_t* dlogit, int ldg, float gscale, hipStream_t st);
+int64_t mmd_imq_ws_bytes(int n, int d);
+int mmd_imq_launch(const float* q, int ldq, const float* p, int ldp, int n, int d, float sigma2, const float* scales,
+                   int nscales, float w, float* total, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
+                   hipStream_t st);
 int compose_gate_launch(float* scal, int* flags, float batch, float nfeat, float npix, float lambda_mse,
                         float equilibrium, float margin, float beta, const float* hp_dev, int mode, int gate_on,
                         int force_dis, int force_dec, hipStream_t st);

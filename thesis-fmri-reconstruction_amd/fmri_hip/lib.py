@@ -84,6 +84,7 @@ _SIGS = {
     "fmri_gan_head_parts": [_p, _i, _i, _p, _p, _i, _p],
     "fmri_gan_head_bwd_parts": [_p, _i, _i, _p, _i, _f, _p, _i, _p],
     "fmri_wae_logloss": [_p, _i, _i, _i, _f, _p, _p, _p, _i, _f, _p],
+    "fmri_mmd_imq": [_p, _i, _p, _i, _i, _i, _f, _p, _i, _f, _p, _p, _i, _f, _p, _l, _p],
     "fmri_mlp_fwd": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "fmri_mlp_bwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _p],
     "fmri_compose_gate": [_p, _p, _f, _f, _f, _f, _f, _i, _i, _i, _p],
@@ -115,7 +116,8 @@ EP_AFFINE_APPLIED = 0x20000000
 
 
 EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_test_fastdiv", "fmri_bn_ws_floats",
-                             "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale"])
+                             "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
+                             "fmri_mmd_imq_ws_bytes"])
 
 _lib = None
 
@@ -147,6 +149,8 @@ def load():
     lib.fmri_resize_coeffs.argtypes = [_i, _i, _p, _p, _i]
     lib.fmri_latent_range_scale.restype = _f
     lib.fmri_latent_range_scale.argtypes = [_f, _f]
+    lib.fmri_mmd_imq_ws_bytes.restype = _l
+    lib.fmri_mmd_imq_ws_bytes.argtypes = [_i, _i]
     _lib = lib
     return lib
 

@@ -12,6 +12,12 @@ Every script runs two phases per batch with an optimizer step in between:
            discriminator scores the latents, and reconstruction + penalty are back-propagated.
 Nothing synchronises with the host inside a step; fp16 cotangents are kept in range with static scales and the
 device-side unit-RMS re-normalisation of the encoder cotangent (same scheme as steps.py).
+
+WaeStep(penalty="mmd") replaces the adversarial latent penalty with the IMQ-kernel MMD of the WAE paper (fmri_hip.mmd,
+csrc/mmd.hip): no D phase, the latent discriminator is neither run nor updated; the generator-side forward passes (and
+their BatchNorm running-statistic updates) stay those of the script.  The reference has no MMD step: this one is pinned
+by the formula and by an oracle composed of the reference's encoder / decoder / Adam pieces (tests/mmd_oracle.py).
+DualStage1Step keeps the adversarial penalty only.
 """
 from __future__ import annotations
 
@@ -23,6 +29,7 @@ import torch
 
 from . import lib
 from .nets import CognitiveEncoderNet, DecoderNet, EncoderNet, WaeDiscriminatorNet
+from .mmd import mmd_imq
 from .ops import images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
 from .steps import (S_ESQ, S_NA, S_NB, S_NE, GanHyper, Scales, Stage1Step, _attach_reducers, _Dist, _GanStepBase,
@@ -44,6 +51,8 @@ class WaeHyper:
     lr_dis: float = 0.5e-4
     lam: float = 10.0
     betas: tuple = (0.5, 0.999)
+    lam_mmd: float = 10.0          # penalty="mmd": weight of MMD_u (Stage I: lam_mmd * n * MMD_u, the sum convention)
+    mmd_sigma2: float = 0.25       # penalty="mmd": IMQ bandwidth sigma^2, the variance of the Stage-I prior 0.5 * N(0, I)
 
     @staticmethod
     def stage23() -> "WaeHyper":
@@ -83,11 +92,22 @@ class _LatentDiscPhase:
 
 
 class WaeStep(_LatentDiscPhase):
-    """WAE/GAN Stage I / II / III step."""
+    """WAE/GAN Stage I / II / III step.
+
+    ``penalty``: "gan" (default) the scripts' latent discriminator; "mmd" the IMQ-kernel MMD_u between the trained
+    encoder's means q = head[:, :Z] (fp32) and the other side p -- Stage I the prior sample 0.5 * z_fake_noise, Stages
+    II / III the Stage-I teacher's means -- with the statistic over the GLOBAL batch (data parallel: q and p gathered by
+    one SUM all-reduce of a zero-padded buffer).  loss_penalty is lam_mmd * n * MMD_u in Stage I, lam_mmd * MMD_u in
+    Stages II / III (the "sum" / "mean" conventions of the GAN penalty); Stage III logs it without back-propagating it;
+    the two discriminator losses log 0."""
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
-                 scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True):
+                 scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
+                 penalty: str = "gan"):
         assert stage in (1, 2, 3)
+        if penalty not in ("gan", "mmd"):
+            raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
+        self.penalty = penalty
         self.cfg, self.stage, self.n_voxels = cfg, stage, n_voxels
         self.sc = Scales() if scales is None else scales
         self.hp = hp if hp is not None else (WaeHyper() if stage == 1 else WaeHyper.stage23())
@@ -143,6 +163,7 @@ class WaeStep(_LatentDiscPhase):
         Bg = B * self.dd.world
         self.scal.zero_()
         x16 = images_to_nhwc(image)
+        gan = self.penalty == "gan"
 
         def latent16(head32, rows=B):
             z16 = torch.empty(rows, zp, dtype=torch.float16, device=dev)
@@ -153,14 +174,18 @@ class WaeStep(_LatentDiscPhase):
         if st == 1:
             head32, ectx = self.img_enc.forward(x16, updates=2)                       # :275 and :296
             z16 = latent16(head32)
-            z_real16, z_fake16 = z16, rows_to_f16(z_fake_noise, 0.5)
+            if gan:
+                z_real16, z_fake16 = z16, rows_to_f16(z_fake_noise, 0.5)
+            else:
+                p32 = z_fake_noise.float() * 0.5                                      # :276
             y, dctx = self.dec.forward(z16, 1)                                        # :297
         else:
             head_t, _ = self.img_enc.forward(x16, updates=2 if st == 2 else 1)        # stage 2: :284,:293; 3: :312
-            z_t16 = latent16(head_t)
+            z_t16 = latent16(head_t) if gan or st == 2 else None
             head32, ectx = self.cog.forward(rows_to_f16(fmri), updates=2)             # :292,:314 / :311,:333
             z16 = latent16(head32)
             z_real16, z_fake16 = z_t16, z16
+            p32 = head_t
             if st == 2:
                 # decoder call order: x_gt = dec(z_teacher) (:285, unused, moves BN statistics), then x_recon
                 yy, dctx = self.dec.forward(torch.cat([z_t16, z16], 0), 2, stat_order=(0, 1))
@@ -171,8 +196,9 @@ class WaeStep(_LatentDiscPhase):
         if st != 2:
             g_rec = 0
 
-        # ---- D phase ---------------------------------------------------------------------------------------------
-        self._dis_phase(self.wd, self.opt_dis, z_real16, z_fake16, hp.lam, self.scal, self.dd)
+        # ---- D phase (GAN penalty only) --------------------------------------------------------------------------
+        if gan:
+            self._dis_phase(self.wd, self.opt_dis, z_real16, z_fake16, hp.lam, self.scal, self.dd)
 
         # ---- G phase ---------------------------------------------------------------------------------------------
         npix = B * H * W
@@ -187,7 +213,11 @@ class WaeStep(_LatentDiscPhase):
         lib.call("fmri_pixel_sq", _P(x16), _P(y), npix, 3, 8, _P(self.scal[W_REC:W_REC + 1]), _P(dxt), 1.0)
         self.scal[W_REC:W_REC + 1].mul_(rec_w)
         train_enc = st != 3
-        dz_pen = self._penalty(self.wd, z16, pen_w, pen_scale, self.scal, need_dz=train_enc)
+        if gan:
+            dz_pen = self._penalty(self.wd, z16, pen_w, pen_scale, self.scal, need_dz=train_enc)
+        else:
+            mmd_w = hp.lam_mmd * Bg if st == 1 else hp.lam_mmd
+            dz_pen = self._mmd_penalty(head32, p32, mmd_w, need_dz=train_enc)
         self.dd.all_reduce(self.scal[:4])
 
         train_dec = st != 2
@@ -212,6 +242,29 @@ class WaeStep(_LatentDiscPhase):
             self.opt_dec.step()
         self.fw = dict(B=B, y=y, head32=head32, Z=Z)
         return self.scal
+
+    def _mmd_penalty(self, head32, p32, w: float, need_dz: bool):
+        """w * MMD_u(q, p) into the penalty slot and, with need_dz, d/dq of it for this rank's rows (fp32 [B, Z], true
+        scale).  q = head32[:, :Z] (the trained encoder's means), p = p32[:, :Z]; the statistic is over the global batch:
+        with data parallelism every rank fills its slice of a zero buffer [2, n_global, Z], one SUM all-reduce gathers
+        both sides, every rank evaluates the same global statistic (only rank 0 adds it to the slot, which the loss
+        all-reduce then sums) and keeps the gradient rows of its own samples."""
+        B, Z = head32.shape[0], self.cfg.latent_dim
+        dd = self.dd
+        rank = dd.dist.get_rank() if dd.on else 0
+        if dd.on:
+            buf = torch.zeros(2, B * dd.world, Z, dtype=torch.float32, device=head32.device)
+            buf[0, rank * B:(rank + 1) * B] = head32[:, :Z]
+            buf[1, rank * B:(rank + 1) * B] = p32[:, :Z]
+            dd.all_reduce(buf)
+            q, p = buf[0], buf[1]
+        else:
+            q, p = head32[:, :Z], p32[:, :Z]
+        dq = torch.empty(q.shape, dtype=torch.float32, device=q.device) if need_dz else None
+        mmd_imq(q, p, self.hp.mmd_sigma2, w=w, total=self.scal[W_PEN:W_PEN + 1] if rank == 0 else None, dq=dq)
+        if dq is None:
+            return None
+        return dq[rank * B:(rank + 1) * B] if dd.on else dq
 
     # HIP-graph recording of the whole step (Adam's step count and learning rates live on the device): the WAE steps are
     # ~300 launches of a few microseconds each -- eagerly issued they are bound by the host, replayed by the GPU
@@ -245,8 +298,9 @@ class WaeStep(_LatentDiscPhase):
         """True-scale gradients of the last step (syncs; tests only)."""
         ne = self.scal[S_NE].item()
         out = {}
-        for k, v in self.wd.group.grads.items():
-            out["discriminator." + k] = v.clone()
+        if self.penalty == "gan":
+            for k, v in self.wd.group.grads.items():
+                out["discriminator." + k] = v.clone()
         if self.stage != 3:
             for k, v in self.enc.group.grads.items():
                 out["encoder." + k] = v / ne
