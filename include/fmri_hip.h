@@ -205,6 +205,27 @@ int fmri_pcc(const float* pred, const float* truth, int64_t n, double* ws5, floa
 int fmri_ssim(const float* img1, const float* img2, int planes, int H, int W, double* ws2, float* ssim,
               float* contrast, void* stream);
 
+/* ---- pairwise similarity of n-way identification (objective_assessment, train/train_utils.py:752-816) ----------
+ * fmri_pcc_matrix: S[i * ldS + j] = PearsonCorrelation.forward(pred_i, truth_j) (:276-292 over ONE image) for
+ *   pred [N][D], truth [M][D] fp32 contiguous rows, D = C*H*W.  First pass: per-row mean and centred norm in fp64;
+ *   second pass: the centred Gram from v_mfma_f32_16x16x4_f32, each operand centred as it is loaded, K split into
+ *   fixed 1024-element chunks summed in chunk order (fp64).  ws: fmri_pcc_matrix_ws_bytes(N, M, D) bytes (< 0: bad
+ *   geometry); FMRI_E_WORKSPACE if smaller.
+ * fmri_ssim_pairs: out[p] = StructuralSimilarity.forward(pred[pairs[2p]], truth[pairs[2p+1]]) (:343-420, size_average,
+ *   mean over C, H, W) for pred [N][C][H][W], truth [M][C][H][W] fp32 and pairs int32 [P][2] in device memory
+ *   (0 <= i < N, 0 <= j < M; a pair outside writes NaN).  11x11 Gaussian sigma 1.5, padding 5, C1 = 1e-4,
+ *   C2 = 9e-4; H or W < 11: FMRI_E_UNSUPPORTED, as fmri_ssim.  The filtered x and x^2 of every image are computed
+ *   once per call into ws (fmri_ssim_pairs_ws_bytes(N, M, C, H, W) bytes: 8 (N + M) C H W), then one block per pair
+ *   filters the cross term x_i y_j and sums its SSIM map in a fixed order.  P = 0 launches nothing.
+ * Both: no atomics, no allocation, no host sync.  A pair's value is a bitwise function of the two images only (not of
+ *   its position, N, M or P), so two calls are bit-identical and truth_j == truth_i bitwise gives S_ij == S_ii. */
+int64_t fmri_pcc_matrix_ws_bytes(int N, int M, int64_t D);
+int fmri_pcc_matrix(const float* pred, const float* truth, int N, int M, int64_t D, float* sim, int ldS, void* ws,
+                    int64_t ws_bytes, void* stream);
+int64_t fmri_ssim_pairs_ws_bytes(int N, int M, int C, int H, int W);
+int fmri_ssim_pairs(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
+                    float* out, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- layout casts ------------------------------------------------------------------------------- */
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream);
 int fmri_nhwc_to_nchw(const void* src, float* dst, int N, int C, int HW, int Cp, float scale, void* stream);

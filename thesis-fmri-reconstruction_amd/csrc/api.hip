@@ -91,6 +91,24 @@ int fmri_ssim(const float* img1, const float* img2, int planes, int H, int W, do
     if (!img1 || !img2 || !ws2 || planes < 1 || H < 1 || W < 1 || (!ssim && !contrast)) return FMRI_E_BADARG;
     return ssim_launch(img1, img2, planes, H, W, ws2, ssim, contrast, S(stream));
 }
+/* ---- pairwise PCC / SSIM of n-way identification (train/train_utils.py:752-816) ---- */
+int64_t fmri_pcc_matrix_ws_bytes(int N, int M, int64_t D) { return pcc_matrix_ws_bytes(N, M, D); }
+int fmri_pcc_matrix(const float* pred, const float* truth, int N, int M, int64_t D, float* sim, int ldS, void* ws,
+                    int64_t ws_bytes, void* stream) {
+    if (!pred || !truth || !sim || !ws || N < 1 || M < 1 || D < 1 || ldS < M) return FMRI_E_BADARG;
+    // grid limits: N + M row blocks, ceil(M / 16) and ceil(D / 1024) in the y / z grid dimensions
+    if ((int64_t)N + M > INT32_MAX || M > 65535 * 16 || (D + 1023) / 1024 > 65535) return FMRI_E_UNSUPPORTED;
+    return pcc_matrix_launch(pred, truth, N, M, D, sim, ldS, ws, ws_bytes, S(stream));
+}
+int64_t fmri_ssim_pairs_ws_bytes(int N, int M, int C, int H, int W) { return ssim_pairs_ws_bytes(N, M, C, H, W); }
+int fmri_ssim_pairs(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
+                    float* out, void* ws, int64_t ws_bytes, void* stream) {
+    if (!pred || !truth || !ws || N < 1 || M < 1 || C < 1 || H < 1 || W < 1 || P < 0 || (P && (!pairs || !out)))
+        return FMRI_E_BADARG;
+    if (H < 11 || W < 11) return FMRI_E_UNSUPPORTED;   // as fmri_ssim: the reference's window shrinks, its padding not
+    if (((int64_t)N + M) * C > INT32_MAX || H > 65535 * 16 || W > 65535 * 16) return FMRI_E_UNSUPPORTED;
+    return ssim_pairs_launch(pred, truth, N, M, C, H, W, pairs, P, out, ws, ws_bytes, S(stream));
+}
 
 int fmri_version(void) { return 100; }
 

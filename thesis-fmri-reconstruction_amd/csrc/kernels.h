@@ -208,5 +208,11 @@ int crop_resize_u8_launch(const uint8_t* pool, const int64_t* offsets, const int
 int pcc_launch(const float* x, const float* y, int64_t n, double* sums5, float* out, hipStream_t st);
 int ssim_launch(const float* a, const float* b, int planes, int H, int W, double* acc2, float* ssim, float* contrast,
                 hipStream_t st);
+int64_t pcc_matrix_ws_bytes(int N, int M, int64_t D);
+int pcc_matrix_launch(const float* pred, const float* truth, int N, int M, int64_t D, float* S, int ldS, void* ws,
+                      int64_t ws_bytes, hipStream_t st);
+int64_t ssim_pairs_ws_bytes(int N, int M, int C, int H, int W);
+int ssim_pairs_launch(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
+                      float* out, void* ws, int64_t ws_bytes, hipStream_t st);
 
 }  // namespace fmri

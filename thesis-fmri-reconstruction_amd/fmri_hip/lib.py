@@ -36,6 +36,8 @@ _SIGS = {
     "fmri_crop_resize_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p],
     "fmri_pcc": [_p, _p, _l, _p, _p, _p],
     "fmri_ssim": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
+    "fmri_pcc_matrix": [_p, _p, _i, _i, _l, _p, _i, _p, _l, _p],
+    "fmri_ssim_pairs": [_p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _l, _p],
     "fmri_unpack_grad": [_p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _l, _p],
     "fmri_igemm": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p],
     "fmri_igemm_ep": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _l, _p, _p,
@@ -117,7 +119,7 @@ EP_AFFINE_APPLIED = 0x20000000
 
 EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_test_fastdiv", "fmri_bn_ws_floats",
                              "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
-                             "fmri_mmd_imq_ws_bytes"])
+                             "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes"])
 
 _lib = None
 
@@ -151,6 +153,10 @@ def load():
     lib.fmri_latent_range_scale.argtypes = [_f, _f]
     lib.fmri_mmd_imq_ws_bytes.restype = _l
     lib.fmri_mmd_imq_ws_bytes.argtypes = [_i, _i]
+    lib.fmri_pcc_matrix_ws_bytes.restype = _l
+    lib.fmri_pcc_matrix_ws_bytes.argtypes = [_i, _i, _l]
+    lib.fmri_ssim_pairs_ws_bytes.restype = _l
+    lib.fmri_ssim_pairs_ws_bytes.argtypes = [_i, _i, _i, _i, _i]
     _lib = lib
     return lib
 
