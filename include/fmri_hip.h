@@ -215,8 +215,9 @@ int fmri_ssim(const float* img1, const float* img2, int planes, int H, int W, do
  *   mean over C, H, W) for pred [N][C][H][W], truth [M][C][H][W] fp32 and pairs int32 [P][2] in device memory
  *   (0 <= i < N, 0 <= j < M; a pair outside writes NaN).  11x11 Gaussian sigma 1.5, padding 5, C1 = 1e-4,
  *   C2 = 9e-4; H or W < 11: FMRI_E_UNSUPPORTED, as fmri_ssim.  The filtered x and x^2 of every image are computed
- *   once per call into ws (fmri_ssim_pairs_ws_bytes(N, M, C, H, W) bytes: 8 (N + M) C H W), then one block per pair
- *   filters the cross term x_i y_j and sums its SSIM map in a fixed order.  P = 0 launches nothing.
+ *   once per call into ws (fmri_ssim_pairs_ws_bytes(N, M, C, H, W) bytes: 16 (N + M) C H W), then one block per pair
+ *   filters the cross term x_i y_j and sums its SSIM map in a fixed order.  Window, filtered statistics and SSIM map
+ *   are fp64 (the variances cancel in fp32).  P = 0 launches nothing.
  * Both: no atomics, no allocation, no host sync.  A pair's value is a bitwise function of the two images only (not of
  *   its position, N, M or P), so two calls are bit-identical and truth_j == truth_i bitwise gives S_ij == S_ii. */
 int64_t fmri_pcc_matrix_ws_bytes(int N, int M, int64_t D);

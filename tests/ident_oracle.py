@@ -6,7 +6,10 @@ train/train_utils.py:752-816) on top of oracle.metrics_oracle, and the seeded im
     as metrics_oracle.structural_similarity, batched).
   * ``n_way`` / ``n_way_expected`` / ``objective_assessment``: the counting of the reference on those matrices.
   * ``synth_batch``: fixed "model outputs" and targets from a numpy seed (the fixture stores the seeds, not the images);
-    ``StoredModel`` replays them as a model.
+    ``StoredModel`` replays them as a model.  ``edge_batch``: the same, offset per image, with saturated and flat regions.
+  * ``pcc_matrix64`` / ``ssim_pairs64`` / ``ssim_matrix64`` / ``pcc64`` / ``ssim64``: the same formulas in float64 (window
+    built in float64, every intermediate in float64), the anchor the HIP kernels are measured against; pinned to the
+    reference's values by tests/test_ident_host.py.
 """
 import random
 from fractions import Fraction
@@ -31,6 +34,29 @@ def synth_batch(n, c, h, w, seed, dup=None):
     alpha = rs.uniform(0.15, 0.85, (n, 1, 1, 1))
     pred = alpha * truth + (1 - alpha) * truth[other] + 0.4 * rs.uniform(-1, 1, (n, c, h, w))
     return torch.from_numpy(pred.astype(np.float32)), torch.from_numpy(truth.astype(np.float32))
+
+
+def edge_batch(n, m, c, h, w, seed):
+    """pred [n] and truth [m] (fp32, CPU) from synth_batch, each image scaled into [-1, 1] around its own offset of
+    0.2..0.5 in magnitude and random sign s.  pred 1, 5, 9, ... are tanh(20 x) (saturated to exactly +-1 where
+    |x| > 0.45); flat regions at exactly s (a white or black background): the top third of truth 2, 6, ..., the right
+    third of truth 3, 7, ..., the bottom third of pred 2, 6, ... and the top half of pred 3, 7, ...  Across pairs, flat
+    regions of equal and of opposite value overlap."""
+    k = max(n, m)
+    pred, truth = synth_batch(k, c, h, w, seed)
+    rs = np.random.RandomState(seed + 1)
+
+    def place(x):
+        o = (rs.uniform(0.2, 0.5, k) * rs.choice([-1, 1], k))[:, None, None, None]
+        amp = np.abs(x).reshape(k, -1).max(1)[:, None, None, None]
+        return (1 - np.abs(o)) * x / amp + o, np.sign(o)
+    (p, sp), (t, st) = place(pred.double().numpy()), place(truth.double().numpy())
+    p[1::4] = np.tanh(20 * p[1::4])
+    t[2::4, :, :h // 3] = st[2::4]
+    t[3::4, :, :, w - w // 3:] = st[3::4]
+    p[2::4, :, h - h // 3:] = sp[2::4]
+    p[3::4, :, :h // 2] = sp[3::4]
+    return torch.from_numpy(p[:n].astype(np.float32)), torch.from_numpy(t[:m].astype(np.float32))
 
 
 class StoredModel:
@@ -111,6 +137,75 @@ def n_way_expected_from(S_pcc, S_ssim, top):
 
 def n_way_expected(pred, truth, top):
     return n_way_expected_from(pcc_matrix(pred, truth), ssim_matrix(pred, truth), top)
+
+
+def pcc_matrix64(pred, truth):
+    """float64 [N, M]: every row centred in float64, one float64 matmul.  A zero-variance row gives 0 / 0 = NaN."""
+    a = pred.reshape(pred.shape[0], -1).double()
+    b = truth.reshape(truth.shape[0], -1).double()
+    a = a - a.mean(1, keepdim=True)
+    b = b - b.mean(1, keepdim=True)
+    return (a @ b.t()) / (a.norm(dim=1)[:, None] * b.norm(dim=1)[None, :])
+
+
+def gaussian64(size=11, sigma=1.5):
+    """The reference's 1-D Gaussian (train/train_utils.py:313-326) in float64, normalised to sum 1."""
+    x = torch.arange(size, dtype=torch.float64) - size // 2
+    g = torch.exp(-x * x / (2 * sigma * sigma))
+    return g / g.sum()
+
+
+def _filter64(t):
+    """float64 [N, C, H, W] filtered by the 11 x 11 window outer(g, g) with zero padding 5, applied as its two 1-D
+    passes (the same sum; one fifth of the work of the 2-D convolution)."""
+    C = t.shape[1]
+    g = gaussian64()
+    t = F.conv2d(t, g.view(1, 1, 1, 11).expand(C, 1, 1, 11), padding=(0, 5), groups=C)
+    return F.conv2d(t, g.view(1, 1, 11, 1).expand(C, 1, 11, 1), padding=(5, 0), groups=C)
+
+
+def _ssim_map64(m1, m2, e11, e22, e12):
+    s1, s2, s12 = e11 - m1 * m1, e22 - m2 * m2, e12 - m1 * m2
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    ssim = ((2 * m1 * m2 + C1) * (2 * s12 + C2)) / ((m1 * m1 + m2 * m2 + C1) * (s1 + s2 + C2))
+    return ssim, (2 * s12 + C2) / (s1 + s2 + C2)
+
+
+def ssim_pairs64(pred, truth, pairs, chunk=1024):
+    """float64 [P]: mean SSIM of pred[i] against truth[j] for every row (i, j) of ``pairs`` (the formula of
+    ``ssim_pairs``), in chunks of ``chunk`` pairs."""
+    a, b = pred.double(), truth.double()
+    mp, mt, ep, et = _filter64(a), _filter64(b), _filter64(a * a), _filter64(b * b)
+    pairs = torch.as_tensor(pairs, dtype=torch.int64).reshape(-1, 2)
+    out = torch.empty(pairs.shape[0], dtype=torch.float64)
+    for s in range(0, pairs.shape[0], chunk):
+        i, j = pairs[s:s + chunk, 0], pairs[s:s + chunk, 1]
+        ssim, _ = _ssim_map64(mp[i], mt[j], ep[i], et[j], _filter64(a[i] * b[j]))
+        out[s:s + chunk] = ssim.mean((1, 2, 3))
+    return out
+
+
+def ssim_matrix64(pred, truth):
+    N, M = pred.shape[0], truth.shape[0]
+    ii, jj = torch.meshgrid(torch.arange(N), torch.arange(M), indexing="ij")
+    return ssim_pairs64(pred, truth, torch.stack([ii.reshape(-1), jj.reshape(-1)], 1)).view(N, M)
+
+
+def pcc64(y_pred, y_true):
+    """float64 PearsonCorrelation of two whole tensors (one value over the batch, as the metric module)."""
+    a, b = y_pred.double().reshape(-1), y_true.double().reshape(-1)
+    a, b = a - a.mean(), b - b.mean()
+    return (a @ b) / (a.norm() * b.norm())
+
+
+def ssim64(img1, img2):
+    """float64 (mean SSIM, mean contrast term) over a whole [N, C, H, W] or [C, H, W] batch: StructuralSimilarity's
+    ``full=True`` pair."""
+    a, b = img1.double(), img2.double()
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    ssim, contrast = _ssim_map64(_filter64(a), _filter64(b), _filter64(a * a), _filter64(b * b), _filter64(a * b))
+    return ssim.mean(), contrast.mean()
 
 
 def draw_distractors(n, top):

@@ -152,3 +152,51 @@ def test_objective_assessment_batch_of_one_raises_the_reference_index_error():
             raise AssertionError("the model must not run before the draws")
     with pytest.raises(IndexError):
         objective_assessment(Model(), [torch.zeros(1, 3, 16, 16)], top=2)
+
+
+def test_fp64_oracle_matches_reference_goldens(golden_dir):
+    """The float64 restatement (ident_oracle.pcc_matrix64 / ssim_matrix64 / pcc64 / ssim64) against the reference's own
+    fp32 values: tests/golden/ident.npz (every pair of every batch) and tests/golden/metrics.npz (PCC, SSIM and the
+    contrast term of whole batches).  The reference's fp32 rounding is below 1e-6 here, so 2e-6 absolute ties the anchor
+    of the fp64 sweeps (test_ident_edges_gpu.py, test_metrics.py) to the reference."""
+    from test_metrics import _cases, _inputs
+    g, cases = golden_cases(golden_dir)
+    for name, _, batches in cases:
+        for b, (pred, truth) in enumerate(batches):
+            np.testing.assert_allclose(IO.pcc_matrix64(pred, truth).numpy(), g[f"{name}/b{b}/pcc"], rtol=0, atol=2e-6)
+            np.testing.assert_allclose(IO.ssim_matrix64(pred, truth).numpy(), g[f"{name}/b{b}/ssim"], rtol=0,
+                                       atol=2e-6)
+    g, tags = _cases(golden_dir)
+    for tag in tags:
+        a, b = _inputs(g[f"{tag}/shape"])
+        s, c = IO.ssim64(a, b)
+        assert abs(IO.pcc64(a, b).item() - float(g[f"{tag}/pcc"])) <= 2e-6, tag
+        assert abs(s.item() - float(g[f"{tag}/ssim"])) <= 2e-6, tag
+        assert abs(c.item() - float(g[f"{tag}/contrast"])) <= 2e-6, tag
+        # a 3-D [C, H, W] input is one image
+        s0, c0 = IO.ssim64(a[0], b[0])
+        s1, c1 = IO.ssim64(a[:1], b[:1])
+        assert s0.item() == s1.item() and c0.item() == c1.item()
+
+
+def test_fp64_oracle_is_the_exact_formula():
+    """Exact cases of the float64 restatement: identical images give PCC 1 and SSIM 1; y = 2 x + 1 gives PCC 1; a
+    constant image gives PCC NaN; the separable filter equals the 2-D 11 x 11 window; the pair list equals the
+    matrix."""
+    import torch.nn.functional as F
+    pred, truth = IO.synth_batch(5, 2, 13, 17, 3)
+    assert torch.allclose(IO.pcc_matrix64(pred, pred).diagonal(), torch.ones(5, dtype=torch.float64), rtol=0, atol=1e-14)
+    assert torch.allclose(IO.ssim_matrix64(pred, pred).diagonal(), torch.ones(5, dtype=torch.float64), rtol=0,
+                          atol=1e-14)
+    assert abs(IO.pcc_matrix64(pred[:1], 2 * pred[:1] + 1).item() - 1) < 1e-14
+    assert torch.isnan(IO.pcc_matrix64(torch.full((1, 2, 13, 17), 0.1), truth)).all()
+    g = IO.gaussian64()
+    w2 = torch.outer(g, g).expand(2, 1, 11, 11)
+    x = pred.double()
+    assert torch.allclose(IO._filter64(x), F.conv2d(x, w2, padding=5, groups=2), rtol=0, atol=1e-14)
+    S = IO.ssim_matrix64(pred, truth)
+    pairs = torch.tensor([[4, 0], [1, 3], [0, 4]])
+    assert torch.equal(IO.ssim_pairs64(pred, truth, pairs, chunk=2), S[pairs[:, 0], pairs[:, 1]])
+    # the fp32 oracle agrees with it to fp32 rounding
+    assert (IO.pcc_matrix(pred, truth).double() - IO.pcc_matrix64(pred, truth)).abs().max() < 1e-6
+    assert (IO.ssim_matrix(pred, truth).double() - S).abs().max() < 1e-6

@@ -6,12 +6,15 @@
 //     ident_rowstats_kernel  one block per row of pred / truth: fp64 mean, then the fp64 sum of (x - mean)^2 of the
 //                            fp32-centred row; fixed-order block sums
 //     ident_gram_kernel      one wave per (16 x 16 tile, K chunk of PCC_KC): centred Gram tile with
-//                            v_mfma_f32_16x16x4_f32, each operand centred as it is loaded
+//                            v_mfma_f32_16x16x4_f32, each operand centred as it is loaded, fp32 over 16 k, then fp64
 //     ident_pcc_final_kernel S_ij = sum over the chunks in chunk order (fp64) / (|vx_i| |vy_j|)
-//   SSIM of a pair list
+//   SSIM of a pair list (fp32 images in, every filtered statistic and the SSIM map in fp64, window built in fp64)
 //     ident_ssim_stats_kernel   Gaussian-filtered x and x^2 of every image plane, once per image, into the workspace
 //     ident_ssim_pair_kernel    one block per pair: the filtered cross term G * (x_i y_j) in separable form in LDS,
 //                               tile by tile in a fixed order, fp64 per-thread sums, fixed-order block sum
+//   The variances E[x^2] - mu^2 cancel: in fp32, windows where |x| = 1 almost everywhere (a saturated output against a
+//   flat background) lose ~1e-7 against C2 = 9e-4, and a pair's mean SSIM was 2e-5 from the exact value.  In fp64 they
+//   are exact to ~1e-12.
 //
 // A pair's value is a bitwise function of the two images alone: the chunking depends on D only, the tile order on
 // (C, H, W) only, and there are no atomics.  Two calls are bit-identical, a pair's value does not depend on its
@@ -59,7 +62,9 @@ __global__ __launch_bounds__(256) void ident_rowstats_kernel(const float* __rest
 
 // grid (ceil(N/16), ceil(M/16), chunks), one wave.  Lane (lr, lg) feeds row lr of A (pred) and column lr of B (truth)
 // with k = kb + 4 lg + e in the e-th MFMA of a 16-step: both operands use the same k order, so every element of the
-// tile is the same k-ordered chain whatever its position.  Out-of-range k and rows enter as exact zeros.
+// tile is the same k-ordered chain whatever its position.  Out-of-range k and rows enter as exact zeros.  Each 16-step
+// starts a fresh fp32 chain and is added to an fp64 sum: one fp32 chain over the whole chunk grows with the partial
+// sum of a correlated pair and was 5e-6 from fp64 at D = 30000.
 __global__ __launch_bounds__(64) void ident_gram_kernel(const float* __restrict__ pred, int N,
                                                         const float* __restrict__ truth, int M, int64_t D,
                                                         const float* __restrict__ mean, float* __restrict__ part) {
@@ -71,8 +76,9 @@ __global__ __launch_bounds__(64) void ident_gram_kernel(const float* __restrict_
     const float* xa = pred + (int64_t)(va ? ra : 0) * D;
     const float* xb = truth + (int64_t)(vb ? cb : 0) * D;
     const float ma = va ? mean[ra] : 0.f, mb = vb ? mean[N + cb] : 0.f;
-    f4 g = f4{0.f, 0.f, 0.f, 0.f};
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t kb = k0; kb < k1; kb += 16) {     // wave-uniform trip count: every lane issues every MFMA
+        f4 g = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int64_t kk = kb + 4 * lg + e;
@@ -80,6 +86,8 @@ __global__ __launch_bounds__(64) void ident_gram_kernel(const float* __restrict_
             const float b = vb && kk < k1 ? xb[kk] - mb : 0.f;
             g = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, g, 0, 0, 0);
         }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] += (double)g[r];
     }
     // C/D layout: column lane & 15, row 4 (lane >> 4) + r
     const int gj = blockIdx.y * 16 + lr;
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(64) void ident_gram_kernel(const float* __restrict_
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int gi = blockIdx.x * 16 + lg * 4 + r;
-        if (gi < N && gj < M) out[(int64_t)gi * M + gj] = g[r];
+        if (gi < N && gj < M) out[(int64_t)gi * M + gj] = (float)acc[r];
     }
 }
 
@@ -103,23 +111,23 @@ __global__ __launch_bounds__(256) void ident_pcc_final_kernel(const float* __res
     }
 }
 
-// gaussian(11, 1.5) normalised to sum 1 in fp32, as metrics.hip ssim_kernel and the reference compute it
-__device__ inline void gauss11(float* g) {
+// gaussian(11, 1.5) normalised to sum 1, in fp64 (the reference's window is the fp32 rounding of the same numbers)
+__device__ inline void gauss11(double* g) {
     if (threadIdx.x < SS_WIN) {
-        float s = 0.f;
-        for (int i = 0; i < SS_WIN; ++i) s += expf(-(float)((i - 5) * (i - 5)) / 4.5f);
+        double s = 0.0;
+        for (int i = 0; i < SS_WIN; ++i) s += exp(-(double)((i - 5) * (i - 5)) / 4.5);
         const int i = threadIdx.x;
-        g[i] = expf(-(float)((i - 5) * (i - 5)) / 4.5f) / s;
+        g[i] = exp(-(double)((i - 5) * (i - 5)) / 4.5) / s;
     }
 }
 
 // grid (images * C, ceil(H/16), ceil(W/16)): filtered x (mu) and x^2 (e) of one 16 x 16 tile of one plane, zero padding
 __global__ __launch_bounds__(256) void ident_ssim_stats_kernel(const float* __restrict__ pred, int N,
                                                                const float* __restrict__ truth, int C, int H, int W,
-                                                               float* __restrict__ mu, float* __restrict__ ex) {
+                                                               double* __restrict__ mu, double* __restrict__ ex) {
     __shared__ float t[SS_R][SS_R + 1];
-    __shared__ float hx[2][SS_R][SS_TS + 1];
-    __shared__ float g[SS_WIN];
+    __shared__ double hx[2][SS_R][SS_TS + 1];
+    __shared__ double g[SS_WIN];
     const int tx0 = blockIdx.z * SS_TS, ty0 = blockIdx.y * SS_TS;
     const int plane = blockIdx.x;
     const int64_t hw = (int64_t)H * W;
@@ -133,11 +141,11 @@ __global__ __launch_bounds__(256) void ident_ssim_stats_kernel(const float* __re
     __syncthreads();
     for (int e = threadIdx.x; e < SS_R * SS_TS; e += 256) {
         const int j = e / SS_TS, i = e - j * SS_TS;
-        float s0 = 0.f, s1 = 0.f;
+        double s0 = 0.0, s1 = 0.0;
         for (int k = 0; k < SS_WIN; ++k) {
-            const float w = g[k], u = t[j][i + k];
+            const double w = g[k], u = t[j][i + k];
             s0 += w * u;
-            s1 += w * u * u;
+            s1 += w * (u * u);
         }
         hx[0][j][i] = s0;
         hx[1][j][i] = s1;
@@ -146,7 +154,7 @@ __global__ __launch_bounds__(256) void ident_ssim_stats_kernel(const float* __re
     const int oy = threadIdx.x >> 4, ox = threadIdx.x & 15;
     const int y = ty0 + oy, x = tx0 + ox;
     if (y < H && x < W) {
-        float m = 0.f, q = 0.f;
+        double m = 0.0, q = 0.0;
         for (int k = 0; k < SS_WIN; ++k) {
             m += g[k] * hx[0][oy + k][ox];
             q += g[k] * hx[1][oy + k][ox];
@@ -160,11 +168,11 @@ __global__ __launch_bounds__(256) void ident_ssim_stats_kernel(const float* __re
 __global__ __launch_bounds__(256) void ident_ssim_pair_kernel(const float* __restrict__ pred, int N,
                                                               const float* __restrict__ truth, int M, int C, int H,
                                                               int W, const int* __restrict__ pairs,
-                                                              const float* __restrict__ mu,
-                                                              const float* __restrict__ ex, float* __restrict__ out) {
-    __shared__ float t[SS_R][SS_R + 1];
-    __shared__ float hx[SS_R][SS_TS + 1];
-    __shared__ float g[SS_WIN];
+                                                              const double* __restrict__ mu,
+                                                              const double* __restrict__ ex, float* __restrict__ out) {
+    __shared__ double t[SS_R][SS_R + 1];
+    __shared__ double hx[SS_R][SS_TS + 1];
+    __shared__ double g[SS_WIN];
     __shared__ double sh[4];
     const int p = blockIdx.x;
     const int pi = pairs[2 * p], pj = pairs[2 * p + 1];
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(256) void ident_ssim_pair_kernel(const float* __res
     const int64_t hw = (int64_t)H * W;
     const int tw = (W + SS_TS - 1) / SS_TS, th = (H + SS_TS - 1) / SS_TS;
     const int oy = threadIdx.x >> 4, ox = threadIdx.x & 15;
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
     double acc = 0.0;
     for (int c = 0; c < C; ++c) {
         const int64_t pa = ((int64_t)pi * C + c) * hw, pb = ((int64_t)pj * C + c) * hw;
@@ -189,26 +197,26 @@ __global__ __launch_bounds__(256) void ident_ssim_pair_kernel(const float* __res
                     const int j = e / SS_R, i = e - j * SS_R;
                     const int y = ty0 - SS_PAD + j, x = tx0 - SS_PAD + i;
                     const int64_t o = (int64_t)y * W + x;
-                    t[j][i] = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W ? pred[pa + o] * truth[pb + o]
-                                                                                     : 0.f;
+                    t[j][i] = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W   // exact product in fp64
+                                  ? (double)pred[pa + o] * (double)truth[pb + o] : 0.0;
                 }
                 __syncthreads();
                 for (int e = threadIdx.x; e < SS_R * SS_TS; e += 256) {
                     const int j = e / SS_TS, i = e - j * SS_TS;
-                    float s = 0.f;
+                    double s = 0.0;
                     for (int k = 0; k < SS_WIN; ++k) s += g[k] * t[j][i + k];
                     hx[j][i] = s;
                 }
                 __syncthreads();
                 const int y = ty0 + oy, x = tx0 + ox;
                 if (y < H && x < W) {
-                    float e12 = 0.f;
+                    double e12 = 0.0;
                     for (int k = 0; k < SS_WIN; ++k) e12 += g[k] * hx[oy + k][ox];
                     const int64_t o = (int64_t)y * W + x;
-                    const float m1 = mu[sa + o], m2 = mu[sb + o], e11 = ex[sa + o], e22 = ex[sb + o];
-                    const float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
-                    const float s1 = e11 - m11, s2 = e22 - m22, s12 = e12 - m12;
-                    acc += (double)(((2.f * m12 + C1) * (2.f * s12 + C2)) / ((m11 + m22 + C1) * (s1 + s2 + C2)));
+                    const double m1 = mu[sa + o], m2 = mu[sb + o], e11 = ex[sa + o], e22 = ex[sb + o];
+                    const double m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
+                    const double s1 = e11 - m11, s2 = e22 - m22, s12 = e12 - m12;
+                    acc += ((2.0 * m12 + C1) * (2.0 * s12 + C2)) / ((m11 + m22 + C1) * (s1 + s2 + C2));
                 }
             }
     }
@@ -246,20 +254,20 @@ int pcc_matrix_launch(const float* pred, const float* truth, int N, int M, int64
 
 int64_t ssim_pairs_ws_bytes(int N, int M, int C, int H, int W) {
     if (N < 1 || M < 1 || C < 1 || H < 1 || W < 1) return -1;
-    return 2 * align256((int64_t)(N + M) * C * H * W * 4);
+    return 2 * align256((int64_t)(N + M) * C * H * W * 8);
 }
 
 int ssim_pairs_launch(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
                       float* out, void* ws, int64_t ws_bytes, hipStream_t st) {
     if (ws_bytes < ssim_pairs_ws_bytes(N, M, C, H, W)) return E_WORKSPACE;
     if (P == 0) return OK;
-    const int64_t one = align256((int64_t)(N + M) * C * H * W * 4);
-    float* mu = (float*)ws;
-    float* ex = (float*)((char*)ws + one);
+    const int64_t one = align256((int64_t)(N + M) * C * H * W * 8);
+    double* mu = (double*)ws;
+    double* ex = (double*)((char*)ws + one);
     hipLaunchKernelGGL(ident_ssim_stats_kernel, dim3((N + M) * C, (H + SS_TS - 1) / SS_TS, (W + SS_TS - 1) / SS_TS),
                        dim3(256), 0, st, pred, N, truth, C, H, W, mu, ex);
     hipLaunchKernelGGL(ident_ssim_pair_kernel, dim3(P), dim3(256), 0, st, pred, N, truth, M, C, H, W, pairs,
-                       (const float*)mu, (const float*)ex, out);
+                       (const double*)mu, (const double*)ex, out);
     return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
 }
 

@@ -11,7 +11,13 @@ pairwise similarities computed by csrc/ident.hip through the C ABI (include/fmri
 
 Images are GPU tensors [N, C, H, W]: a CPU tensor is a RuntimeError, there is no eager fallback.  A pair's value is a
 bitwise function of the two images (include/fmri_hip.h), so the strict ``>`` of the reference counts as on the host,
-also for a batch that holds the same stimulus twice.
+also for a batch that holds the same stimulus twice.  An empty batch (N = 0 or M = 0) gives empty results.
+
+Degenerate images.  A NaN image gives NaN PCC and SSIM in its row or column, as in the reference, so it is never a hit.
+A constant image has zero variance: its PCC is 0 / 0 = NaN and never a hit.  The reference agrees when the constant's
+fp32 mean is exact (0.5, -1.0).  When it is not (0.1), the reference's fp32 ``torch.mean`` is off by a rounding error and
+its PCC is rounding noise (|PCC| up to about 1e-7) instead of NaN; the engine's fp64 row mean of a constant row is the
+constant itself, so it stays NaN.  SSIM of a constant image is finite.
 """
 from __future__ import annotations
 
@@ -53,7 +59,7 @@ def _workspace(nbytes: int, what: str, device) -> torch.Tensor:
 def pcc_matrix(pred: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
     """S[i, j] = PearsonCorrelation(pred[i], truth[j]) as fp32 [N, M] on the device."""
     a, b = _pair_of_batches(pred, truth)
-    N, M, D = a.shape[0], b.shape[0], a[0].numel()
+    N, M, D = a.shape[0], b.shape[0], a.shape[1:].numel()
     S = torch.empty(N, M, dtype=torch.float32, device=a.device)
     if N == 0 or M == 0:
         return S
@@ -129,8 +135,8 @@ def n_way(pred: torch.Tensor, truth: torch.Tensor, distractors) -> torch.Tensor:
     if d.dim() != 2 or d.shape[0] != N or d.dtype.is_floating_point or d.dtype == torch.bool:
         raise ValueError(f"distractors must be an integer tensor [N={N}, top - 1], got {d.dtype} {tuple(d.shape)}")
     k = d.shape[1]
-    if k == 0:
-        return torch.ones(N, 2, dtype=torch.bool, device=a.device)
+    if k == 0 or N == 0:
+        return torch.full((N, 2), k == 0, dtype=torch.bool, device=a.device)
     if d.is_cuda:
         lo, hi = d.min().item(), d.max().item()
     else:
