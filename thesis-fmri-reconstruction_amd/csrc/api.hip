@@ -288,86 +288,268 @@ int fmri_igemm_route(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int CoStore,
     return FMRI_OK;
 }
 
-int fmri_igemm_ep(const void* in, const void* w, void* out, const float* bias, const void* zero16, int N, int Hi,
-                  int Wi, int Ci, int Ho, int Wo, int CoStore, int Co, int k, int stride, int pad, int mode, int act,
-                  int out_f32, int splits, int64_t slab_stride, int bn_tile, int64_t w_elems, const fmri_epilogue* ep,
-                  int* ep_done, void* stream) {
-    if (ep_done) *ep_done = 0;
-    if (!in || !w || !out || !zero16) return FMRI_E_BADARG;
-    StatEpi se;
-    se.part = nullptr; se.rows_cap = 0; se.C = CoStore; se.group_n = 0;
-    se.tpg[0] = se.tpg[1] = se.tpg[2] = se.tpg[3] = 0;
-    BnBwdEpi bb;
-    memset(&bb, 0, sizeof(bb));
+// kill switch of a kernel family: FMRI_<family>=off (only "off") disables it; call sites keep the answer in a static
+static bool family_off(const char* var) { const char* v = getenv(var); return v && !strcmp(v, "off"); }
+// What the family selectors route a validated fmri_igemm_ep call on besides the tap-list kernel's arguments a (a.st,
+// a.bb: the statistics and BatchNorm-backward epilogues as the caller requested them).
+struct IgemmReq {
     AffEpi aff;
-    memset(&aff, 0, sizeof(aff));
-    if (ep && ep->aff_scale) {
-        if (!ep->aff_shift || ep->stat_part || bias || act != FMRI_ACT_NONE || out_f32) return FMRI_E_BADARG;
-        aff.scale = ep->aff_scale; aff.shift = ep->aff_shift; aff.relu = ep->aff_relu ? 1 : 0;
+    const half_t* act_y;
+    int mode, k, stride, pad, bn_tile, copad, maxM;
+    bool out_f32;
+    int64_t w_elems;
+    int* ep_done;
+    hipStream_t st;
+};
+// Statistics-row planner (StatEpi): a block writes one row per statistics group it covers, so the group_n images of a
+// group (0: one group of all ntiles tiles) must fill whole tiles of ipt images (tpi tiles per ipt images) and whole
+// blocks of tpb tiles (the caller picks tpb), and a group's rows (mult per block) must fit rows_cap.  Sets st.tpg[cls]
+// to the rows per group; false: statistics were requested and do not fit.  The caller's decline policy is
+// plain_output(), or E_UNSUPPORTED to leave the call to the narrower family.
+static bool plan_stat_rows(StatEpi& st, int cls, int64_t group_n, int64_t ipt, int64_t tpi, int64_t ntiles, int tpb, int mult) {
+    if (!st.part) return true;
+    const int64_t tiles = group_n > 0 ? (group_n + ipt - 1) / ipt * tpi : ntiles;
+    st.tpg[cls] = (int)((tiles + tpb - 1) / tpb) * mult;
+    return group_n % ipt == 0 && st.tpg[cls] <= st.rows_cap;
+}
+// decline policy of the narrow forms: no statistics rows, no BatchNorm-backward masking (*ep_done = 0 tells the caller)
+static void plain_output(StatEpi& st, BnBwdEpi& bb) { st.part = nullptr; bb.x = nullptr; }
+// *ep_done after a launch: statistics rows per group (summed over the classes; 0: none) | flags of the epilogues applied
+static int ep_report(int r, int* ep_done, const StatEpi* st, const float* aff_scale, const half_t* relu_y) {
+    if (r == OK && ep_done)
+        *ep_done = (st && st->part ? st->tpg[0] + st->tpg[1] + st->tpg[2] + st->tpg[3] : 0) |
+                   (aff_scale ? FMRI_EP_AFFINE_APPLIED : 0) | (relu_y ? FMRI_EP_ACT_APPLIED : 0);
+    return r;
+}
+// The class geometry of a k5 p2 stride-2 transposed convolution that igemm_tc5 and igemm_tc32 hard-wire: class i writes
+// output parity (i >> 1, i & 1); parity-0 classes have 3 taps from input offset +1 downwards, parity-1 classes 2 taps.
+static bool k5p2_classes(const IgemmArgs& a) {
+    for (int i = 0; i < 4; ++i) {
+        const IgemmClass& s = a.cls[i];
+        if (s.T / s.TW != ((i >> 1) ? 2 : 3) || s.TW != ((i & 1) ? 2 : 3) || s.dy0 != 1 || s.dx0 != 1 || s.dstep != -1 ||
+            s.oy0 != (i >> 1) || s.ox0 != (i & 1) || s.Kpad < s.T * a.Ci)
+            return false;
     }
-    if (ep && ep->stat_part) {
-        if (ep->stat_rows_cap < 1 || ep->stat_group_n < 0 || out_f32 || (ep->stat_group_n > 0 && N % ep->stat_group_n))
-            return FMRI_E_BADARG;
-        se.part = ep->stat_part; se.rows_cap = ep->stat_rows_cap; se.group_n = ep->stat_group_n;
-        if (ep->bn_x) {
-            // BatchNorm backward: <= 4 groups, every used group fully described; no bias / activation
-            const int groups = se.group_n > 0 ? N / se.group_n : 1;
-            if (groups > 4 || !ep->bn_gamma || !ep->bn_beta || bias || act != FMRI_ACT_NONE || Co != CoStore)
-                return FMRI_E_BADARG;
-            bb.x = (const half_t*)ep->bn_x; bb.gamma = ep->bn_gamma; bb.beta = ep->bn_beta; bb.relu = ep->bn_relu;
-            for (int i = 0; i < groups; ++i) {
-                if (!ep->bn_mean[i] || !ep->bn_rstd[i] || ep->bn_x_img0[i] < 0) return FMRI_E_BADARG;
-                bb.mean[i] = ep->bn_mean[i]; bb.rstd[i] = ep->bn_rstd[i]; bb.x_img0[i] = ep->bn_x_img0[i];
-            }
+    return true;
+}
+
+// Every family selector below returns its launcher's code, or E_UNSUPPORTED to pass the call on to the next family.
+// 5x5 stride-1 convolutions between 3(8)- and 32-channel maps -> register-resident-weight kernel
+// (csrc/igemm_narrow.hip); FMRI_NARROW=off disables
+static int select_narrow(const IgemmArgs& a, const IgemmReq& r) {
+    static const bool off = family_off("FMRI_NARROW");
+    const int co_tiles = a.Co <= 16 ? 1 : 2;
+    if (off || (r.mode != FMRI_CONV && r.mode != FMRI_CONV_FLIP) || r.stride != 1 || r.k != 5 || r.pad != 2 ||
+        !(a.Ci == 8 || (a.Ci == 32 && co_tiles == 1)) || a.Co > 32 || r.out_f32 || a.splits != 1 || a.Hi != a.Ho ||
+        a.Wi != a.Wo || (int64_t)a.N * a.Hi * a.Wi * 32 >= 0x7fffffffLL || r.copad < co_tiles * 16 ||
+        a.cls[0].Kpad < (a.Ci == 32 ? 800 : 224))
+        return E_UNSUPPORTED;
+    NarrowArgs q;
+    q.in = a.in; q.w = a.w + a.cls[0].w_off; q.out = (half_t*)a.out; q.bias = a.bias;
+    q.N = a.N; q.H = a.Hi; q.W = a.Wi; q.CoStore = a.CoStore; q.Co = a.Co; q.Kpad = a.cls[0].Kpad; q.act = a.act;
+    q.tiles_y = (a.Hi + 15) / 16; q.tiles_x = (a.Wi + 15) / 16; q.ntiles = a.N * q.tiles_y * q.tiles_x;
+    return igemm_narrow_launch(q, a.Ci, co_tiles, r.mode == FMRI_CONV_FLIP, r.st);
+}
+// wide form of the c5 family (csrc/igemm_c5w.hip): 16 x 16-pixel tiles of one image or 8 x 8-pixel tiles of four, one
+// 8-wave block per CU, loader / compute waves; FMRI_C5W=off disables.  n: the narrow form's arguments
+static int select_c5w(const IgemmArgs& a, const IgemmReq& r, const C5Args& n) {
+    static const bool off = family_off("FMRI_C5W");
+    // (gated on the caller's REQUEST for the BatchNorm-backward epilogue, bb.x: the wide kernel has none, and the narrow
+    // form clears its bb.x when its rows do not fit -- the wide form, needing fewer rows, would then emit FORWARD
+    // statistics rows that the caller reads as (sum g, sum g*xhat))
+    if (off || a.bb.x || (n.pw16 && a.Ho <= 8)) return E_UNSUPPORTED;
+    C5Args w = n;
+    const int ipb = n.pw16 ? 1 : 4, ph = n.pw16 ? 16 : 8, ncol = r.copad / 128, group_n = n.st.group_n;
+    w.tiles_y = (a.Ho + ph - 1) / ph;
+    w.ntiles = ((a.N + ipb - 1) / ipb) * w.tiles_y * w.tiles_x;
+    w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
+    const int tpg = group_n > 0 ? (group_n / ipb) * w.tiles_y * w.tiles_x : w.ntiles;
+    // whole rounds of one block per CU, statistics groups not sharing a block
+    w.tpb = 1;
+    for (int t = (w.ntiles * ncol) / 256; t > 1; --t)
+        if (tpg % t == 0 && w.ntiles % t == 0 && ((w.ntiles / t) * ncol) % 256 == 0) { w.tpb = t; break; }
+    if (!plan_stat_rows(w.st, 0, group_n, ipb, w.tiles_y * w.tiles_x, w.ntiles, w.tpb, 1)) return E_UNSUPPORTED;
+    w.aff = r.aff;
+    return ep_report(igemm_c5w_launch(w, r.copad, r.st), r.ep_done, &w.st, w.aff.scale, nullptr);
+}
+// stride-2 convolution k5 p2, Ci % 32 == 0, 128-channel tiles, no bias / activation -> window-resident kernels: the wide
+// form, then csrc/igemm_c5.hip; FMRI_C5=off disables both
+static int select_c5(const IgemmArgs& a, const IgemmReq& r) {
+    static const bool off = family_off("FMRI_C5");
+    const IgemmClass& c = a.cls[0];
+    if (off || r.mode != FMRI_CONV || r.stride != 2 || r.k != 5 || r.pad != 2 || (a.Ci & 31) || r.bn_tile != 128 ||
+        r.out_f32 || a.splits != 1 || a.bias || a.act != FMRI_ACT_NONE ||
+        a.Ho != (a.Hi - 1) / 2 + 1 || a.Wo != (a.Wi - 1) / 2 + 1 || c.Kpad < 25 * a.Ci ||
+        (int64_t)a.N * a.Hi * a.Wi * a.Ci * 2 >= 0x7fffffffLL || (int64_t)r.copad * c.Kpad * 2 >= 0xffffffffLL ||
+        (r.w_elems != 0 && r.w_elems < (int64_t)r.copad * c.Kpad))
+        return E_UNSUPPORTED;
+    C5Args q;
+    memset(&q, 0, sizeof(q));      // no affine epilogue
+    q.in = a.in; q.w = a.w + c.w_off; q.out = (half_t*)a.out;
+    q.N = a.N; q.Hi = a.Hi; q.Wi = a.Wi; q.Ci = a.Ci; q.Ho = a.Ho; q.Wo = a.Wo; q.CoStore = a.CoStore; q.Co = a.Co;
+    q.Kpad = c.Kpad; q.nsub = a.Ci / 32;
+    q.pw16 = a.Wo > 8 ? 1 : 0;
+    const int ipb = q.pw16 ? 1 : 2;
+    q.tiles_x = q.pw16 ? (a.Wo + 15) / 16 : 1;
+    q.tiles_y = (a.Ho + 7) / 8;
+    q.ntiles = ((a.N + ipb - 1) / ipb) * q.tiles_y * q.tiles_x;
+    q.in_bytes = (uint32_t)((int64_t)a.N * a.Hi * a.Wi * a.Ci * 2);
+    q.w_bytes = (uint32_t)((int64_t)r.copad * q.Kpad * 2);
+    q.fdTPI = make_fastdiv((uint32_t)(q.tiles_y * q.tiles_x));
+    q.fdTX = make_fastdiv((uint32_t)q.tiles_x);
+    q.st = a.st; q.bb = a.bb;
+    // persistent blocks: tpb consecutive tiles each when that makes whole rounds of 2 blocks per CU
+    q.tpb = (q.ntiles * (r.copad / 128)) / 512;      // whole rounds only: fewer, longer blocks leave CUs idle
+    if (q.tpb < 1) q.tpb = 1;
+    const int rw = select_c5w(a, r, q);
+    if (rw != E_UNSUPPORTED) return rw;
+    // statistics: one row per block; the blocks of a group's tiles must not reach into the next group
+    const int group_n = q.st.group_n, tpi = q.tiles_y * q.tiles_x;
+    if (q.st.part && group_n > 0 && group_n % ipb == 0)
+        while (((group_n / ipb) * tpi) % q.tpb) --q.tpb;
+    if (!plan_stat_rows(q.st, 0, group_n, ipb, tpi, q.ntiles, q.tpb, 1)) plain_output(q.st, q.bb);
+    return ep_report(igemm_c5_launch(q, r.copad, r.st), r.ep_done, &q.st, nullptr, nullptr);
+}
+// wide form of the tc5 family (csrc/igemm_tc5w.hip): 16 x 16-position tiles, one 8-wave block per CU, loader / compute
+// waves; FMRI_TC5W=off disables.  n: the narrow form's arguments
+static int select_tc5w(const IgemmArgs& a, const IgemmReq& r, const Tc5Args& n) {
+    static const bool off = family_off("FMRI_TC5W");
+    const int Yc0 = a.cls[0].Yc, Xc0 = a.cls[0].Xc;
+    const bool wide16 = Xc0 > 8 && Yc0 > 8;
+    const bool wide8 = Xc0 <= 8 && Yc0 <= 8 && a.Hi <= 8 && a.Wi <= 8;
+    if (off || r.bn_tile != 128 || !(wide16 || wide8) || a.bb.x || (n.nchunks & 1)) return E_UNSUPPORTED;  // bb.x: as c5w
+    Tc5Args w = n;
+    if (wide16) {
+        w.pw_log2 = 4; w.ph_log2 = 4; w.PH = 16; w.IPB = 1; w.IH = 18; w.IW = 18; w.nslice = 11;
+        w.tiles_x = (Xc0 + 15) / 16;
+        w.tiles_y = (Yc0 + 15) / 16;
+        w.ntiles = a.N * w.tiles_y * w.tiles_x;
+    } else {
+        w.pw_log2 = 3; w.ph_log2 = 3; w.PH = 8; w.IPB = 4; w.IH = 10; w.IW = 10; w.nslice = 13;
+        w.tiles_x = w.tiles_y = 1;
+        w.ntiles = (a.N + 3) / 4;
+    }
+    w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
+    w.fdTX = make_fastdiv((uint32_t)w.tiles_x);
+    // few tiles (at most 128 tile x column-block pairs): one parity class per block, grid.z = 4, one row per class block
+    w.solo = w.ntiles * (r.copad / 128) <= 128 ? 1 : 0;
+    if (!plan_stat_rows(w.st, 0, w.st.group_n, w.IPB, w.tiles_y * w.tiles_x, w.ntiles, 1, w.solo ? 4 : 1))
+        return E_UNSUPPORTED;
+    w.aff = r.aff;
+    return ep_report(igemm_tc5w_launch(w, r.copad, r.st), r.ep_done, &w.st, w.aff.scale, nullptr);
+}
+// stride-2 transposed convolution k5 p2, Ci % 128 == 0, >= 64 output channels, no bias / activation: all four parity
+// classes per block -- the wide form, then csrc/igemm_tc5.hip; FMRI_TC5=off disables both
+static int select_tc5(const IgemmArgs& a, const IgemmReq& r) {
+    static const bool off = family_off("FMRI_TC5");
+    if (off || r.mode != FMRI_TCONV2 || r.k != 5 || r.pad != 2 || (a.Ci & 127) || r.bn_tile < 64 || r.out_f32 ||
+        a.splits != 1 || a.bias || a.act != FMRI_ACT_NONE || r.w_elems <= 0 || r.w_elems * 2 >= 0xffffffffLL ||
+        (int64_t)a.N * a.Hi * a.Wi * a.Ci * 2 >= 0x7fffffffLL || !k5p2_classes(a))
+        return E_UNSUPPORTED;
+    Tc5Args q;
+    memset(&q, 0, sizeof(q));      // no bias, affine epilogue or one-class-per-block form
+    q.in = a.in; q.w = a.w; q.out = (half_t*)a.out;
+    q.N = a.N; q.Hi = a.Hi; q.Wi = a.Wi; q.Ci = a.Ci; q.Ho = a.Ho; q.Wo = a.Wo; q.CoStore = a.CoStore; q.Co = a.Co;
+    q.act = a.act; q.nchunks = a.Ci / 64;
+    for (int i = 0; i < 4; ++i) {
+        if (a.cls[i].w_off + (int64_t)r.copad * a.cls[i].Kpad > r.w_elems) return E_UNSUPPORTED;
+        q.cls[i] = {a.cls[i].Yc, a.cls[i].Xc, a.cls[i].Kpad, 0, a.cls[i].w_off};
+    }
+    const int Yc0 = a.cls[0].Yc, Xc0 = a.cls[0].Xc;          // class (0, 0) has the largest grid
+    q.pw_log2 = Xc0 > 8 ? 4 : 3;
+    q.ph_log2 = (q.pw_log2 == 3 && Yc0 > 8) ? 4 : 3;
+    q.PH = 1 << q.ph_log2;
+    q.IPB = 128 >> (q.pw_log2 + q.ph_log2);
+    q.IH = q.PH + 2;
+    q.IW = (1 << q.pw_log2) + 2;
+    q.tiles_x = (Xc0 + (1 << q.pw_log2) - 1) >> q.pw_log2;
+    q.tiles_y = (Yc0 + q.PH - 1) >> q.ph_log2;
+    q.ntiles = Yc0 > 0 && Xc0 > 0 ? ((a.N + q.IPB - 1) / q.IPB) * q.tiles_y * q.tiles_x : 0;
+    q.nslice = (q.IPB * q.IH * q.IW * 8 + 255) / 256;
+    // whole class grid (and input) inside one 8 x 8 tile per image: the window's halo is all padding -> dense form
+    if (q.IPB == 2 && q.tiles_x == 1 && q.tiles_y == 1 && a.Hi <= 8 && a.Wi <= 8) q.nslice = 4;
+    q.in_bytes = (uint32_t)((int64_t)a.N * a.Hi * a.Wi * a.Ci * 2);
+    q.w_bytes = (uint32_t)(r.w_elems * 2);
+    q.fdTPI = make_fastdiv((uint32_t)(q.tiles_y * q.tiles_x));
+    q.fdTX = make_fastdiv((uint32_t)q.tiles_x);
+    q.fdIHW = make_fastdiv((uint32_t)(q.IH * q.IW));
+    q.fdIW = make_fastdiv((uint32_t)q.IW);
+    q.st = a.st; q.bb = a.bb;
+    const int rw = select_tc5w(a, r, q);
+    if (rw != E_UNSUPPORTED || q.ntiles < 1) return rw;
+    // statistics: one row per tile
+    if (!plan_stat_rows(q.st, 0, q.st.group_n, q.IPB, q.tiles_y * q.tiles_x, q.ntiles, 1, 1)) plain_output(q.st, q.bb);
+    return ep_report(igemm_tc5_launch(q, r.bn_tile, r.copad, r.st), r.ep_done, &q.st, nullptr, nullptr);
+}
+// stride-2 transposed convolution 128 -> <= 32 channels -> persistent register-resident-weight kernel
+// (csrc/igemm_tc32.hip); FMRI_TC32=off disables
+static int select_tc32(const IgemmArgs& a, const IgemmReq& r) {
+    static const bool off = family_off("FMRI_TC32");
+    const int tiles_y = (a.cls[0].Yc + 7) / 8, tiles_x = (a.cls[0].Xc + 15) / 16;     // class (0,0) has the largest grid
+    if (off || r.mode != FMRI_TCONV2 || a.Ci != 128 || a.CoStore > 32 || r.out_f32 || a.splits != 1 ||
+        (int64_t)a.N * a.Hi * a.Wi * 128 >= 0x7fffffffLL || r.copad < 32 || r.k != 5 || r.pad != 2 || !k5p2_classes(a) ||
+        a.N * tiles_y * tiles_x < 1)
+        return E_UNSUPPORTED;
+    Tc32Args q;
+    q.in = a.in; q.w = a.w; q.out = (half_t*)a.out; q.bias = a.bias;
+    q.N = a.N; q.Hi = a.Hi; q.Wi = a.Wi; q.Ho = a.Ho; q.Wo = a.Wo; q.CoStore = a.CoStore; q.Co = a.Co; q.act = a.act;
+    for (int i = 0; i < 4; ++i) q.cls[i] = {a.cls[i].Yc, a.cls[i].Xc, a.cls[i].Kpad, 0, a.cls[i].w_off};
+    q.tiles_y = tiles_y; q.tiles_x = tiles_x; q.ntiles = a.N * tiles_y * tiles_x;
+    q.relu_y = r.act_y;
+    const int begin = q.ntiles < 256 ? q.ntiles : 256;                          // one persistent block per CU
+    // E_UNSUPPORTED: bias / activation epilogue
+    return ep_report(igemm_tc32_launch(q, begin, r.st), r.ep_done, nullptr, nullptr, q.relu_y);
+}
+// generic tap-list kernel (csrc/igemm.hip): one statistics row per row tile of bm output positions, so the planner's
+// images are a class's output positions here -- a tile must not straddle two statistics groups
+static int select_generic(IgemmArgs& a, const IgemmReq& r) {
+    if (a.st.part) {
+        const int bm = igemm_bm(a, r.maxM, r.bn_tile, r.copad, false);
+        bool fits = true;
+        int rows = 0;
+        for (int i = 0; i < a.ncls; ++i) {
+            const IgemmClass& c = a.cls[i];
+            fits &= plan_stat_rows(a.st, i, (int64_t)a.st.group_n * c.Yc * c.Xc, bm, 1, ((int64_t)c.M + bm - 1) / bm, 1, 1);
+            rows += a.st.tpg[i];
         }
-    } else if (ep && ep->bn_x) {
-        return FMRI_E_BADARG;
+        if (!fits || rows > a.st.rows_cap) plain_output(a.st, a.bb);
     }
-    if (N < 1 || Ci < 8 || (Ci & 7) || CoStore < 4 || (CoStore & 3) || Co < 1 || Co > CoStore) return FMRI_E_BADARG;
-    if (bn_tile != 32 && bn_tile != 64 && bn_tile != 128) return FMRI_E_UNSUPPORTED;
-    if (splits < 1) return FMRI_E_BADARG;
-    if (splits > 1 && !out_f32) return FMRI_E_BADARG;
-    const int copad = pad_to(Co, bn_tile);
-    if (copad < CoStore) return FMRI_E_BADARG;   // every stored channel must be covered by a tile
-    IgemmArgs a;
-    a.in = (const half_t*)in; a.w = (const half_t*)w; a.out = out; a.bias = bias; a.zero = (const half_t*)zero16;
-    a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci; a.Ho = Ho; a.Wo = Wo; a.CoStore = CoStore; a.Co = Co;
-    a.act = act; a.splits = splits; a.slab_stride = slab_stride;
-    a.st = se; a.st.part = nullptr;
-    a.bb = bb;
-    a.fdCi = make_fastdiv((uint32_t)Ci);
-    a.fdCpt = make_fastdiv((uint32_t)(Ci >= 64 ? Ci / 64 : 1));
-    int maxM = 0;
+    return ep_report(igemm_launch(a, r.maxM, r.bn_tile, r.copad, r.out_f32, r.st), r.ep_done, &a.st, nullptr, nullptr);
+}
+
+// the output-pixel classes of the contraction: one for a convolution, the four parity classes of a stride-2 transposed
+// convolution; *maxM = the rows of the largest
+static int igemm_classes(IgemmArgs& a, int mode, int k, int stride, int pad, int copad, int* maxM) {
+    *maxM = 0;
     auto set_class = [&](IgemmClass& c, int Yc, int Xc, int oy0, int ox0, int TH, int TW, int dy0, int dx0, int dstep,
                          int kpad, int64_t w_off) -> bool {
         c.Yc = Yc; c.Xc = Xc; c.oy0 = oy0; c.ox0 = ox0; c.T = TH * TW; c.TW = TW;
         c.dy0 = dy0; c.dx0 = dx0; c.dstep = dstep;
-        const int64_t M = (int64_t)N * Yc * Xc;
+        const int64_t M = (int64_t)a.N * Yc * Xc;
         if (M > 0x7fffff00LL) return false;
         c.M = (int)(M > 0 ? M : 0);
         c.Kpad = kpad; c.ksteps = kpad / 64; c.w_off = w_off;
         c.fdX = make_fastdiv((uint32_t)(Xc > 0 ? Xc : 1));
         c.fdYX = make_fastdiv((uint32_t)(Yc * Xc > 0 ? Yc * Xc : 1));
         c.fdTW = make_fastdiv((uint32_t)TW);
-        if (c.M > maxM) maxM = c.M;
+        if (c.M > *maxM) *maxM = c.M;
         return true;
     };
     if (mode == FMRI_CONV || mode == FMRI_CONV_FLIP) {
         if (mode == FMRI_CONV_FLIP && stride != 1) return FMRI_E_UNSUPPORTED;
         a.s = stride; a.os = 1; a.ncls = 1;
-        const int d0 = mode == FMRI_CONV ? -pad : pad;
-        const int ds = mode == FMRI_CONV ? 1 : -1;
-        if (!set_class(a.cls[0], Ho, Wo, 0, 0, k, k, d0, d0, ds, pad_to(k * k * Ci, 64), 0)) return FMRI_E_BADARG;
+        const int d0 = mode == FMRI_CONV ? -pad : pad, ds = mode == FMRI_CONV ? 1 : -1;
+        if (!set_class(a.cls[0], a.Ho, a.Wo, 0, 0, k, k, d0, d0, ds, pad_to(k * k * a.Ci, 64), 0)) return FMRI_E_BADARG;
         for (int i = 1; i < 4; ++i) a.cls[i] = a.cls[0];
     } else if (mode == FMRI_TCONV2) {
         if (stride != 2) return FMRI_E_UNSUPPORTED;
         a.s = 1; a.os = 2; a.ncls = 4;
         TClass tc[4];
-        tconv_classes(k, pad, Ci, copad, tc);
+        tconv_classes(k, pad, a.Ci, copad, tc);
         for (int cy = 0; cy < 2; ++cy)
             for (int cx = 0; cx < 2; ++cx) {
                 const TClass& t = tc[cy * 2 + cx];
-                const int Yc = (Ho - cy + 1) / 2, Xc = (Wo - cx + 1) / 2;
+                const int Yc = (a.Ho - cy + 1) / 2, Xc = (a.Wo - cx + 1) / 2;
                 if (!set_class(a.cls[cy * 2 + cx], Yc, Xc, cy, cx, t.th, t.tw, t.dy0, t.dx0, -1, t.kpad, t.w_off))
                     return FMRI_E_BADARG;
             }
@@ -376,252 +558,65 @@ int fmri_igemm_ep(const void* in, const void* w, void* out, const float* bias, c
     }
     // no empty split: every split must own >= 1 K-step in every class
     for (int i = 0; i < a.ncls; ++i) {
-        const int per = (a.cls[i].ksteps + splits - 1) / splits;
-        if (per * (splits - 1) >= a.cls[i].ksteps && splits > 1) return FMRI_E_BADARG;
+        const int per = (a.cls[i].ksteps + a.splits - 1) / a.splits;
+        if (per * (a.splits - 1) >= a.cls[i].ksteps && a.splits > 1) return FMRI_E_BADARG;
     }
-    if (maxM == 0) return FMRI_OK;
-    // 5x5 stride-1 convolutions between 3(8)- and 32-channel maps -> register-resident-weight kernel
-    // (csrc/igemm_narrow.hip); FMRI_NARROW=off disables
-    static const char* nar_env = getenv("FMRI_NARROW");
-    static const bool no_narrow = nar_env && !strcmp(nar_env, "off");
-    if (!no_narrow && (mode == FMRI_CONV || mode == FMRI_CONV_FLIP) && stride == 1 && k == 5 && pad == 2 &&
-        (Ci == 8 || Ci == 32) && Co <= 32 && !out_f32 && splits == 1 && Hi == Ho && Wi == Wo &&
-        (int64_t)N * Hi * Wi * 32 < 0x7fffffffLL) {
-        const int co_tiles = Co <= 16 ? 1 : 2;
-        if ((Ci == 32 && co_tiles == 1) || Ci == 8) {
-            NarrowArgs q;
-            q.in = a.in; q.w = a.w + a.cls[0].w_off; q.out = (half_t*)out; q.bias = bias;
-            q.N = N; q.H = Hi; q.W = Wi; q.CoStore = CoStore; q.Co = Co; q.Kpad = a.cls[0].Kpad; q.act = act;
-            q.tiles_y = (Hi + 15) / 16; q.tiles_x = (Wi + 15) / 16;
-            q.ntiles = N * q.tiles_y * q.tiles_x;
-            if (copad >= co_tiles * 16 && q.Kpad >= (Ci == 32 ? 800 : 224)) {
-                const int r = igemm_narrow_launch(q, Ci, co_tiles, mode == FMRI_CONV_FLIP, S(stream));
-                if (r != E_UNSUPPORTED) return r;
+    return FMRI_OK;
+}
+
+int fmri_igemm_ep(const void* in, const void* w, void* out, const float* bias, const void* zero16, int N, int Hi,
+                  int Wi, int Ci, int Ho, int Wo, int CoStore, int Co, int k, int stride, int pad, int mode, int act,
+                  int out_f32, int splits, int64_t slab_stride, int bn_tile, int64_t w_elems, const fmri_epilogue* ep,
+                  int* ep_done, void* stream) {
+    if (ep_done) *ep_done = 0;
+    if (!in || !w || !out || !zero16) return FMRI_E_BADARG;
+    IgemmArgs a;
+    AffEpi aff;
+    memset(&a, 0, sizeof(a));      // no statistics, BatchNorm backward or affine epilogue unless ep asks
+    memset(&aff, 0, sizeof(aff));
+    a.st.C = CoStore;
+    if (ep && ep->bn_x && !ep->stat_part) return FMRI_E_BADARG;
+    if (ep && ep->aff_scale) {
+        if (!ep->aff_shift || ep->stat_part || bias || act != FMRI_ACT_NONE || out_f32) return FMRI_E_BADARG;
+        aff.scale = ep->aff_scale; aff.shift = ep->aff_shift; aff.relu = ep->aff_relu ? 1 : 0;
+    }
+    if (ep && ep->stat_part) {
+        if (ep->stat_rows_cap < 1 || ep->stat_group_n < 0 || out_f32 || (ep->stat_group_n > 0 && N % ep->stat_group_n))
+            return FMRI_E_BADARG;
+        a.st.part = ep->stat_part; a.st.rows_cap = ep->stat_rows_cap; a.st.group_n = ep->stat_group_n;
+        if (ep->bn_x) {
+            // BatchNorm backward: <= 4 groups, every used group fully described; no bias / activation
+            const int groups = a.st.group_n > 0 ? N / a.st.group_n : 1;
+            if (groups > 4 || !ep->bn_gamma || !ep->bn_beta || bias || act != FMRI_ACT_NONE || Co != CoStore)
+                return FMRI_E_BADARG;
+            a.bb.x = (const half_t*)ep->bn_x; a.bb.gamma = ep->bn_gamma; a.bb.beta = ep->bn_beta; a.bb.relu = ep->bn_relu;
+            for (int i = 0; i < groups; ++i) {
+                if (!ep->bn_mean[i] || !ep->bn_rstd[i] || ep->bn_x_img0[i] < 0) return FMRI_E_BADARG;
+                a.bb.mean[i] = ep->bn_mean[i]; a.bb.rstd[i] = ep->bn_rstd[i]; a.bb.x_img0[i] = ep->bn_x_img0[i];
             }
         }
     }
-    // stride-2 convolution k5 p2, Ci % 32 == 0, 128-channel tiles, no bias / activation -> window-resident kernel
-    // (csrc/igemm_c5.hip); FMRI_C5=off disables
-    static const char* c5_env = getenv("FMRI_C5");
-    static const bool no_c5 = c5_env && !strcmp(c5_env, "off");
-    if (!no_c5 && mode == FMRI_CONV && stride == 2 && k == 5 && pad == 2 && (Ci & 31) == 0 && bn_tile == 128 &&
-        (copad & 127) == 0 && !out_f32 && splits == 1 && !bias && act == FMRI_ACT_NONE &&
-        Ho == (Hi - 1) / 2 + 1 && Wo == (Wi - 1) / 2 + 1 && a.cls[0].Kpad >= 25 * Ci &&
-        (int64_t)N * Hi * Wi * Ci * 2 < 0x7fffffffLL && (int64_t)copad * a.cls[0].Kpad * 2 < 0xffffffffLL &&
-        (w_elems == 0 || w_elems >= (int64_t)copad * a.cls[0].Kpad)) {
-        C5Args q;
-        q.in = a.in; q.w = a.w + a.cls[0].w_off; q.out = (half_t*)out;
-        q.N = N; q.Hi = Hi; q.Wi = Wi; q.Ci = Ci; q.Ho = Ho; q.Wo = Wo; q.CoStore = CoStore; q.Co = Co;
-        q.Kpad = a.cls[0].Kpad; q.nsub = Ci / 32;
-        q.pw16 = Wo > 8 ? 1 : 0;
-        const int ipb = q.pw16 ? 1 : 2;
-        q.tiles_x = q.pw16 ? (Wo + 15) / 16 : 1;
-        q.tiles_y = (Ho + 7) / 8;
-        q.ntiles = ((N + ipb - 1) / ipb) * q.tiles_y * q.tiles_x;
-        q.in_bytes = (uint32_t)((int64_t)N * Hi * Wi * Ci * 2);
-        q.w_bytes = (uint32_t)((int64_t)copad * q.Kpad * 2);
-        q.fdTPI = make_fastdiv((uint32_t)(q.tiles_y * q.tiles_x));
-        q.fdTX = make_fastdiv((uint32_t)q.tiles_x);
-        q.st = se;
-        // persistent blocks: tpb consecutive tiles each when that makes whole rounds of 2 blocks per CU
-        const int ncol = copad / 128;
-        q.tpb = (q.ntiles * ncol) / 512;      // whole rounds only: fewer, longer blocks leave CUs idle
-        if (q.tpb < 1) q.tpb = 1;
-        // statistics: one row per block; statistics groups must not share a tile, nor a block
-        const int tpg5 = se.group_n > 0 ? (se.group_n / ipb) * q.tiles_y * q.tiles_x : q.ntiles;
-        if (se.part && se.group_n > 0) {
-            if (se.group_n % ipb) q.st.part = nullptr;
-            else while (tpg5 % q.tpb) --q.tpb;
-        }
-        if (se.part) {
-            q.st.tpg[0] = (tpg5 + q.tpb - 1) / q.tpb;
-            if (q.st.tpg[0] > se.rows_cap) q.st.part = nullptr;
-        }
-        q.bb = bb;
-        if (!q.st.part) q.bb.x = nullptr;       // no statistics rows: plain output (*ep_done = 0 tells the caller)
-        memset(&q.aff, 0, sizeof(q.aff));
-        // wide form (csrc/igemm_c5w.hip): 16 x 16-pixel tiles of one image or 8 x 8-pixel tiles of four, one 8-wave block per
-        // CU, loader / compute waves; FMRI_C5W=off disables
-        static const char* c5w_env = getenv("FMRI_C5W");
-        static const bool no_c5w = c5w_env && !strcmp(c5w_env, "off");
-        const int ipbw = q.pw16 ? 1 : 4;
-        // (gated on the caller's REQUEST for the BatchNorm-backward epilogue, bb.x: the wide kernel has none, and q.bb.x is
-        // also cleared when the narrow form's rows did not fit -- the wide form, needing fewer rows, would then emit
-        // FORWARD statistics rows that the caller reads as (sum g, sum g*xhat))
-        if (!no_c5w && !bb.x && (q.pw16 ? Ho > 8 : true) &&
-            !(se.part && se.group_n > 0 && (se.group_n % ipbw))) {
-            C5Args w = q;
-            const int ph = q.pw16 ? 16 : 8;
-            w.tiles_y = (Ho + ph - 1) / ph;
-            w.ntiles = ((N + ipbw - 1) / ipbw) * w.tiles_y * w.tiles_x;
-            w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
-            w.st = se;
-            const int tpgw = se.group_n > 0 ? (se.group_n / ipbw) * w.tiles_y * w.tiles_x : w.ntiles;
-            // whole rounds of one block per CU, statistics groups not sharing a block
-            w.tpb = 1;
-            for (int t = (w.ntiles * ncol) / 256; t > 1; --t)
-                if (tpgw % t == 0 && w.ntiles % t == 0 && ((w.ntiles / t) * ncol) % 256 == 0) { w.tpb = t; break; }
-            if (se.part) {
-                w.st.tpg[0] = (tpgw + w.tpb - 1) / w.tpb;
-                if (w.st.tpg[0] > se.rows_cap) w.st.part = nullptr;
-            }
-            if (w.st.part || !se.part) {
-                w.aff = aff;
-                const int r = igemm_c5w_launch(w, copad, S(stream));
-                if (r == OK && ep_done && w.st.part) *ep_done = w.st.tpg[0];
-                if (r == OK && ep_done && w.aff.scale) *ep_done |= FMRI_EP_AFFINE_APPLIED;
-                if (r != E_UNSUPPORTED) return r;
-            }
-        }
-        const int r = igemm_c5_launch(q, copad, S(stream));
-        if (r == OK && ep_done && q.st.part) *ep_done = q.st.tpg[0];
-        if (r != E_UNSUPPORTED) return r;
+    if (N < 1 || Ci < 8 || (Ci & 7) || CoStore < 4 || (CoStore & 3) || Co < 1 || Co > CoStore) return FMRI_E_BADARG;
+    if (bn_tile != 32 && bn_tile != 64 && bn_tile != 128) return FMRI_E_UNSUPPORTED;
+    if (splits < 1 || (splits > 1 && !out_f32)) return FMRI_E_BADARG;
+    const int copad = pad_to(Co, bn_tile);
+    if (copad < CoStore) return FMRI_E_BADARG;   // every stored channel must be covered by a tile
+    a.in = (const half_t*)in; a.w = (const half_t*)w; a.out = out; a.bias = bias; a.zero = (const half_t*)zero16;
+    a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci; a.Ho = Ho; a.Wo = Wo; a.CoStore = CoStore; a.Co = Co;
+    a.act = act; a.splits = splits; a.slab_stride = slab_stride;
+    a.fdCi = make_fastdiv((uint32_t)Ci);
+    a.fdCpt = make_fastdiv((uint32_t)(Ci >= 64 ? Ci / 64 : 1));
+    int maxM;
+    const int e = igemm_classes(a, mode, k, stride, pad, copad, &maxM);
+    if (e != FMRI_OK || maxM == 0) return e;
+    const IgemmReq r = {aff, ep ? (const half_t*)ep->act_y : nullptr, mode, k, stride, pad, bn_tile, copad, maxM,
+                        out_f32 != 0, w_elems, ep_done, S(stream)};
+    // the specialised families in order of preference, then the generic tap-list kernel
+    for (auto select : {select_narrow, select_c5, select_tc5, select_tc32}) {
+        const int ret = select(a, r);
+        if (ret != E_UNSUPPORTED) return ret;
     }
-    // stride-2 transposed convolution k5 p2, Ci % 128 == 0, >= 64 output channels, no bias / activation: all four parity
-    // classes per block (csrc/igemm_tc5.hip); FMRI_TC5=off disables
-    static const char* tc5_env = getenv("FMRI_TC5");
-    static const bool no_tc5 = tc5_env && !strcmp(tc5_env, "off");
-    if (!no_tc5 && mode == FMRI_TCONV2 && k == 5 && pad == 2 && (Ci & 127) == 0 && bn_tile >= 64 && !out_f32 &&
-        splits == 1 && !bias && act == FMRI_ACT_NONE && w_elems > 0 && w_elems * 2 < 0xffffffffLL &&
-        (int64_t)N * Hi * Wi * Ci * 2 < 0x7fffffffLL) {
-        Tc5Args q;
-        q.in = a.in; q.w = a.w; q.out = (half_t*)out; q.bias = nullptr;
-        q.N = N; q.Hi = Hi; q.Wi = Wi; q.Ci = Ci; q.Ho = Ho; q.Wo = Wo; q.CoStore = CoStore; q.Co = Co;
-        q.act = act; q.nchunks = Ci / 64;
-        bool ok = true;
-        for (int i = 0; i < 4; ++i) {
-            const IgemmClass& s = a.cls[i];
-            const int th = s.T / s.TW;
-            if (th != ((i >> 1) ? 2 : 3) || s.TW != ((i & 1) ? 2 : 3) || s.dy0 != 1 || s.dx0 != 1 || s.dstep != -1 ||
-                s.oy0 != (i >> 1) || s.ox0 != (i & 1) || s.Kpad < s.T * Ci)
-                ok = false;
-            q.cls[i].Yc = s.Yc; q.cls[i].Xc = s.Xc; q.cls[i].Kpad = s.Kpad; q.cls[i].pad0 = 0; q.cls[i].w_off = s.w_off;
-            if ((s.w_off + (int64_t)copad * s.Kpad) > w_elems) ok = false;
-        }
-        const int Yc0 = a.cls[0].Yc, Xc0 = a.cls[0].Xc;          // class (0, 0) has the largest grid
-        q.pw_log2 = Xc0 > 8 ? 4 : 3;
-        q.ph_log2 = (q.pw_log2 == 3 && Yc0 > 8) ? 4 : 3;
-        q.PH = 1 << q.ph_log2;
-        q.IPB = 128 >> (q.pw_log2 + q.ph_log2);
-        q.IH = q.PH + 2;
-        q.IW = (1 << q.pw_log2) + 2;
-        q.tiles_x = (Xc0 + (1 << q.pw_log2) - 1) >> q.pw_log2;
-        q.tiles_y = (Yc0 + q.PH - 1) >> q.ph_log2;
-        q.ntiles = Yc0 > 0 && Xc0 > 0 ? ((N + q.IPB - 1) / q.IPB) * q.tiles_y * q.tiles_x : 0;
-        q.nslice = (q.IPB * q.IH * q.IW * 8 + 255) / 256;
-        // whole class grid (and input) inside one 8 x 8 tile per image: the window's halo is all padding -> dense form
-        if (q.IPB == 2 && q.tiles_x == 1 && q.tiles_y == 1 && Hi <= 8 && Wi <= 8) q.nslice = 4;
-        q.in_bytes = (uint32_t)((int64_t)N * Hi * Wi * Ci * 2);
-        q.w_bytes = (uint32_t)(w_elems * 2);
-        q.fdTPI = make_fastdiv((uint32_t)(q.tiles_y * q.tiles_x));
-        q.fdTX = make_fastdiv((uint32_t)q.tiles_x);
-        q.fdIHW = make_fastdiv((uint32_t)(q.IH * q.IW));
-        q.fdIW = make_fastdiv((uint32_t)q.IW);
-        q.st = se;
-        q.bb = bb;
-        memset(&q.aff, 0, sizeof(q.aff));
-        q.solo = 0; q.pad_solo = 0;
-        // statistics: one row per tile; groups must not share a tile
-        const int tpi5 = q.tiles_y * q.tiles_x;
-        if (se.part) {
-            if (se.group_n > 0 && (se.group_n % q.IPB)) q.st.part = nullptr;
-            q.st.tpg[0] = se.group_n > 0 ? (se.group_n / q.IPB) * tpi5 : q.ntiles;
-            if (q.st.tpg[0] > se.rows_cap) q.st.part = nullptr;
-        }
-        if (!q.st.part) q.bb.x = nullptr;       // no statistics rows: plain output (*ep_done = 0 tells the caller)
-        // wide form (csrc/igemm_tc5w.hip): 16 x 16-position tiles, one 8-wave block per CU, loader / compute waves;
-        // FMRI_TC5W=off disables
-        static const char* tc5w_env = getenv("FMRI_TC5W");
-        static const bool no_tc5w = tc5w_env && !strcmp(tc5w_env, "off");
-        const bool wide16 = Xc0 > 8 && Yc0 > 8;
-        const bool wide8 = Xc0 <= 8 && Yc0 <= 8 && Hi <= 8 && Wi <= 8 && !(se.part && se.group_n > 0 && (se.group_n & 3));
-        if (ok && !no_tc5w && bn_tile == 128 && (wide16 || wide8) && !bb.x && !(q.nchunks & 1)) {      // bb.x: as above
-            Tc5Args w = q;
-            if (wide16) {
-                w.pw_log2 = 4; w.ph_log2 = 4; w.PH = 16; w.IPB = 1; w.IH = 18; w.IW = 18; w.nslice = 11;
-                w.tiles_x = (Xc0 + 15) / 16;
-                w.tiles_y = (Yc0 + 15) / 16;
-                w.ntiles = N * w.tiles_y * w.tiles_x;
-            } else {
-                w.pw_log2 = 3; w.ph_log2 = 3; w.PH = 8; w.IPB = 4; w.IH = 10; w.IW = 10; w.nslice = 13;
-                w.tiles_x = w.tiles_y = 1;
-                w.ntiles = (N + 3) / 4;
-            }
-            w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
-            w.fdTX = make_fastdiv((uint32_t)w.tiles_x);
-            w.st = se;
-            // few tiles (at most 128 tile x column-block pairs): one parity class per block, grid.z = 4
-            w.solo = w.ntiles * (copad / 128) <= 128 ? 1 : 0;
-            w.pad_solo = 0;
-            if (se.part) {
-                w.st.tpg[0] = (se.group_n > 0 ? (se.group_n / w.IPB) * w.tiles_y * w.tiles_x : w.ntiles) * (w.solo ? 4 : 1);
-                if (w.st.tpg[0] > se.rows_cap) w.st.part = nullptr;
-            }
-            if (w.st.part || !se.part) {
-                w.aff = aff;
-                const int r = igemm_tc5w_launch(w, copad, S(stream));
-                if (r == OK && ep_done && w.st.part) *ep_done = w.st.tpg[0];
-                if (r == OK && ep_done && w.aff.scale) *ep_done |= FMRI_EP_AFFINE_APPLIED;
-                if (r != E_UNSUPPORTED) return r;
-            }
-        }
-        if (ok && q.ntiles > 0) {
-            const int r = igemm_tc5_launch(q, bn_tile, copad, S(stream));
-            if (r == OK && ep_done && q.st.part) *ep_done = q.st.tpg[0];
-            if (r != E_UNSUPPORTED) return r;
-        }
-    }
-    // stride-2 transposed convolution 128 -> <= 32 channels -> persistent register-resident-weight kernel
-    // (csrc/igemm_tc32.hip); FMRI_TC32=off disables
-    static const char* tc_env = getenv("FMRI_TC32");
-    static const bool no_tc32 = tc_env && !strcmp(tc_env, "off");
-    if (!no_tc32 && mode == FMRI_TCONV2 && Ci == 128 && CoStore <= 32 && !out_f32 && splits == 1 &&
-        (int64_t)N * Hi * Wi * 128 < 0x7fffffffLL) {
-        Tc32Args q;
-        q.in = a.in; q.w = a.w; q.out = (half_t*)out; q.bias = bias;
-        q.N = N; q.Hi = Hi; q.Wi = Wi; q.Ho = Ho; q.Wo = Wo; q.CoStore = CoStore; q.Co = Co; q.act = act;
-        // the kernel hard-wires the k5 p2 class geometry: parity-0 classes have 3 taps from input offset +1 downwards,
-        // parity-1 classes 2 taps from +1 downwards
-        bool ok = copad >= 32 && k == 5 && pad == 2;
-        for (int i = 0; i < 4 && ok; ++i) {
-            const IgemmClass& s = a.cls[i];
-            Tc32Class& d = q.cls[i];
-            const int th = s.T / s.TW;
-            if (th != ((i >> 1) ? 2 : 3) || s.TW != ((i & 1) ? 2 : 3) || s.dy0 != 1 || s.dx0 != 1 || s.dstep != -1 ||
-                s.oy0 != (i >> 1) || s.ox0 != (i & 1) || s.Kpad < s.T * 128)
-                ok = false;
-            d.Yc = s.Yc; d.Xc = s.Xc; d.Kpad = s.Kpad; d.pad0 = 0; d.w_off = s.w_off;
-        }
-        q.tiles_y = (a.cls[0].Yc + 7) / 8; q.tiles_x = (a.cls[0].Xc + 15) / 16;     // class (0,0) has the largest grid
-        q.ntiles = N * q.tiles_y * q.tiles_x;
-        if (q.ntiles < 1) ok = false;
-        const int begin = q.ntiles < 256 ? q.ntiles : 256;                          // one persistent block per CU
-        q.relu_y = (ep && ep->act_y) ? (const half_t*)ep->act_y : nullptr;
-        if (ok) {
-            const int r = igemm_tc32_launch(q, begin, S(stream));       // E_UNSUPPORTED: bias / activation epilogue
-            if (r == OK && ep_done && q.relu_y) *ep_done |= FMRI_EP_ACT_APPLIED;
-            if (r != E_UNSUPPORTED) return r;
-        }
-    }
-    // generic kernel: statistics epilogue (one row per row tile) when no tile straddles two statistics groups
-    a.st = se;
-    int prows = 0;
-    if (se.part && !out_f32) {
-        const int bm = igemm_bm(a, maxM, bn_tile, copad, false);
-        for (int i = 0; i < a.ncls; ++i) {
-            const int64_t mg = se.group_n > 0 ? (int64_t)se.group_n * a.cls[i].Yc * a.cls[i].Xc : a.cls[i].M;
-            if (se.group_n > 0 && (mg % bm)) a.st.part = nullptr;
-            a.st.tpg[i] = (int)((mg + bm - 1) / bm);
-            prows += a.st.tpg[i];
-        }
-        if (prows > se.rows_cap) a.st.part = nullptr;
-    } else {
-        a.st.part = nullptr;
-    }
-    if (!a.st.part) a.bb.x = nullptr;           // no statistics rows: plain output (*ep_done = 0 tells the caller)
-    const int r = igemm_launch(a, maxM, bn_tile, copad, out_f32 != 0, S(stream));
-    if (r == OK && ep_done && a.st.part) *ep_done = prows;
-    return r;
+    return select_generic(a, r);
 }
 
 // K pieces (8 x 8 pixel tiles per block) of the four parity planes of fmri_wgrad's window kernel for a budget of `splits`
@@ -680,6 +675,86 @@ int fmri_wgrad(const void* P, const void* Q, float* out, const void* zero16, int
                          splits, atomic, stream);
 }
 
+// one fmri_wgrad_if call after validation
+struct WgradReq {
+    const int* gate; const half_t *P, *Q, *zero; float* out;
+    int N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, apad, ba_tile, ldo, splits, atomic;
+    hipStream_t st;
+};
+// stride-2 sampling, >= 128 rows, 32-channel column blocks, pre-zeroed fp32 output (atomic accumulation):
+// window-resident kernel (csrc/wgrad_win.hip).  FMRI_WGRAD_WIN=off disables.  False: not this kernel's call.
+static bool wgrad_win_args(const WgradReq& q, WgradWinArgs& w) {
+    static const bool off = family_off("FMRI_WGRAD_WIN");
+    const int64_t M = (int64_t)q.N * q.Yc * q.Xc;
+    if (off || q.stride != 2 || q.flip || (q.atomic != 1 && q.atomic != 2) || q.ba_tile != 128 || (q.Bc & 31) ||
+        q.Yc * q.Xc <= 1 || (int64_t)q.N * q.Hq * q.Wq * q.Bc >= 0x7fffffffLL || M * q.A >= 0x7fffffffLL)
+        return false;
+    for (int par = 0; par < 2; ++par) {
+        int cnt = 0, emin = 0;
+        for (int t = 0; t < q.k; ++t)
+            if (((t - q.pad) & 1) == par) { if (!cnt) emin = t - q.pad; ++cnt; }
+        if (cnt < 2 || cnt > 3) return false;
+        w.nsy[par] = w.nsx[par] = cnt;
+        w.tmin[par] = (emin - par) / 2;      // exact: emin and par have the same parity
+    }
+    w.gate = q.gate; w.P = q.P; w.Q = q.Q; w.out = q.out; w.zero = q.zero;
+    w.N = q.N; w.Yc = q.Yc; w.Xc = q.Xc; w.A = q.A; w.Hq = q.Hq; w.Wq = q.Wq; w.Bc = q.Bc; w.pad = q.pad; w.TW = q.k;
+    w.ldo = q.ldo; w.a_tiles = q.apad / 128;
+    w.slab_stride = q.atomic == 2 ? (int64_t)q.apad * q.ldo : 0;
+    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = q.N * w.tiles_y * w.tiles_x;
+    // `splits` = blocks per (row block, column block) over the 4 planes; K pieces per plane: wgrad_plane_pieces()
+    int tps4[4];
+    const int smax = wgrad_plane_pieces(q.N, q.Yc, q.Xc, q.k, q.pad, q.splits, tps4);  // = fmri_wgrad_slabs(): in slab mode
+    for (int pl = 0; pl < 4; ++pl) {                                                   // the caller sized the output with
+        w.plane_tps[pl] = tps4[pl];                                                    // it, and every allocated slab is
+        w.plane_pieces[pl] = (w.ntiles + tps4[pl] - 1) / tps4[pl];                     // written
+    }
+    w.splits = smax;
+    w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
+    w.fdTX = make_fastdiv((uint32_t)w.tiles_x);
+    return true;
+}
+// generic weight-gradient kernel (csrc/wgrad.hip)
+static int wgrad_generic(const WgradReq& q) {
+    WgradArgs a;
+    a.gate = q.gate; a.P = q.P; a.Q = q.Q; a.out = q.out; a.zero = q.zero;
+    a.N = q.N; a.Yc = q.Yc; a.Xc = q.Xc; a.A = q.A; a.Hq = q.Hq; a.Wq = q.Wq; a.Bc = q.Bc;
+    a.s = q.stride; a.T = q.k * q.k; a.TW = q.k;
+    a.dy0 = q.flip ? q.pad : -q.pad; a.dx0 = a.dy0; a.dstep = q.flip ? -1 : 1;
+    a.M = (int)((int64_t)q.N * q.Yc * q.Xc); a.ldo = q.ldo;
+    const int steps = (a.M + 63) / 64;
+    const int splits = q.splits > steps ? steps : q.splits;
+    a.steps_per_split = (steps + splits - 1) / splits;
+    a.splits = (steps + a.steps_per_split - 1) / a.steps_per_split;
+    // atomic == 4: per-split slabs of the generic kernel -- the caller allocated `splits` (as passed in) slabs of
+    // apad x ldo; the kernel writes every element of the first a.splits (<= splits) of them with plain stores, the
+    // rest stay as the caller left them (zero-filled)
+    a.atomic = q.atomic == 4 ? 2 : q.atomic;
+    a.slab_stride = (int64_t)q.apad * q.ldo;
+    a.ncol_chunks = a.T * q.Bc / 8;
+    a.fdX = make_fastdiv((uint32_t)q.Xc);
+    a.fdYX = make_fastdiv((uint32_t)(q.Yc * q.Xc));
+    a.fdTW = make_fastdiv((uint32_t)q.k);
+    a.fdBc8 = make_fastdiv((uint32_t)(q.Bc / 8));
+    return wgrad_launch(a, q.apad, q.ba_tile, q.st);
+}
+// 5x5 stride-1 layers between 32 and 3(8) channels, pre-zeroed output: wave-private window kernel
+// (csrc/wgrad_narrow.hip), the only one with the slabs of atomic = 3.  FMRI_WGRAD_NARROW=off disables.
+static int wgrad_narrow(const WgradReq& q) {
+    static const bool off = family_off("FMRI_WGRAD_NARROW");
+    if (off || !(q.stride == 1 && q.k == 5 && q.pad == 2 && q.A == 32 && q.Bc == 8 && q.apad == 32 && q.Yc == q.Hq &&
+                 q.Xc == q.Wq))
+        return FMRI_E_UNSUPPORTED;
+    if ((int64_t)q.N * q.Yc * q.Xc * 32 >= 0x7fffffffLL) return wgrad_generic(q);      // P beyond 2^31 elements
+    WgradNarrowArgs w;
+    w.gate = q.gate; w.P = q.P; w.Q = q.Q; w.out = q.out; w.zero = q.zero;
+    w.N = q.N; w.H = q.Yc; w.W = q.Xc; w.ldo = q.ldo; w.flip = q.flip;
+    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = q.N * w.tiles_y * w.tiles_x;
+    w.nslabs = q.splits < 1 ? 1 : q.splits; w.pad0 = 0;     // the caller allocated `splits` zeroed slabs of apad x ldo
+    w.slab_stride = (int64_t)q.apad * q.ldo;
+    return wgrad_narrow_launch(w, wgrad_narrow_blocks(q.N, q.Yc, q.Xc), q.st);
+}
+
 int fmri_wgrad_if(const int* gate, const void* P, const void* Q, float* out, const void* zero16, int N, int Yc, int Xc,
                   int A, int Hq, int Wq, int Bc, int k, int stride, int pad, int flip, int apad, int ba_tile, int ldo,
                   int splits, int atomic, void* stream) {
@@ -688,93 +763,18 @@ int fmri_wgrad_if(const int* gate, const void* P, const void* Q, float* out, con
     if (N < 1 || A < 8 || (A & 7) || Bc < 8 || (Bc & 7) || splits < 1) return FMRI_E_BADARG;
     if (ba_tile != 32 && ba_tile != 64 && ba_tile != 128) return FMRI_E_UNSUPPORTED;
     if (apad % ba_tile || apad < A) return FMRI_E_BADARG;
-    const int T = k * k;
-    if (ldo % 128 || ldo < T * Bc) return FMRI_E_BADARG;
+    if (ldo % 128 || ldo < k * k * Bc) return FMRI_E_BADARG;
     if (splits > 1 && !atomic) return FMRI_E_BADARG;
     if (atomic < 0 || atomic > 4) return FMRI_E_BADARG;
     const int64_t M = (int64_t)N * Yc * Xc;
     if (M < 1 || M > 0x7fffff00LL) return FMRI_E_BADARG;
-    // stride-2 sampling, >= 128 rows, 32-channel column blocks, pre-zeroed fp32 output (atomic accumulation):
-    // window-resident kernel (csrc/wgrad_win.hip).  FMRI_WGRAD_WIN=off disables.
-    static const char* ww_env = getenv("FMRI_WGRAD_WIN");
-    static const bool no_ww = ww_env && !strcmp(ww_env, "off");
-    if (!no_ww && stride == 2 && !flip && (atomic == 1 || atomic == 2) && ba_tile == 128 && (Bc & 31) == 0 && Yc * Xc > 1 &&
-        (int64_t)N * Hq * Wq * Bc < 0x7fffffffLL && M * A < 0x7fffffffLL) {
-        WgradWinArgs w;
-        w.gate = gate;
-        w.P = (const half_t*)P; w.Q = (const half_t*)Q; w.out = out; w.zero = (const half_t*)zero16;
-        w.N = N; w.Yc = Yc; w.Xc = Xc; w.A = A; w.Hq = Hq; w.Wq = Wq; w.Bc = Bc; w.pad = pad; w.TW = k; w.ldo = ldo;
-        w.slab_stride = atomic == 2 ? (int64_t)apad * ldo : 0;
-        w.a_tiles = apad / 128;
-        bool ok = true;
-        for (int par = 0; par < 2; ++par) {
-            int cnt = 0, emin = 0;
-            for (int t = 0; t < k; ++t)
-                if (((t - pad) & 1) == par) { if (!cnt) emin = t - pad; ++cnt; }
-            w.nsy[par] = w.nsx[par] = cnt;
-            w.tmin[par] = (emin - par) / 2;      // exact: emin and par have the same parity
-            if (cnt < 2 || cnt > 3) ok = false;
-        }
-        if (ok) {
-            w.tiles_y = (Yc + 7) / 8; w.tiles_x = (Xc + 7) / 8;
-            w.ntiles = N * w.tiles_y * w.tiles_x;
-            // `splits` = blocks per (row block, column block) over the 4 planes; K pieces per plane: wgrad_plane_pieces()
-            int tps4[4];
-            const int smax = wgrad_plane_pieces(N, Yc, Xc, k, pad, splits, tps4);      // = fmri_wgrad_slabs(): in slab mode the
-            for (int pl = 0; pl < 4; ++pl) {                                          // caller sized the output with it, and
-                w.plane_tps[pl] = tps4[pl];                                           // every allocated slab is written
-                w.plane_pieces[pl] = (w.ntiles + tps4[pl] - 1) / tps4[pl];
-            }
-            w.splits = smax;
-            w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
-            w.fdTX = make_fastdiv((uint32_t)w.tiles_x);
-            return wgrad_win_launch(w, apad, S(stream));
-        }
-    }
-    // 5x5 stride-1 layers between 32 and 3(8) channels, pre-zeroed output: wave-private window kernel
-    // (csrc/wgrad_narrow.hip).  FMRI_WGRAD_NARROW=off disables.
-    static const char* wn_env = getenv("FMRI_WGRAD_NARROW");
-    static const bool no_wn = wn_env && !strcmp(wn_env, "off");
-    if (atomic == 3 && (no_wn || !(stride == 1 && k == 5 && pad == 2 && A == 32 && Bc == 8 && apad == 32 && Yc == Hq &&
-                           Xc == Wq)))
-        return FMRI_E_UNSUPPORTED;
-    if (atomic == 3 && stride == 1 && k == 5 && pad == 2 && A == 32 && Bc == 8 && apad == 32 && Yc == Hq &&
-        Xc == Wq && (int64_t)N * Yc * Xc * 32 < 0x7fffffffLL) {
-        WgradNarrowArgs w;
-        w.gate = gate;
-        w.P = (const half_t*)P; w.Q = (const half_t*)Q; w.out = out; w.zero = (const half_t*)zero16;
-        w.N = N; w.H = Yc; w.W = Xc; w.ldo = ldo; w.flip = flip;
-        w.tiles_y = (Yc + 7) / 8; w.tiles_x = (Xc + 7) / 8;
-        w.ntiles = N * w.tiles_y * w.tiles_x;
-        const int nb = wgrad_narrow_blocks(N, Yc, Xc);
-        w.nslabs = splits < 1 ? 1 : splits;         // the caller allocated `splits` zeroed slabs of apad x ldo
-        w.pad0 = 0;
-        w.slab_stride = (int64_t)apad * ldo;
-        return wgrad_narrow_launch(w, nb, S(stream));
-    }
+    const WgradReq q = {gate, (const half_t*)P, (const half_t*)Q, (const half_t*)zero16, out, N, Yc, Xc, A, Hq, Wq, Bc, k,
+                        stride, pad, flip, apad, ba_tile, ldo, splits, atomic, S(stream)};
+    WgradWinArgs w;
+    if (wgrad_win_args(q, w)) return wgrad_win_launch(w, apad, q.st);      // its code is final, E_UNSUPPORTED too
+    if (atomic == 3) return wgrad_narrow(q);
     if (atomic == 2) return FMRI_E_UNSUPPORTED;      // plane-piece slabs exist only in the window-resident kernel
-    WgradArgs a;
-    a.gate = gate;
-    a.P = (const half_t*)P; a.Q = (const half_t*)Q; a.out = out; a.zero = (const half_t*)zero16;
-    a.N = N; a.Yc = Yc; a.Xc = Xc; a.A = A; a.Hq = Hq; a.Wq = Wq; a.Bc = Bc;
-    a.s = stride; a.T = T; a.TW = k;
-    a.dy0 = flip ? pad : -pad; a.dx0 = a.dy0; a.dstep = flip ? -1 : 1;
-    a.M = (int)M; a.ldo = ldo;
-    const int steps = (int)((M + 63) / 64);
-    if (splits > steps) splits = steps;
-    a.steps_per_split = (steps + splits - 1) / splits;
-    a.splits = (steps + a.steps_per_split - 1) / a.steps_per_split;
-    // atomic == 4: per-split slabs of the generic kernel -- the caller allocated `splits` (as passed in) slabs of
-    // apad x ldo; the kernel writes every element of the first a.splits (<= splits) of them with plain stores, the
-    // rest stay as the caller left them (zero-filled)
-    a.atomic = atomic == 4 ? 2 : atomic;
-    a.slab_stride = (int64_t)apad * ldo;
-    a.ncol_chunks = T * Bc / 8;
-    a.fdX = make_fastdiv((uint32_t)Xc);
-    a.fdYX = make_fastdiv((uint32_t)(Yc * Xc));
-    a.fdTW = make_fastdiv((uint32_t)k);
-    a.fdBc8 = make_fastdiv((uint32_t)(Bc / 8));
-    return wgrad_launch(a, apad, ba_tile, S(stream));
+    return wgrad_generic(q);
 }
 
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream) {
