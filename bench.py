@@ -11,6 +11,12 @@ forward (encoder, 2x decoder, fused REC+GAN discriminator), losses, two-stream b
 gradient sets, SUM all-reduce over RCCL (N > 1), gated RMSprop updates, fp16 weight re-pack.
 Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: set-up, warm-up, the launch-mode probe, the timed steps, --dump-outputs
+if given, the result line.  --full adds everything else the benchmark measures, each after the timed region: the
+gate-skip pass (`gate_skip`), the per-kernel family timing and roofline with its live rocprofv3 counter passes
+(`roofline`, `families`), the HBM-bound kernel rows (`hbm_bound_kernels`) and the CPU baseline (`cpu_baseline`); the
+--no-* options switch single legs of it off.
+
 --workload selects the other BASELINE configs (same contract, their own metric names):
     stage1        configs[1]  Stage-I VAE/GAN 64 px, B = 256 per GPU                       (default, the headline)
     stage2        configs[2]  Stage-II cognitive VAE/GAN, V = 4096, decoder frozen, B = 256 per GPU
@@ -127,7 +133,7 @@ def live_pmc_traffic(family, timeout_s=75):
             out = os.path.join(tmp, counter)
             cmd = [rocprof, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "x", "--",
                    sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "2", "--eager", "--serial",
-                   "--no-cpu-baseline", "--no-hbm-rows", "--no-pmc", "--no-gate-pass"]
+                   "--full", "--no-cpu-baseline", "--no-hbm-rows", "--no-pmc", "--no-gate-pass"]
             # a process group of its own: on a timeout the profiler AND the python it started are killed together
             proc = subprocess.Popen(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL,
                                     stderr=subprocess.DEVNULL, start_new_session=True)
@@ -242,6 +248,62 @@ def family_table(prof, steps, key=_family_of):
             row["frac_of_hbm_peak"] = round(row["gb_s"] / HBM_PEAK_GBS, 4)
         rows.append((row, f))
     return rows
+
+
+def kernel_report(prof, prof_steps, prof_ms_per_step, workload, live_pmc):
+    """``roofline`` and ``families`` of the result line (--full) from the per-launch HIP events of ``prof_steps``
+    one-stream steps; ``live_pmc``: measure the dominant family's traffic by rocprofv3 child passes of this script."""
+    # dominant kernel FAMILY = the group of library launches with the largest total HIP-event time in the profiled
+    # steps: GEMM forward / data-gradient kernels, the weight-gradient kernels, BatchNorm and the rest all compete
+    fams = family_table(prof, max(prof_steps, 1))
+    ps = max(prof_steps, 1)
+    if fams:
+        top, tf = fams[0]
+    else:
+        top, tf = {"family": "none", "ms_per_step": 0.0}, dict(ms=0.0, n=1, flops=0.0, bytes=0.0, ms_b=0.0)
+    label = top["family"]
+    nl = max(tf["n"], 1)
+    ms = tf["ms"]
+    mfma_bound = tf["flops"] > 0
+    if mfma_bound:
+        achieved, peak, runit = tf["flops"] / (ms * 1e-3) / 1e12 if ms > 0 else 0.0, MFMA_PEAK_TFLOPS, "TFLOP/s"
+    else:
+        achieved = tf["bytes"] / (tf["ms_b"] * 1e-3) / 1e9 if tf["ms_b"] > 0 else 0.0
+        peak, runit = HBM_PEAK_GBS, "GB/s"
+    # the committed PMC passes are of the Stage-I workload: no traffic figure for the other workloads
+    traffic, traffic_src = None, None
+    if live_pmc:
+        traffic = live_pmc_traffic(label)
+        traffic_src = "live" if traffic else None
+    if traffic is None and workload == "stage1":
+        traffic, traffic_src = pmc_traffic(label)
+    alg_bytes = int(tf["bytes"] / nl) if tf["bytes"] > 0 else None
+    lib_ms = sum(f["ms"] for _, f in fams) / ps
+    return {
+        "roofline": {"bound": "mfma" if mfma_bound else "hbm", "achieved": round(achieved, 1), "peak": peak,
+                     "unit": runit, "frac": round(achieved / peak, 4), "traffic": traffic,
+                     "algorithmic_bytes": alg_bytes,
+                     "traffic_over_algorithmic": round(traffic / alg_bytes, 2) if traffic and alg_bytes else None,
+                     "traffic_source": ("live" if traffic_src == "live" else f"committed:{traffic_src}") if traffic else None,
+                     "traffic_unit": ("bytes per launch leaving L2, (2*FETCH_SIZE + WRITE_SIZE)*1024, "
+                                      + ("measured on THIS box by two rocprofv3 --pmc child passes of this script "
+                                         "(FETCH_SIZE, WRITE_SIZE: separate runs, --kernel-trace only, 5 one-stream steps)"
+                                         if traffic_src == "live" else
+                                         f"of the rocprofv3 PMC passes of this workload committed as profiles/{traffic_src}")
+                                      + "; algorithmic_bytes = input + output + weights once, per launch") if traffic else None,
+                     "kernel": label,
+                     "measured": "HIP events around each library launch, 5 steps issued on ONE stream (the timed "
+                                 "region overlaps weight gradients on a second stream when launched eagerly); the "
+                                 "family with the largest total time is reported",
+                     "launches_per_step": nl // ps,
+                     "avg_launch_ms": round(ms / nl, 4),
+                     "avg_launch_gflop": round(tf["flops"] / nl / 1e9, 2) if mfma_bound else None},
+        "families": {"ms_per_step_one_stream": round(prof_ms_per_step, 3),
+                     "ms_per_step_library_launches": round(lib_ms, 3),
+                     "ms_per_step_torch_ops_and_gaps": round(prof_ms_per_step - lib_ms, 3),
+                     "groups": [row for row, _ in family_table(prof, ps, _group_of)],
+                     "rows": [row for row, _ in fams if row["ms_per_step"] >= 0.02]},
+    }
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -498,13 +560,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="stage1")
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU (weak scaling); 0 = the workload's own")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-rows", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the gate-skip pass, the per-kernel family / roofline pass with "
+                         "its rocprofv3 counter passes, the HBM-bound kernel rows and the CPU baseline (off by default: "
+                         "a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-hbm-rows", action="store_true", help="--full without the HBM-bound kernel rows")
     ap.add_argument("--no-gate-pass", dest="gate_pass", action="store_false",
-                    help="skip the extra timed pass with the engine's default gate_skip=True")
+                    help="--full without the extra timed pass with the engine's default gate_skip=True")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not run the two rocprofv3 counter passes for roofline.traffic (then the committed passes of "
-                         "the same command under profiles/ are quoted)")
+                    help="--full without the two rocprofv3 counter passes for roofline.traffic (then the committed "
+                         "passes of the same command under profiles/ are quoted)")
     ap.add_argument("--sync-bn", action="store_true",
                     help="data-parallel runs: all-reduce the BatchNorm partial sums (statistics of the GLOBAL batch, one "
                          "small collective per BatchNorm call).  Default: per-rank statistics over the rank's own batch, "
@@ -699,7 +765,7 @@ def main():
     # the same steps with the engine's default gate_skip=True (launches that are recorded into a full-step graph keep the
     # setting they were recorded with, so this pass uses the hybrid / eager launches), and how often the gate trained what
     gate_out = None
-    if has_gate and a.gate_pass and a.workload in ("stage1", "stage2"):
+    if a.full and has_gate and a.gate_pass and a.workload in ("stage1", "stage2"):
         grun = modes.get("hybrid", run_i)
         st.gate_skip = True
         for i in range(10):
@@ -730,20 +796,21 @@ def main():
     # dominant-kernel timing: HIP events around every fmri_igemm launch over a few eagerly issued steps (events cannot be
     # placed inside a replayed graph).  The side stream is switched off for this pass: next to concurrently running
     # weight-gradient kernels a launch's duration says nothing about the kernel.
-    ops.join_side()
-    side_was, ops._SIDE["on"] = ops._SIDE["on"], False
-    lib.PROFILE = [] if rank == 0 else None
-    prof_steps = min(a.steps, 5)
-    e_first, e_last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e_first.record()
-    for i in range(prof_steps):
-        run_i(i)
-    e_last.record()
-    barrier()
-    prof, lib.PROFILE = lib.PROFILE, None
-    require_finite("the per-kernel profiling pass", st.logs())
-    prof_ms_per_step = e_first.elapsed_time(e_last) / max(prof_steps, 1)
-    ops._SIDE["on"] = side_was
+    if a.full:
+        ops.join_side()
+        side_was, ops._SIDE["on"] = ops._SIDE["on"], False
+        lib.PROFILE = [] if rank == 0 else None
+        prof_steps = min(a.steps, 5)
+        e_first, e_last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_first.record()
+        for i in range(prof_steps):
+            run_i(i)
+        e_last.record()
+        barrier()
+        prof, lib.PROFILE = lib.PROFILE, None
+        require_finite("the per-kernel profiling pass", st.logs())
+        prof_ms_per_step = e_first.elapsed_time(e_last) / max(prof_steps, 1)
+        ops._SIDE["on"] = side_was
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -751,33 +818,6 @@ def main():
 
     if rank == 0:
         value = world * B * a.steps / dt
-        # dominant kernel FAMILY = the group of library launches with the largest total HIP-event time in the profiled
-        # steps: GEMM forward / data-gradient kernels, the weight-gradient kernels, BatchNorm and the rest all compete
-        fams = family_table(prof, max(prof_steps, 1))
-        ps = max(prof_steps, 1)
-        if fams:
-            top, tf = fams[0]
-        else:
-            top, tf = {"family": "none", "ms_per_step": 0.0}, dict(ms=0.0, n=1, flops=0.0, bytes=0.0, ms_b=0.0)
-        label = top["family"]
-        nl = max(tf["n"], 1)
-        ms = tf["ms"]
-        mfma_bound = tf["flops"] > 0
-        if mfma_bound:
-            achieved, peak, runit = tf["flops"] / (ms * 1e-3) / 1e12 if ms > 0 else 0.0, MFMA_PEAK_TFLOPS, "TFLOP/s"
-        else:
-            achieved = tf["bytes"] / (tf["ms_b"] * 1e-3) / 1e9 if tf["ms_b"] > 0 else 0.0
-            peak, runit = HBM_PEAK_GBS, "GB/s"
-        # the committed PMC passes are of the Stage-I workload: no traffic figure for the other workloads
-        traffic, traffic_src = None, None
-        # live counter passes only for the default configuration (the child runs profile THAT workload)
-        if a.workload == "stage1" and world == 1 and not a.no_pmc and not a.batch:
-            traffic = live_pmc_traffic(label)
-            traffic_src = "live" if traffic else None
-        if traffic is None and a.workload == "stage1":
-            traffic, traffic_src = pmc_traffic(label)
-        alg_bytes = int(tf["bytes"] / nl) if tf["bytes"] > 0 else None
-        lib_ms = sum(f["ms"] for _, f in fams) / ps
         finite = all(np.isfinite(v) for v in logs.values() if isinstance(v, float))
         out = {
             "metric": metric, "value": round(value, 1), "unit": unit,
@@ -786,29 +826,12 @@ def main():
             "config": {"workload": desc, "name": a.workload, "batch_per_gpu": B, "global_batch": B * world,
                        "synthetic_batches": NBATCH, "gate_skip": False if has_gate else None,
                        "parallelism": f"dp{world}" + ("" if world == 1 else ("-syncbn" if a.sync_bn else "-localbn"))},
-            "roofline": {"bound": "mfma" if mfma_bound else "hbm", "achieved": round(achieved, 1), "peak": peak,
-                         "unit": runit, "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "algorithmic_bytes": alg_bytes,
-                         "traffic_over_algorithmic": round(traffic / alg_bytes, 2) if traffic and alg_bytes else None,
-                         "traffic_source": ("live" if traffic_src == "live" else f"committed:{traffic_src}") if traffic else None,
-                         "traffic_unit": ("bytes per launch leaving L2, (2*FETCH_SIZE + WRITE_SIZE)*1024, "
-                                          + ("measured on THIS box by two rocprofv3 --pmc child passes of this script "
-                                             "(FETCH_SIZE, WRITE_SIZE: separate runs, --kernel-trace only, 5 one-stream steps)"
-                                             if traffic_src == "live" else
-                                             f"of the rocprofv3 PMC passes of this workload committed as profiles/{traffic_src}")
-                                          + "; algorithmic_bytes = input + output + weights once, per launch") if traffic else None,
-                         "kernel": label,
-                         "measured": "HIP events around each library launch, 5 steps issued on ONE stream (the timed "
-                                     "region overlaps weight gradients on a second stream when launched eagerly); the "
-                                     "family with the largest total time is reported",
-                         "launches_per_step": nl // ps,
-                         "avg_launch_ms": round(ms / nl, 4),
-                         "avg_launch_gflop": round(tf["flops"] / nl / 1e9, 2) if mfma_bound else None},
-            "families": {"ms_per_step_one_stream": round(prof_ms_per_step, 3),
-                         "ms_per_step_library_launches": round(lib_ms, 3),
-                         "ms_per_step_torch_ops_and_gaps": round(prof_ms_per_step - lib_ms, 3),
-                         "groups": [row for row, _ in family_table(prof, ps, _group_of)],
-                         "rows": [row for row, _ in fams if row["ms_per_step"] >= 0.02]},
+        }
+        if a.full:
+            # live counter passes only for the default configuration (the child runs profile THAT workload)
+            out.update(kernel_report(prof, prof_steps, prof_ms_per_step, a.workload,
+                                     a.workload == "stage1" and world == 1 and not a.no_pmc and not a.batch))
+        out.update({
             "launch": {"graph": "hip-graph replay" if single else "hip-graph segments + eager collectives",
                        "hybrid": "forward replayed from a HIP graph, backward eager with weight gradients on a side "
                                  "stream" + ("" if single else " and eager collectives"),
@@ -818,14 +841,14 @@ def main():
             "gflop_per_sample": round(flop_per_sample / 1e9, 2),
             "losses_last_step": {k: v for k, v in logs.items() if isinstance(v, float)},
             "losses_finite": bool(finite),
-        }
+        })
         if gate_out is not None:
             out["gate_skip"] = gate_out
         if dump is not None:
             out["dump_outputs"] = dump
-        if world == 1 and not a.no_hbm_rows:
+        if a.full and world == 1 and not a.no_hbm_rows:
             out["hbm_bound_kernels"] = dict(peak_gb_s=HBM_PEAK_GBS, rows=hbm_rows(dev, 256))
-        if world == 1 and not a.no_cpu_baseline and a.workload == "stage1":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "stage1":
             out["cpu_baseline"] = cpu_baseline(32, 10)        # ~10-15 s of CPU work (bounded to 25 s inside)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1 or force_dist:

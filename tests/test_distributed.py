@@ -448,12 +448,13 @@ def test_two_rank_other_steps_equal_single_process_global_batch(kind):
 
 @pytest.mark.gpu
 @pytest.mark.selfcheck
-@pytest.mark.parametrize("extra", [[], ["--sync-bn"]])
+@pytest.mark.parametrize("extra", [[], ["--sync-bn"], ["--full"]])
 def test_bench_two_rank_control_flow_rehearsal(extra, tmp_path):
     """bench.py's multi-process control flow (what the driver launches for N > 1) with two ranks sharing this one GPU,
     gloo as the collective backend: launch-mode probe decided collectively, barrier + max-over-ranks timing, one JSON
-    line from rank 0 with the whole-job aggregate, finite losses, exit code 0.  (Two GPUs over RCCL are not available
-    to the tests; the data path of the ranks is covered by the 2-rank step tests above.)"""
+    line from rank 0 with the whole-job aggregate, finite losses, exit code 0; with --full also the collective gate-skip
+    pass and the one-stream profiling pass.  (Two GPUs over RCCL are not available to the tests; the data path of the
+    ranks is covered by the 2-rank step tests above.)"""
     import json
     import socket
     import subprocess
@@ -473,7 +474,8 @@ def test_bench_two_rank_control_flow_rehearsal(extra, tmp_path):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 8 and out["warmup"] == 3 and out["scaling"] == "weak"
     assert out["config"]["global_batch"] == 128 and out["config"]["batch_per_gpu"] == 64
-    assert out["config"]["parallelism"] == ("dp2-syncbn" if extra else "dp2-localbn")
+    assert out["config"]["parallelism"] == ("dp2-syncbn" if "--sync-bn" in extra else "dp2-localbn")
+    assert ("gate_skip" in out and "roofline" in out) == ("--full" in extra)
     assert out["losses_finite"] is True and out["value"] > 0
     assert abs(out["value"] - 128 * 8 / (out["ms_per_step"] * 8e-3)) < 0.01 * out["value"]      # whole-job aggregate
 

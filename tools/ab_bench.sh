@@ -4,7 +4,7 @@ P=thesis-fmri-reconstruction_amd/fmri_hip
 for r in 1 2; do
 for v in old new; do
   cp ab/$v.so $P/libfmri_hip.so
-  python bench.py --steps 40 --warmup 5 2>/dev/null | python -c "
+  python bench.py --steps 40 --warmup 5 --full 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['roofline']['kernel'], d['roofline']['avg_launch_ms'])"
 done; done
 for v in old new; do

@@ -7,9 +7,9 @@ OUT=$R/gpurun_out/final
 mkdir -p $OUT
 cd $R
 timeout -k 10 700 python -m pytest tests -q -m gpu > $OUT/gpu_tests.log 2>&1; tail -3 $OUT/gpu_tests.log
-timeout -k 10 400 python bench.py > $OUT/bench_stage1.json 2> $OUT/bench_stage1.err; cut -c1-200 $OUT/bench_stage1.json
+timeout -k 10 400 python bench.py --full > $OUT/bench_stage1.json 2> $OUT/bench_stage1.err; cut -c1-200 $OUT/bench_stage1.json
 for w in stage2 dual1 stage3_px128; do
-  timeout -k 10 300 python bench.py --workload $w --steps 100 --warmup 20 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout -k 10 300 python bench.py --workload $w --steps 100 --warmup 20 --full > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
 timeout -k 10 200 python tools/microbench_igemm.py > $OUT/microbench_igemm.log 2>&1
 timeout -k 10 300 python tools/time_other_steps.py > $OUT/other_steps.log 2>&1

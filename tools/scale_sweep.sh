@@ -7,9 +7,9 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 cd "$(dirname "$0")/.."
 for n in 1 2 4 8; do
   if [ "$n" = 1 ]; then
-    python bench.py --gpus 1 --no-cpu-baseline --no-hbm-rows "$@"
+    python bench.py --gpus 1 --full --no-cpu-baseline --no-hbm-rows "$@"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --no-cpu-baseline "$@"
+      bench.py --gpus $n --full --no-cpu-baseline "$@"
   fi
 done
