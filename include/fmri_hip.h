@@ -492,6 +492,56 @@ int fmri_apply_entry_fill(void* host_entry, const float* gsrc, float* w, float* 
 int fmri_apply_batch(const void* table_dev, int n, int total_tiles, int mode, const float* lr_dev, float alpha, float eps,
                      float gscale, const float* gdev, float clamp, const int* flag, int gated, void* stream);
 
+/* ---- numerics monitor (opt-in; fmri_hip/monitor.py) ------------------------------------------------------------------
+ * Statistics of one tensor segment.  Every field is order-independent or folded in a fixed order: two runs give the same
+ * bits.  `sumsq` (double), `max`, `min` and `max_abs` cover the FINITE elements only (max = -inf, min = +inf, max_abs = 0
+ * when there is none), `nonfinite` counts NaN / +-inf, `clamped` counts the elements that fminf(fmaxf(v, -clamp), clamp)
+ * changes (0 when clamp <= 0), `written` is 1 once a statistics launch has filled the record (0: gated off / not run). */
+typedef struct fmri_stat {
+    double sumsq;
+    float max, min, max_abs;
+    int32_t nonfinite, clamped, written;
+} fmri_stat;                                     /* 32 bytes */
+/* One segment of fmri_tensor_stats: rows x cols fp32 values at x[r * ld + c], each taken as v = x * (scale / *div)
+ * (div may be NULL: 1) -- the true-scale gradient of fmri_rmsprop_dev / fmri_adam_dev with scale = gscale, div = gdev.
+ * `gate` (may be NULL): when *gate == 0 the segment is skipped and `out` is left as it is. */
+typedef struct fmri_stat_seg {
+    const float* x;
+    int64_t rows, cols, ld;
+    const float* div;
+    const int* gate;
+    fmri_stat* out;
+    float scale, clamp;
+} fmri_stat_seg;                                 /* 64 bytes */
+#define FMRI_STAT_MAX_SEGS 8
+#define FMRI_STAT_BLOCKS 256                     /* partial records per segment at most */
+/* Up to FMRI_STAT_MAX_SEGS segments (host array, read before the call returns) in two launches: per-block partial records
+ * into `ws` (fmri_tensor_stats_ws_bytes(nseg) bytes, 8-byte aligned), then a fixed-order fold into each segment's `out`. */
+int fmri_tensor_stats_ws_bytes(int nseg);
+int fmri_tensor_stats(const fmri_stat_seg* segs, int nseg, void* ws, void* stream);
+/* fmri_apply_batch (modes 1 / 3) that also writes, per block, the statistics of the true-scale gradients it consumed
+ * (before the clamp) and of the new weights: part[2 * b] = gradient, part[2 * b + 1] = weights, zero for a block that
+ * updates nothing; `part` holds 2 * total_tiles records.  Same update, bit for bit.  fmri_stat_fold then folds the
+ * records in a fixed order: out[0] <- the gradient records, out[1] <- the weight records, both only when `flag` is NULL
+ * or *flag != 0. */
+int fmri_apply_batch_stats(const void* table_dev, int n, int total_tiles, int mode, const float* lr_dev, float alpha,
+                           float eps, float gscale, const float* gdev, float clamp, const int* flag, int gated,
+                           fmri_stat* part, void* stream);
+int fmri_stat_fold(const fmri_stat* part, int nrec, const int* flag, fmri_stat* out, void* stream);
+/* fmri_bn_bwd_apply / fmri_bn_bwd_apply2 / fmri_bn_cols_bwd that also count, into cnt[0] and cnt[1] (caller-zeroed ints,
+ * added to), the dx values the saturating fp16 store clipped to +-65504 and the NaN values it stored.  Same dx, bit for
+ * bit; integer adds: deterministic. */
+int fmri_bn_bwd_apply_cnt(const void* x, const void* dy, void* dx, int M, int C, float count, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, int relu, const float* sums2C,
+                          int* cnt, void* stream);
+int fmri_bn_bwd_apply2_cnt(const void* x, const void* dy2, void* dx2, int M, int C, float count, const float* mean,
+                           const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
+                           int* cnt, void* stream);
+int fmri_bn_cols_bwd_cnt(const void* x, const void* dy, void* dx, int M, int C, int nstreams, float count,
+                         const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
+                         float* sums, float* dbeta, float* dgamma, float gscale, int param_stream, int* cnt,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

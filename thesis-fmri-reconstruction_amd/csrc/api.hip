@@ -9,6 +9,10 @@
 
 using namespace fmri;
 
+static_assert(sizeof(fmri_stat) == sizeof(StatRec) && sizeof(fmri_stat) == 32, "fmri_stat layout");
+static_assert(sizeof(fmri_stat_seg) == sizeof(StatSeg) && sizeof(fmri_stat_seg) == 64, "fmri_stat_seg layout");
+static_assert(FMRI_STAT_MAX_SEGS == STAT_MAX_SEGS && FMRI_STAT_BLOCKS == STAT_BLOCKS, "monitor limits");
+
 namespace {
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
@@ -235,6 +239,39 @@ int fmri_apply_batch(const void* table_dev, int n, int total_tiles, int mode, co
     o.lr_dev = lr_dev; o.gdev = gdev; o.flag = flag; o.alpha = alpha; o.eps = eps; o.gscale = gscale; o.clamp = clamp;
     o.mode = mode; o.gated = gated ? 1 : 0;
     return apply_batch_launch((const ApplyEntry*)table_dev, n, total_tiles, o, S(stream));
+}
+
+int fmri_apply_batch_stats(const void* table_dev, int n, int total_tiles, int mode, const float* lr_dev, float alpha,
+                           float eps, float gscale, const float* gdev, float clamp, const int* flag, int gated,
+                           fmri_stat* part, void* stream) {
+    if (!table_dev || !part || ((uintptr_t)part & 7) || n < 0 || total_tiles < 0 || (mode != 1 && mode != 3) || !lr_dev)
+        return FMRI_E_BADARG;
+    ApplyOpt o;
+    o.lr_dev = lr_dev; o.gdev = gdev; o.flag = flag; o.alpha = alpha; o.eps = eps; o.gscale = gscale; o.clamp = clamp;
+    o.mode = mode; o.gated = gated ? 1 : 0;
+    return apply_batch_stats_launch((const ApplyEntry*)table_dev, n, total_tiles, o, (StatRec*)part, S(stream));
+}
+int fmri_stat_fold(const fmri_stat* part, int nrec, const int* flag, fmri_stat* out, void* stream) {
+    if (!part || !out || nrec < 0 || ((uintptr_t)part & 7) || ((uintptr_t)out & 7)) return FMRI_E_BADARG;
+    return stat_fold_launch((const StatRec*)part, nrec, flag, (StatRec*)out, S(stream));
+}
+int fmri_tensor_stats_ws_bytes(int nseg) {
+    return nseg < 1 || nseg > FMRI_STAT_MAX_SEGS ? 0 : nseg * STAT_BLOCKS * (int)sizeof(StatRec);
+}
+int fmri_tensor_stats(const fmri_stat_seg* segs, int nseg, void* ws, void* stream) {
+    if (!segs || nseg < 1 || nseg > FMRI_STAT_MAX_SEGS || !ws || ((uintptr_t)ws & 7)) return FMRI_E_BADARG;
+    StatSegs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nseg; ++i) {
+        const fmri_stat_seg& g = segs[i];
+        if (!g.x || !g.out || ((uintptr_t)g.out & 7) || g.rows < 0 || g.cols < 1 || g.ld < g.cols) return FMRI_E_BADARG;
+        StatSeg& d = a.s[i];
+        d.x = g.x; d.rows = g.rows; d.cols = g.cols; d.ld = g.ld; d.div = g.div; d.gate = g.gate;
+        d.out = (StatRec*)g.out; d.scale = g.scale; d.clamp = g.clamp;
+        const int64_t n = g.rows * g.cols, want = (n + 2047) / 2048;
+        a.nblk[i] = (int)(want < 1 ? 1 : (want > STAT_BLOCKS ? STAT_BLOCKS : want));
+    }
+    return tensor_stats_launch(a, nseg, (StatRec*)ws, S(stream));
 }
 
 int fmri_unpack_grad(const float* src, float* dst, int64_t sa, int64_t sta, int64_t sb, int64_t stb, int A, int TA,
@@ -861,7 +898,17 @@ int fmri_bn_cols_bwd(const void* x, const void* dy, void* dx, int M, int C, int 
         param_stream < 0 || param_stream >= nstreams)
         return FMRI_E_BADARG;
     return bn_cols_bwd_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, nstreams, count, mean, rstd, gamma,
-                              beta, relu, sums, dbeta, dgamma, gscale, param_stream, S(stream));
+                              beta, relu, sums, dbeta, dgamma, gscale, param_stream, nullptr, S(stream));
+}
+int fmri_bn_cols_bwd_cnt(const void* x, const void* dy, void* dx, int M, int C, int nstreams, float count,
+                         const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
+                         float* sums, float* dbeta, float* dgamma, float gscale, int param_stream, int* cnt,
+                         void* stream) {
+    if (!cnt || !x || !dy || !dx || !sums || (C & 7) || C < 8 || M < 1 || !mean || !rstd || !gamma || !beta ||
+        count <= 0.f || param_stream < 0 || param_stream >= nstreams)
+        return FMRI_E_BADARG;
+    return bn_cols_bwd_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, nstreams, count, mean, rstd, gamma,
+                              beta, relu, sums, dbeta, dgamma, gscale, param_stream, cnt, S(stream));
 }
 int fmri_bn_fold_finalize(const float* stat_part, int rows, int C, float* scratch, float* sums2C, float count,
                           const float* gamma, const float* beta, float eps, float momentum, int updates,
@@ -909,14 +956,28 @@ int fmri_bn_bwd_apply2(const void* x, const void* dy2, void* dx2, int M, int C, 
                        void* stream) {
     if (!x || !dy2 || !dx2 || !sums4C || (C & 7) || M < 1) return FMRI_E_BADARG;
     return bn_bwd_apply2_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, count, mean, rstd, gamma, beta,
-                                relu, sums4C, S(stream));
+                                relu, sums4C, nullptr, S(stream));
 }
 int fmri_bn_bwd_apply(const void* x, const void* dy, void* dx, int M, int C, float count, const float* mean,
                       const float* rstd, const float* gamma, const float* beta, int relu, const float* sums2C,
                       void* stream) {
     if (!x || !dy || !dx || (C & 7)) return FMRI_E_BADARG;
     return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, count, mean, rstd, gamma, beta,
-                               relu, sums2C, S(stream));
+                               relu, sums2C, nullptr, S(stream));
+}
+int fmri_bn_bwd_apply2_cnt(const void* x, const void* dy2, void* dx2, int M, int C, float count, const float* mean,
+                           const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
+                           int* cnt, void* stream) {
+    if (!cnt || !x || !dy2 || !dx2 || !sums4C || (C & 7) || M < 1) return FMRI_E_BADARG;
+    return bn_bwd_apply2_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, count, mean, rstd, gamma, beta,
+                                relu, sums4C, cnt, S(stream));
+}
+int fmri_bn_bwd_apply_cnt(const void* x, const void* dy, void* dx, int M, int C, float count, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, int relu, const float* sums2C,
+                          int* cnt, void* stream) {
+    if (!cnt || !x || !dy || !dx || (C & 7)) return FMRI_E_BADARG;
+    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, count, mean, rstd, gamma, beta,
+                               relu, sums2C, cnt, S(stream));
 }
 int fmri_act_bwd(const void* y, const void* dy, void* dpre, int M, int C, int act, float* colsum2C, float* ws,
                  int64_t ws_floats, float* dbias, int dbias_n, float gscale, void* stream) {

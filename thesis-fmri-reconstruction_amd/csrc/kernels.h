@@ -67,6 +67,87 @@ constexpr int APPLY_CHUNK = 1024;       // elements per block of kinds 1 / 2
 int apply_entry_tiles(ApplyEntry& e, int TH, int TW, int KW, int py, int px, int step, int64_t stb);
 int apply_batch_launch(const ApplyEntry* tab, int n, int total_tiles, const ApplyOpt& o, hipStream_t st);
 
+// Numerics monitor (fmri_stat / fmri_stat_seg of include/fmri_hip.h, same layout)
+struct StatRec {
+    double sumsq;
+    float max, min, max_abs;
+    int32_t nonfinite, clamped, written;
+};
+struct StatSeg {
+    const float* x;
+    int64_t rows, cols, ld;
+    const float* div;
+    const int* gate;
+    StatRec* out;
+    float scale, clamp;
+};
+constexpr int STAT_MAX_SEGS = 8, STAT_BLOCKS = 256;
+struct StatSegs {
+    StatSeg s[STAT_MAX_SEGS];
+    int32_t nblk[STAT_MAX_SEGS];   // partial records (blocks) of each segment
+};
+// `part` gets 2 * total_tiles records (gradient, weights) per block
+int apply_batch_stats_launch(const ApplyEntry* tab, int n, int total_tiles, const ApplyOpt& o, StatRec* part,
+                             hipStream_t st);
+int stat_fold_launch(const StatRec* part, int nrec, const int* flag, StatRec* out, hipStream_t st);
+int tensor_stats_launch(const StatSegs& segs, int nseg, StatRec* ws, hipStream_t st);
+
+// per-thread accumulator of a StatRec (finite elements: double sum of squares, max, min, max |v|; the rest counted)
+struct StatAcc {
+    double ss;
+    float mx, mn, amax;
+    int nf, cl;
+};
+__device__ __forceinline__ void stat_init(StatAcc& a) {
+    a.ss = 0.0; a.mx = -__builtin_inff(); a.mn = __builtin_inff(); a.amax = 0.f; a.nf = 0; a.cl = 0;
+}
+__device__ __forceinline__ void stat_add(StatAcc& a, float v) {
+    if (__builtin_isfinite(v)) {
+        a.ss += (double)v * (double)v;
+        a.mx = fmaxf(a.mx, v); a.mn = fminf(a.mn, v); a.amax = fmaxf(a.amax, fabsf(v));
+    } else {
+        a.nf += 1;
+    }
+}
+// (what the optimizers' clamp does to v: fminf(fmaxf(v, -c), c) -- a NaN becomes -c and is counted as changed)
+__device__ __forceinline__ void stat_add_clamped(StatAcc& a, float v, float clamp) {
+    stat_add(a, v);
+    if (clamp > 0.f) a.cl += fminf(fmaxf(v, -clamp), clamp) != v ? 1 : 0;
+}
+__device__ __forceinline__ void stat_merge(StatAcc& a, const StatAcc& b) {
+    a.ss += b.ss; a.mx = fmaxf(a.mx, b.mx); a.mn = fminf(a.mn, b.mn); a.amax = fmaxf(a.amax, b.amax);
+    a.nf += b.nf; a.cl += b.cl;
+}
+__device__ __forceinline__ void stat_merge_rec(StatAcc& a, const StatRec& r) {
+    a.ss += r.sumsq; a.mx = fmaxf(a.mx, r.max); a.mn = fminf(a.mn, r.min); a.amax = fmaxf(a.amax, r.max_abs);
+    a.nf += r.nonfinite; a.cl += r.clamped;
+}
+__device__ __forceinline__ StatRec stat_rec(const StatAcc& a, int written) {
+    StatRec r;
+    r.sumsq = a.ss; r.max = a.mx; r.min = a.mn; r.max_abs = a.amax; r.nonfinite = a.nf; r.clamped = a.cl;
+    r.written = written;
+    return r;
+}
+// the block's total (fixed order: an xor-shuffle tree per wave, then the waves in index order); valid in thread 0.
+// `red` = __shared__ StatAcc[blockDim.x / 64]; starts and ends with a barrier (callable twice in a row)
+__device__ __forceinline__ StatAcc stat_block(StatAcc a, StatAcc* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.ss += __shfl_xor(a.ss, o, 64);
+        a.mx = fmaxf(a.mx, __shfl_xor(a.mx, o, 64));
+        a.mn = fminf(a.mn, __shfl_xor(a.mn, o, 64));
+        a.amax = fmaxf(a.amax, __shfl_xor(a.amax, o, 64));
+        a.nf += __shfl_xor(a.nf, o, 64);
+        a.cl += __shfl_xor(a.cl, o, 64);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    StatAcc r = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) stat_merge(r, red[w]);
+    return r;
+}
+
 int igemm_launch(const IgemmArgs& a, int maxM, int bn_tile, int copad, bool out_f32, hipStream_t st);
 int igemm_bm(const IgemmArgs& a, int maxM, int bn_tile, int copad, bool out_f32);   // row tile igemm_launch will use
 int igemm_tc32_launch(const Tc32Args& a, int nblocks, hipStream_t st);
@@ -111,7 +192,7 @@ int bn_bwd_reduce2_launch(const half_t* x, const half_t* dy, int M, int C, const
                           float* dbeta, float* dgamma, float gscale, int param_stream, hipStream_t st);
 int bn_bwd_apply2_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
                          const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
-                         hipStream_t st);
+                         int* cnt, hipStream_t st);
 int bn_stats_finalize_launch(const half_t* x, int M, int C, float* sums, float* ws, int64_t ws_floats, float count,
                              const float* gamma, const float* beta, float eps, float momentum, int updates, float* rm,
                              float* rv, float* mean, float* rstd, float* scale, float* shift, long long* nbt,
@@ -136,12 +217,12 @@ int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, co
                        hipStream_t st);
 int bn_cols_bwd_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, float* sums,
-                       float* dbeta, float* dgamma, float gscale, int pstream, hipStream_t st);
+                       float* dbeta, float* dgamma, float gscale, int pstream, int* cnt, hipStream_t st);
 int bn_apply_launch(const half_t* x, half_t* y, int M, int C, const float* scale, const float* shift, int relu,
                     hipStream_t st);
 int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
                         const float* rstd, const float* gamma, const float* beta, int relu, const float* sums,
-                        hipStream_t st);
+                        int* cnt, hipStream_t st);
 int act_bwd_launch(const half_t* y, const half_t* dy, half_t* dpre, int M, int C, int act, float* colsum, float* ws,
                    int64_t ws_floats, float* dbias, int dbias_n, float gscale, hipStream_t st);
 int colsum_rows_launch(const half_t* x, int M, int C, float* sums2C, float* ws, int64_t ws_floats, float* dbias,

@@ -566,7 +566,11 @@ __device__ __forceinline__ float rms_update(float g, float* w, float* sq, float 
     return nw;
 }
 
-__global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __restrict__ tab, int n, const ApplyOpt o) {
+// STATS (fmri_apply_batch_stats): the true-scale gradient (before the clamp) and the new weight of every element this
+// thread updates go into `ga` / `pa` -- from the registers the update already holds, no extra loads
+template <bool STATS>
+__device__ __forceinline__ void apply_batch_body(const ApplyEntry* __restrict__ tab, int n, const ApplyOpt o,
+                                                 StatAcc& ga, StatAcc& pa) {
     __shared__ float t[64 * 65];
     __shared__ int sel;
     if (threadIdx.x < 64) {
@@ -592,8 +596,13 @@ __global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __re
         for (int k = 0; k < APPLY_CHUNK / 256; ++k) {
             const int64_t j = i + k * 256;
             if (j < en.n) {
-                if (o.mode == 2) en.grad[j] = 0.f;
-                else rms_update(en.grad[j], en.w + j, en.sq + j, gs, lr, o);
+                if (o.mode == 2) {
+                    en.grad[j] = 0.f;
+                } else {
+                    const float g = en.grad[j];
+                    const float nw = rms_update(g, en.w + j, en.sq + j, gs, lr, o);
+                    if (STATS) { stat_add_clamped(ga, g * gs, o.clamp); stat_add(pa, nw); }
+                }
             }
         }
         return;
@@ -621,6 +630,7 @@ __global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __re
             if (!live) continue;
             if (!update) { en.grad[off] = v; continue; }
             const float nw = rms_update(v, en.w + off, en.sq + off, gs, lr, o);
+            if (STATS) { stat_add_clamped(ga, v * gs, o.clamp); stat_add(pa, nw); }
             if (en.pk) en.pk[(int64_t)row * en.kpad + b] = (half_t)nw;
         }
         return;
@@ -656,7 +666,11 @@ __global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __re
             const int64_t off = base + (b0 + bl) * en.sb + j;
             const float v = from_grad ? en.grad[off] : t[bl * stride + j] * en.scale;
             if (!update) en.grad[off] = v;
-            else t[bl * stride + j] = rms_update(v, en.w + off, en.sq + off, gs, lr, o);
+            else {
+                const float nw = rms_update(v, en.w + off, en.sq + off, gs, lr, o);
+                t[bl * stride + j] = nw;
+                if (STATS) { stat_add_clamped(ga, v * gs, o.clamp); stat_add(pa, nw); }
+            }
         }
     }
     if (!update || !en.pk) return;
@@ -665,6 +679,25 @@ __global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __re
     for (int e = threadIdx.x; e < run * bt; e += 256) {
         const int tb = e >> sh, bl = e & (bt - 1);
         if (b0 + bl < en.B) d[tb * en.Bp + bl] = (half_t)t[bl * stride + tb];
+    }
+}
+__global__ __launch_bounds__(256) void apply_batch_kernel(const ApplyEntry* __restrict__ tab, int n, const ApplyOpt o) {
+    StatAcc ga, pa;
+    apply_batch_body<false>(tab, n, o, ga, pa);
+}
+// every block writes its two records (zeros for a block that updates nothing): part[2 b] gradient, part[2 b + 1] weights
+__global__ __launch_bounds__(256) void apply_batch_stats_kernel(const ApplyEntry* __restrict__ tab, int n, const ApplyOpt o,
+                                                                StatRec* __restrict__ part) {
+    __shared__ StatAcc red[4];
+    StatAcc ga, pa;
+    stat_init(ga);
+    stat_init(pa);
+    apply_batch_body<true>(tab, n, o, ga, pa);
+    const StatAcc g = stat_block(ga, red);
+    const StatAcc p = stat_block(pa, red);
+    if (threadIdx.x == 0) {
+        part[2 * (int64_t)blockIdx.x] = stat_rec(g, 0);
+        part[2 * (int64_t)blockIdx.x + 1] = stat_rec(p, 0);
     }
 }
 
@@ -689,6 +722,12 @@ int apply_entry_tiles(ApplyEntry& e, int TH, int TW, int KW, int py, int px, int
 int apply_batch_launch(const ApplyEntry* tab, int n, int total_tiles, const ApplyOpt& o, hipStream_t st) {
     if (total_tiles < 1 || n < 1) return OK;
     hipLaunchKernelGGL(apply_batch_kernel, dim3((unsigned)total_tiles), dim3(256), 0, st, tab, n, o);
+    return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
+}
+int apply_batch_stats_launch(const ApplyEntry* tab, int n, int total_tiles, const ApplyOpt& o, StatRec* part,
+                             hipStream_t st) {
+    if (total_tiles < 1 || n < 1) return OK;
+    hipLaunchKernelGGL(apply_batch_stats_kernel, dim3((unsigned)total_tiles), dim3(256), 0, st, tab, n, o, part);
     return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
 }
 

@@ -54,6 +54,35 @@ __device__ __forceinline__ half_t sat16(float v) {
     return (half_t)(v == v ? __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f) : v);
 }
 
+// Counting variants of the three apply kernels (the numerics monitor, fmri_bn_*_cnt): per lane, the results sat16 clips
+// (|v| > 65504, inf included) and the NaNs it stores; at the end of the kernel one ballot + popcount per bit of the lane
+// counts sums them over the wave and the wave's first lane adds them to cnt[0] / cnt[1] (integer adds: the totals do not
+// depend on the order).  COUNT = false compiles to the uncounted kernels' code.
+struct SatCount {
+    int sat = 0, nan = 0;
+};
+template <bool COUNT>
+__device__ __forceinline__ half_t sat16c(float v, SatCount& n) {
+    if (COUNT) {
+        const bool fin = v == v;
+        n.nan += fin ? 0 : 1;
+        n.sat += (fin && fabsf(v) > 65504.f) ? 1 : 0;
+    }
+    return sat16(v);
+}
+__device__ __forceinline__ void sat_count_flush(const SatCount& n, int* cnt) {
+    if (!__ballot((n.sat | n.nan) != 0)) return;            // (the healthy case: no atomic at all)
+    int s = 0, q = 0;
+    for (int b = 0; b < 24; ++b) {
+        s += __popcll(__ballot((n.sat >> b) & 1)) << b;
+        q += __popcll(__ballot((n.nan >> b) & 1)) << b;
+    }
+    if ((int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1) {
+        if (s) atomicAdd(cnt, s);
+        if (q) atomicAdd(cnt + 1, q);
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
                                                         half_t* __restrict__ dout, int M, int C, int cx_log2,
@@ -340,13 +369,13 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums, int C, float 
 }
 
 // MODE 0: y = act(x*scale + shift).   MODE 1: dx = gamma*rstd*(g - sum_g/M - xhat*sum_gx/M), g = dy*mask
-template <int MODE>
-__global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                        half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                        const float* __restrict__ p0, const float* __restrict__ p1,
-                                                        const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int relu, float inv_count,
-                                                        const float* __restrict__ sums) {
+template <int MODE, bool COUNT>
+__device__ __forceinline__ void bn_stream_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                               half_t* __restrict__ out, int M, int C, int cx_log2,
+                                               const float* __restrict__ p0, const float* __restrict__ p1,
+                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                               int relu, float inv_count, const float* __restrict__ sums,
+                                               SatCount& nc) {
     const int CX = 1 << cx_log2;
     const int RY = 256 >> cx_log2;
     const int cx = threadIdx.x & (CX - 1);
@@ -381,7 +410,7 @@ __global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict
                 const float xh = ((float)xv[j] - b[j]) * a[j];
                 float g = (float)gv[j];
                 if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
-                ov[j] = sat16(k[j] * (g - c0[j] - xh * c1[j]));
+                ov[j] = sat16c<COUNT>(k[j] * (g - c0[j] - xh * c1[j]), nc);
             }
         }
         *(h8*)(out + (int64_t)m * C + coff) = ov;
@@ -402,6 +431,26 @@ __global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict
         if (MODE == 1) gv = *(const h8*)(dy + (int64_t)m * C + coff);
         body(xv, gv, m);
     }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                        half_t* __restrict__ out, int M, int C, int cx_log2,
+                                                        const float* __restrict__ p0, const float* __restrict__ p1,
+                                                        const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, int relu, float inv_count,
+                                                        const float* __restrict__ sums) {
+    SatCount nc;
+    bn_stream_body<MODE, false>(x, dy, out, M, C, cx_log2, p0, p1, gamma, beta, relu, inv_count, sums, nc);
+}
+__global__ __launch_bounds__(256) void bn_stream_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                            half_t* __restrict__ out, int M, int C, int cx_log2,
+                                                            const float* __restrict__ p0, const float* __restrict__ p1,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, int relu, float inv_count,
+                                                            const float* __restrict__ sums, int* __restrict__ cnt) {
+    SatCount nc;
+    bn_stream_body<1, true>(x, dy, out, M, C, cx_log2, p0, p1, gamma, beta, relu, inv_count, sums, nc);
+    sat_count_flush(nc, cnt);
 }
 
 // ---- BatchNorm backward of TWO cotangent streams through one saved forward (the discriminator's logit stream A and
@@ -484,12 +533,13 @@ __global__ __launch_bounds__(256) void bn_reduce2_kernel(const half_t* __restric
 }
 
 // dx_s = gamma*rstd*(g_s - sum_g_s/M - xhat*sum_gx_s/M) for both streams, x read once
-__global__ __launch_bounds__(256) void bn_stream2_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                         half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, int relu, float inv_count,
-                                                         const float* __restrict__ sums /* [4][C] */) {
+template <bool COUNT>
+__device__ __forceinline__ void bn_stream2_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                half_t* __restrict__ out, int M, int C, int cx_log2,
+                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                int relu, float inv_count, const float* __restrict__ sums /* [4][C] */,
+                                                SatCount& nc) {
     const int CX = 1 << cx_log2;
     const int RY = 256 >> cx_log2;
     const int cx = threadIdx.x & (CX - 1);
@@ -515,8 +565,8 @@ __global__ __launch_bounds__(256) void bn_stream2_kernel(const half_t* __restric
             const float xh = ((float)xv[j] - b[j]) * a[j];
             const bool on = !relu || (xh * ga[j] + be[j] > 0.f);
             const float g_a = on ? (float)av[j] : 0.f, g_b = on ? (float)bv[j] : 0.f;
-            oa[j] = sat16(k[j] * (g_a - a0[j] - xh * a1[j]));
-            ob[j] = sat16(k[j] * (g_b - b0[j] - xh * b1[j]));
+            oa[j] = sat16c<COUNT>(k[j] * (g_a - a0[j] - xh * a1[j]), nc);
+            ob[j] = sat16c<COUNT>(k[j] * (g_b - b0[j] - xh * b1[j]), nc);
         }
         const int64_t o = (int64_t)m * C + coff;
         *(h8*)(out + o) = oa;
@@ -539,6 +589,26 @@ __global__ __launch_bounds__(256) void bn_stream2_kernel(const half_t* __restric
         const int64_t o = (int64_t)m * C + coff;
         body(*(const h8*)(x + o), *(const h8*)(dy + o), *(const h8*)(dy + sb + o), m);
     }
+}
+__global__ __launch_bounds__(256) void bn_stream2_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                         half_t* __restrict__ out, int M, int C, int cx_log2,
+                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                         const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, int relu, float inv_count,
+                                                         const float* __restrict__ sums /* [4][C] */) {
+    SatCount nc;
+    bn_stream2_body<false>(x, dy, out, M, C, cx_log2, mean, rstd, gamma, beta, relu, inv_count, sums, nc);
+}
+__global__ __launch_bounds__(256) void bn_stream2_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                             half_t* __restrict__ out, int M, int C, int cx_log2,
+                                                             const float* __restrict__ mean,
+                                                             const float* __restrict__ rstd,
+                                                             const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, int relu, float inv_count,
+                                                             const float* __restrict__ sums, int* __restrict__ cnt) {
+    SatCount nc;
+    bn_stream2_body<true>(x, dy, out, M, C, cx_log2, mean, rstd, gamma, beta, relu, inv_count, sums, nc);
+    sat_count_flush(nc, cnt);
 }
 
 // ---- BatchNorm over FEW rows (the dense layers: BatchNorm1d behind fc.0 / fc1.0, M = batch rows) in ONE launch per
@@ -617,14 +687,13 @@ __global__ __launch_bounds__(256) void bn_cols_fwd_kernel(const half_t* __restri
 
 // backward through (ReLU o BN) of NS cotangent streams stacked along the rows (dy = [stream 0 rows | stream 1 rows]);
 // sums [NS][2][C] = (sum g | sum g*xhat) per stream; dbeta / dgamma (may be null) += gscale * sums of stream `pstream`
-template <int NS>
-__global__ __launch_bounds__(256) void bn_cols_bwd_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                          half_t* __restrict__ dx, int M, int C, float inv_count,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, int relu,
-                                                          float* __restrict__ sums, float* __restrict__ dbeta,
-                                                          float* __restrict__ dgamma, float gscale, int pstream) {
+template <int NS, bool COUNT>
+__device__ __forceinline__ void bn_cols_bwd_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                 half_t* __restrict__ dx, int M, int C, float inv_count,
+                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 int relu, float* __restrict__ sums, float* __restrict__ dbeta,
+                                                 float* __restrict__ dgamma, float gscale, int pstream, SatCount& nc) {
     __shared__ float red[256 * 17];
     __shared__ float par[NS][COLS_CX * 8][2];
     const int cx = threadIdx.x & (COLS_CX - 1), ry = threadIdx.x >> 2;
@@ -691,11 +760,38 @@ __global__ __launch_bounds__(256) void bn_cols_bwd_kernel(const half_t* __restri
                 const float xh = ((float)xv[j] - mu[j]) * rs[j];
                 float g = (float)gv[j];
                 if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
-                ov[j] = sat16(ga[j] * rs[j] * (g - c0[j] - xh * c1[j]));
+                ov[j] = sat16c<COUNT>(ga[j] * rs[j] * (g - c0[j] - xh * c1[j]), nc);
             }
             *(h8*)(dx + st * sstride + o) = ov;
         }
     }
+}
+template <int NS>
+__global__ __launch_bounds__(256) void bn_cols_bwd_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                          half_t* __restrict__ dx, int M, int C, float inv_count,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int relu,
+                                                          float* __restrict__ sums, float* __restrict__ dbeta,
+                                                          float* __restrict__ dgamma, float gscale, int pstream) {
+    SatCount nc;
+    bn_cols_bwd_body<NS, false>(x, dy, dx, M, C, inv_count, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma, gscale,
+                                pstream, nc);
+}
+template <int NS>
+__global__ __launch_bounds__(256) void bn_cols_bwd_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                              half_t* __restrict__ dx, int M, int C, float inv_count,
+                                                              const float* __restrict__ mean,
+                                                              const float* __restrict__ rstd,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, int relu,
+                                                              float* __restrict__ sums, float* __restrict__ dbeta,
+                                                              float* __restrict__ dgamma, float gscale, int pstream,
+                                                              int* __restrict__ cnt) {
+    SatCount nc;
+    bn_cols_bwd_body<NS, true>(x, dy, dx, M, C, inv_count, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma, gscale,
+                               pstream, nc);
+    sat_count_flush(nc, cnt);
 }
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? OK : E_LAUNCH)
@@ -795,9 +891,20 @@ int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, co
 }
 int bn_cols_bwd_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, float* sums,
-                       float* dbeta, float* dgamma, float gscale, int pstream, hipStream_t st) {
+                       float* dbeta, float* dgamma, float gscale, int pstream, int* cnt, hipStream_t st) {
     const int nch = C / 8;
     const dim3 grid((nch + COLS_CX - 1) / COLS_CX);
+    if (cnt) {
+        if (nstreams == 1)
+            hipLaunchKernelGGL((bn_cols_bwd_cnt_kernel<1>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd,
+                               gamma, beta, relu, sums, dbeta, dgamma, gscale, pstream, cnt);
+        else if (nstreams == 2)
+            hipLaunchKernelGGL((bn_cols_bwd_cnt_kernel<2>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd,
+                               gamma, beta, relu, sums, dbeta, dgamma, gscale, pstream, cnt);
+        else
+            return E_UNSUPPORTED;
+        return LAUNCH_OK();
+    }
     if (nstreams == 1)
         hipLaunchKernelGGL((bn_cols_bwd_kernel<1>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd, gamma,
                            beta, relu, sums, dbeta, dgamma, gscale, pstream);
@@ -871,16 +978,26 @@ int bn_apply_launch(const half_t* x, half_t* y, int M, int C, const float* scale
 }
 int bn_bwd_apply2_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
                          const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
-                         hipStream_t st) {
+                         int* cnt, hipStream_t st) {
     const RowGeom g = stream_geometry(M, C);
+    if (cnt) {
+        hipLaunchKernelGGL(bn_stream2_cnt_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
+                           gamma, beta, relu, 1.f / count, sums4C, cnt);
+        return LAUNCH_OK();
+    }
     hipLaunchKernelGGL(bn_stream2_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
                        gamma, beta, relu, 1.f / count, sums4C);
     return LAUNCH_OK();
 }
 int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
                         const float* rstd, const float* gamma, const float* beta, int relu, const float* sums,
-                        hipStream_t st) {
+                        int* cnt, hipStream_t st) {
     const RowGeom g = stream_geometry(M, C);
+    if (cnt) {
+        hipLaunchKernelGGL(bn_stream_cnt_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
+                           gamma, beta, relu, 1.f / count, sums, cnt);
+        return LAUNCH_OK();
+    }
     hipLaunchKernelGGL((bn_stream_kernel<1>), dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean,
                        rstd, gamma, beta, relu, 1.f / count, sums);
     return LAUNCH_OK();

@@ -102,6 +102,12 @@ _SIGS = {
     "fmri_renorm_f64": [_p, _p, _l, _f, _p, _f, _p, _p, _p],
     "fmri_rmsprop": [_p, _p, _p, _l, _f, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p, _f, _p, _p],
+    "fmri_tensor_stats": [_p, _i, _p, _p],
+    "fmri_apply_batch_stats": [_p, _i, _i, _i, _p, _f, _f, _f, _p, _f, _p, _i, _p, _p],
+    "fmri_stat_fold": [_p, _i, _p, _p, _p],
+    "fmri_bn_bwd_apply_cnt": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p],
+    "fmri_bn_bwd_apply2_cnt": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p],
+    "fmri_bn_cols_bwd_cnt": [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p],
 }
 
 class Epilogue(C.Structure):
@@ -113,13 +119,24 @@ class Epilogue(C.Structure):
                 ("aff_scale", C.c_void_p), ("aff_shift", C.c_void_p), ("aff_relu", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class StatSeg(C.Structure):
+    """``fmri_stat_seg`` of include/fmri_hip.h (one segment of fmri_tensor_stats)."""
+    _fields_ = [("x", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64), ("div", C.c_void_p),
+                ("gate", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_float), ("clamp", C.c_float)]
+
+
+STAT_BYTES = 32          # sizeof(fmri_stat)
+STAT_MAX_SEGS = 8        # FMRI_STAT_MAX_SEGS
+
+
 EP_ACT_APPLIED = 0x40000000
 EP_AFFINE_APPLIED = 0x20000000
 
 
 EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_test_fastdiv", "fmri_bn_ws_floats",
                              "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
-                             "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes"])
+                             "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
+                             "fmri_tensor_stats_ws_bytes"])
 
 _lib = None
 
@@ -157,6 +174,8 @@ def load():
     lib.fmri_pcc_matrix_ws_bytes.argtypes = [_i, _i, _l]
     lib.fmri_ssim_pairs_ws_bytes.restype = _l
     lib.fmri_ssim_pairs_ws_bytes.argtypes = [_i, _i, _i, _i, _i]
+    lib.fmri_tensor_stats_ws_bytes.restype = _i
+    lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
     _lib = lib
     return lib
 

@@ -674,11 +674,13 @@ def materialize_grads(group):
     group.pending = []            # (defer_grads stays on: the rest of the pass may queue more)
 
 
-def apply_group(group, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0) -> bool:
+def apply_group(group, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0, stats: Optional[int] = None) -> bool:
     """RMSprop update of a whole sub-network from its deferred gradients + the fp16 GEMM copies of the new weights:
     fmri_apply_batch (one launch) and the pack launch(es) of the orientations it does not write.  Returns False -- after
     bringing the reference-layout gradient buffer up to date -- when the group has to take the separate launches
-    (nothing deferred, or a tensor the table cannot describe); the caller then runs the optimizer and the re-pack."""
+    (nothing deferred, or a tensor the table cannot describe); the caller then runs the optimizer and the re-pack.
+    ``stats``: device address of the numerics monitor's (gradient, weights) record pair (fmri_hip/monitor.py): the
+    update then also writes per-block statistics, folded into that pair behind it."""
     if not getattr(group, "defer_grads", False):
         return False
     done = getattr(group, "materialized", [])
@@ -697,8 +699,17 @@ def apply_group(group, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0) -> bool
     lib.note(bytes=22.0 * group.numel)
     gate = getattr(group, "grad_gate", None)
     gated = 1 if (gate is not None and flag is not None and gate.data_ptr() == flag.data_ptr()) else 0
-    lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps, 1.0,
-             _P(gdev), clamp, _P(flag), gated)
+    if stats is None:
+        lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps, 1.0,
+                 _P(gdev), clamp, _P(flag), gated)
+    else:
+        part = plan.get("stat_part")
+        if part is None:                  # two fmri_stat records per block, allocated with the plan
+            part = plan["stat_part"] = torch.empty(max(1, 2 * plan["tiles"]) * lib.STAT_BYTES, dtype=torch.uint8,
+                                                   device=group.device)
+        lib.call("fmri_apply_batch_stats", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps,
+                 1.0, _P(gdev), clamp, _P(flag), gated, _P(part))
+        lib.call("fmri_stat_fold", _P(part), plan["tiles"], _P(flag), stats)
     for p in group.pending:
         h = getattr(p[0], "_fmri_hold", None)
         if h is not None:
@@ -1008,6 +1019,7 @@ class BatchNorm:
 
     def __init__(self, group, prefix: str, C: int, perm=None):
         self.group, self.prefix, self.C, self.perm = group, prefix, C, perm
+        self.mon_cnt: Optional[int] = None      # numerics monitor: device int[2] the dx stores are counted into
         self.gamma, self.beta = group.views[prefix + "weight"], group.views[prefix + "bias"]
         self.ggamma, self.gbeta = group.grads[prefix + "weight"], group.grads[prefix + "bias"]
         self.rm, self.rv = group.bufs[prefix + "running_mean"], group.bufs[prefix + "running_var"]
@@ -1264,9 +1276,9 @@ class BatchNorm:
             if out is None:
                 out = torch.empty_like(dy)
             lib.note(bytes=10.0 * M * C)
-            lib.call("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 1, sv.count, _P(sv.mean), _P(sv.rstd), _P(gamma),
-                     _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if direct else None,
-                     _P(self.ggamma) if direct else None, (1.0 / param_scale) if direct else 0.0, 0)
+            self._call_counted("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 1, sv.count, _P(sv.mean), _P(sv.rstd),
+                               _P(gamma), _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if direct else None,
+                               _P(self.ggamma) if direct else None, (1.0 / param_scale) if direct else 0.0, 0)
             if param_scale is not None and self.perm:
                 self.accumulate_param_grads(sums, param_scale)
             return out, sums
@@ -1289,8 +1301,8 @@ class BatchNorm:
         if out is None:
             out = torch.empty_like(dy)
         lib.note(bytes=6.0 * M * C)
-        lib.call("fmri_bn_bwd_apply", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd), _P(gamma),
-                 _P(beta), 1 if relu else 0, _P(sums))
+        self._call_counted("fmri_bn_bwd_apply", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd),
+                           _P(gamma), _P(beta), 1 if relu else 0, _P(sums))
         return out, sums
 
     def backward2(self, raw: torch.Tensor, dy2: torch.Tensor, sv: BNSaved, relu: bool = True,
@@ -1313,9 +1325,9 @@ class BatchNorm:
             if out is None:
                 out = torch.empty_like(dy2)
             lib.note(bytes=16.0 * M * C)
-            lib.call("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 2, sv.count, _P(sv.mean), _P(sv.rstd), _P(gamma),
-                     _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if pg else None,
-                     _P(self.ggamma) if pg else None, (1.0 / param_scale) if pg else 0.0, int(param_stream))
+            self._call_counted("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 2, sv.count, _P(sv.mean), _P(sv.rstd),
+                               _P(gamma), _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if pg else None,
+                               _P(self.ggamma) if pg else None, (1.0 / param_scale) if pg else 0.0, int(param_stream))
             if param_scale is not None and self.perm:
                 self.accumulate_param_grads(sums[2 * int(param_stream):2 * int(param_stream) + 2], param_scale)
             return out, sums
@@ -1339,9 +1351,16 @@ class BatchNorm:
         if out is None:
             out = torch.empty_like(dy2)
         lib.note(bytes=10.0 * M * C)
-        lib.call("fmri_bn_bwd_apply2", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd), _P(gamma),
-                 _P(beta), 1 if relu else 0, _P(sums))
+        self._call_counted("fmri_bn_bwd_apply2", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd),
+                           _P(gamma), _P(beta), 1 if relu else 0, _P(sums))
         return out, sums
+
+    def _call_counted(self, name: str, *args):
+        """A dx launch of the backward pass; with the numerics monitor on, its counting variant (same dx)."""
+        if self.mon_cnt is None:
+            lib.call(name, *args)
+        else:
+            lib.call(name + "_cnt", *args, self.mon_cnt)
 
     def accumulate_param_grads(self, sums: torch.Tensor, scale: float):
         inv = 1.0 / scale

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib, ops
+from .monitor import Monitored
 from .nets import (CognitiveEncoderNet, DecoderNet, DiscriminatorNet, EncoderNet, WaeDiscriminatorNet,
                    refresh_net)
 from .ops import axpby, images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
@@ -79,6 +80,7 @@ class _Optim:
         self._lr = float(lr)
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=group.device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=group.device) if kind == "adam" else None
+        self.stats = None        # (monitor.Monitor, device address of its record pair): set by a monitored step
 
     @property
     def lr(self) -> float:
@@ -90,20 +92,27 @@ class _Optim:
 
     def step(self, flag: Optional[torch.Tensor] = None, clamp: float = 0.0, gdev: Optional[torch.Tensor] = None):
         g = self.g
-        if self.kind == "rmsprop" and ops.apply_group(g, self.s1, self.lr_dev, self.alpha, self.eps, flag, gdev, clamp):
+        mon, rec = self.stats if self.stats is not None else (None, None)
+        if self.kind == "rmsprop" and ops.apply_group(g, self.s1, self.lr_dev, self.alpha, self.eps, flag, gdev, clamp,
+                                                      stats=rec):
             return                               # deferred gradients: update + fp16 copies in one launch (ops.begin_grads)
+        if self.kind != "rmsprop":
+            ops.flush_pending(g)                 # (Adam has no fused form: deferred gradients -> reference layout)
+        if mon is not None:
+            mon.grad_stats(g.grad, gdev, clamp, flag, rec)
         if self.kind == "rmsprop":
             lib.note(bytes=20.0 * g.numel)       # read p, g, v; write p, v
             lib.call("fmri_rmsprop_dev", _P(g.data), _P(g.grad), _P(self.s1), g.numel, _P(self.lr_dev), self.alpha,
                      self.eps, 1.0, _P(gdev), clamp, _P(flag))
         else:
-            ops.flush_pending(g)                 # (Adam has no fused form: deferred gradients -> reference layout)
             self.t += 1
             b1, b2 = self.betas
             lib.call("fmri_counter_inc", _P(self.t_dev))
             lib.note(bytes=28.0 * g.numel)       # read p, g, m, v; write p, m, v
             lib.call("fmri_adam_dev", _P(g.data), _P(g.grad), _P(self.s1), _P(self.s2), g.numel, _P(self.lr_dev), b1, b2,
                      self.eps, _P(self.t_dev), 1.0, _P(gdev), clamp, _P(flag))
+        if mon is not None:
+            mon.param_stats(g.data, flag, rec)
         g.version += 1
 
 
@@ -258,7 +267,7 @@ def _attach_reducers(nets, d: _Dist):
             bn.reducer = r
 
 
-class _GanStepBase:
+class _GanStepBase(Monitored):
     """Shared pieces of the Stage-I/II/III steps: loss kernels, gate, scalar block, logging."""
 
     def _init_common(self, device, hp, scales, distributed, sync_bn, nets):
@@ -449,8 +458,10 @@ class Stage1Step(_GanStepBase):
     """Stage-I VAE/GAN step (image -> image)."""
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
-                 distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True):
-        """``mode``: the loss composition of train_vgan_stage1.py:359-388 -- 'vae-gan' (default), 'beta-vae' (KL weight
+                 distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
+                 monitor: bool = False):
+        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``mode``: the loss composition of train_vgan_stage1.py:359-388 -- 'vae-gan' (default), 'beta-vae' (KL weight
         hp.beta / batch), 'dcgan' (pixel nle, encoder not trained), 'vae' (pixel nle, discriminator not trained unless
         the gate re-arms both).  ``gate_skip``: in ``step`` the weight-gradient GEMMs of the decoder / discriminator are
         conditioned on the equilibrium gate's device flags (fmri_wgrad_if) -- a sub-network the gate does not train in a
@@ -473,6 +484,8 @@ class Stage1Step(_GanStepBase):
         self.opt_dis = _Optim(self.dis.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.enc_updates = 1                 # encoder passes per batch in the script (BN running-stat updates)
         self.extra_mu_decoder_pass = False   # DualStage1Step (wae_steps.py)
+        self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
+                                     ("discriminator", self.opt_dis, self.dis)], 1)
 
     # ---- parameters -----------------------------------------------------------------------------
     def load_recipe(self, seed: int, perturb: bool = False):
@@ -500,6 +513,8 @@ class Stage1Step(_GanStepBase):
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = x.device
         self.scal.zero_()
+        if self.mon is not None:
+            self.mon.zero()
         # decoder groups: z (x_tilde), z_p (x_p) and -- Dual step only -- mu (wae_vgan_stage1.py:406, BN statistics)
         G = 3 if self.extra_mu_decoder_pass else 2
         dec_out = torch.empty((1 + G) * B, H, W, 8, dtype=torch.float16, device=dev)
@@ -675,7 +690,15 @@ class Stage1Step(_GanStepBase):
         opt.step(flag, gdev=self._slot(slot))
         refresh_net(net)
 
+    def _monitor_tail(self):
+        if self.mon is not None:
+            self.mon.tail(self.fw["head32"], self.cfg.latent_dim, self._monitor_losses(), self.zs)
+
+    def _monitor_losses(self):
+        return [self.scal[:len(LOG_KEYS)]]
+
     def apply(self):
+        self._monitor_tail()
         if self.mode != "dcgan":                         # 'dcgan': train_enc = False (train_vgan_stage1.py:376)
             self.opt_enc.step(None, gdev=self._slot(S_NE))
         if getattr(self, "_applied_early", False):
@@ -776,8 +799,9 @@ class CognitiveStep(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 gate_skip: bool = True, mode: str = "vae-gan"):
-        """``mode``: 'vae-gan' (default) or 'vae' -- the scripts' `--mode vae` (train_vgan_stage2.py:234-238,362-366;
+                 gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False):
+        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``mode``: 'vae-gan' (default) or 'vae' -- the scripts' `--mode vae` (train_vgan_stage2.py:234-238,362-366;
         train_vgan_stage3.py:370-374): no teacher net (the discriminator's "real" slot is the ground-truth image), the
         reconstruction term is the PIXEL nle instead of the feature mse, the discriminator loss bce_orig + bce_sampled.
         Stage II: encoder <- d(KL + nle) through the frozen decoder, discriminator trained (the script's train_dis = False
@@ -801,6 +825,8 @@ class CognitiveStep(_GanStepBase):
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dec = _Optim(self.dec.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dis = _Optim(self.dis.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
+        self._init_monitor(monitor, [("encoder", self.opt_enc, self.cog), ("decoder", self.opt_dec, self.dec),
+                                     ("discriminator", self.opt_dis, self.dis)], 1)
 
     def load_recipe(self, seed: int, perturb: bool = False):
         """Teacher VaeGan weights from seed, cognitive encoder from seed+100 (the golden-fixture recipe)."""
@@ -848,6 +874,8 @@ class CognitiveStep(_GanStepBase):
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         self.scal.zero_()
+        if self.mon is not None:
+            self.mon.zero()
         disc_in = torch.empty(3 * B, H, W, 8, dtype=torch.float16, device=dev)
         fmri16 = rows_to_f16(fmri)
         head32, cctx = self.cog.forward(fmri16)
@@ -960,6 +988,8 @@ class CognitiveStep(_GanStepBase):
         self.dd.wait_all()
 
     def apply(self):
+        if self.mon is not None:
+            self.mon.tail(self.fw["head32"], self.cfg.latent_dim, [self.scal[:len(LOG_KEYS)]], self.zs)
         if self.stage == 2:
             self.opt_enc.step(None, clamp=1.0, gdev=self._slot(S_NE))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))

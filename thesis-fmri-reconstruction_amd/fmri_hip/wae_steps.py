@@ -32,8 +32,9 @@ from .nets import CognitiveEncoderNet, DecoderNet, EncoderNet, WaeDiscriminatorN
 from .mmd import mmd_imq
 from .ops import images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
-from .steps import (S_ESQ, S_NA, S_NB, S_NE, GanHyper, Scales, Stage1Step, _attach_reducers, _Dist, _GanStepBase,
-                    _Optim)
+from .monitor import Monitored
+from .steps import (LOG_KEYS, S_ESQ, S_NA, S_NB, S_NE, GanHyper, Scales, Stage1Step, _attach_reducers, _Dist,
+                    _GanStepBase, _Optim)
 
 _P = lib.ptr
 
@@ -91,7 +92,7 @@ class _LatentDiscPhase:
         return wd.backward(ctx, dlogit, gscale, False, True)
 
 
-class WaeStep(_LatentDiscPhase):
+class WaeStep(_LatentDiscPhase, Monitored):
     """WAE/GAN Stage I / II / III step.
 
     ``penalty``: "gan" (default) the scripts' latent discriminator; "mmd" the IMQ-kernel MMD_u between the trained
@@ -103,7 +104,8 @@ class WaeStep(_LatentDiscPhase):
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 penalty: str = "gan"):
+                 penalty: str = "gan", monitor: bool = False):
+        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py)."""
         assert stage in (1, 2, 3)
         if penalty not in ("gan", "mmd"):
             raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
@@ -127,6 +129,8 @@ class WaeStep(_LatentDiscPhase):
         self.opt_dec = _Optim(self.dec.group, "adam", hp_.lr_dec, betas=hp_.betas)
         self.opt_dis = _Optim(self.wd.group, "adam", hp_.lr_dis, betas=hp_.betas)
         self.fw = {}
+        self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
+                                     ("discriminator", self.opt_dis, self.wd)], 1)
 
     # ---- parameters (the golden-fixture recipes of tests/golden/make_golden.py) --------------------------
     def load_recipe(self, seed: int, perturb: Optional[bool] = None):
@@ -162,6 +166,8 @@ class WaeStep(_LatentDiscPhase):
         dev = image.device
         Bg = B * self.dd.world
         self.scal.zero_()
+        if self.mon is not None:
+            self.mon.zero()
         x16 = images_to_nhwc(image)
         gan = self.penalty == "gan"
 
@@ -241,6 +247,8 @@ class WaeStep(_LatentDiscPhase):
         if train_dec:
             self.opt_dec.step()
         self.fw = dict(B=B, y=y, head32=head32, Z=Z)
+        if self.mon is not None:
+            self.mon.tail(head32, Z, [self.scal[:len(W_LOG_KEYS)]], None)
         return self.scal
 
     def _mmd_penalty(self, head32, p32, w: float, need_dz: bool):
@@ -322,7 +330,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
-                 mode: str = "vae-gan"):
+                 mode: str = "vae-gan", monitor: bool = False):
         super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode)
         hp = self.hp
         self.lam = lam
@@ -333,6 +341,12 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self.enc_updates = 3
         self.extra_mu_decoder_pass = True
         self._it = 0
+        self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
+                                     ("discriminator", self.opt_dis, self.dis),
+                                     ("wae_discriminator", self.opt_wd, self.wd)], 2)
+
+    def _monitor_losses(self):
+        return [self.scal[:len(LOG_KEYS)], self.wscal[:len(W_LOG_KEYS)]]
 
     def load_recipe(self, seed: int, perturb: bool = False):
         super().load_recipe(seed, perturb)

@@ -7,6 +7,7 @@ One process = one arm (the engine's switches are read from the environment at im
     FMRI_SIDE_STREAM=off python tools/nan_hunt.py ...                        # one stream
     python tools/nan_hunt.py --mode hybrid ...                               # recorded forward + eager two-stream backward
     python tools/nan_hunt.py --det --repeats 2 ...                           # deterministic reductions: checksums must agree
+    python tools/nan_hunt.py --numerics ...                                  # + per-step sat16 / clamp / latent range counts
 
 Every repeat builds a fresh Stage1Step with bench.py's weights (recipe 0) and rotating synthetic batches and runs
 ``--steps`` steps with NO host synchronisation; the per-step loss block (and, with --diag, max |mu|, max logvar and the
@@ -34,11 +35,11 @@ import torch  # noqa: E402
 NBATCH = 8
 
 
-def build(dev, B, gate_skip, seed_shift=0):
+def build(dev, B, gate_skip, seed_shift=0, monitor=False):
     from fmri_hip.params import ArchConfig
     from fmri_hip.steps import Stage1Step
     cfg = ArchConfig.px64()
-    st = Stage1Step(cfg, dev, gate_skip=gate_skip)
+    st = Stage1Step(cfg, dev, gate_skip=gate_skip, monitor=monitor)
     st.load_recipe(0, False)
     mk = lambda s, shape, normal: torch.from_numpy(
         (np.random.RandomState(s).standard_normal(shape) if normal else np.random.RandomState(s).uniform(-1, 1, shape))
@@ -189,7 +190,7 @@ def run_repeat(a, dev, rep):
         return run_other(a, dev, rep)
     from fmri_hip import ops
     from fmri_hip.steps import (S_GDEC, S_NA, S_NB, S_NE)
-    st, xs, nz = build(dev, a.batch, a.gate_skip)
+    st, xs, nz = build(dev, a.batch, a.gate_skip, monitor=a.numerics)
     Z = st.cfg.latent_dim
     eager = lambda i: st.step(xs[i % NBATCH], nz[i % NBATCH][0], nz[i % NBATCH][1])
     run = eager
@@ -205,12 +206,14 @@ def run_repeat(a, dev, rep):
             j = i % NBATCH
             sb[0].copy_(xs[j]); sb[1].copy_(nz[j][0]); sb[2].copy_(nz[j][1])
             return replay()
-    rec, diag, snaps = [], [], []
+    rec, diag, snaps, blocks = [], [], [], []
     for i in range(n0, n0 + a.steps):
         if a.snap:
             snaps.append(snapshot(st))
         run(i)
         rec.append(st.scal[:22].clone())
+        if a.numerics:
+            blocks.append(st.numerics_block().clone())        # (no sync: decoded at the end)
         if a.diag:
             h = st.fw["head32"]
             diag.append(torch.stack([h[:, :Z].abs().max(), h[:, Z:].max(), h[:, Z:].min(), st.scal[S_NA], st.scal[S_NB],
@@ -236,9 +239,34 @@ def run_repeat(a, dev, rep):
         out["max_logvar_over_run"] = float(np.nanmax(D[:, 1]))
         out["max_mu_over_run"] = float(np.nanmax(D[:, 0]))
         out["loss_tail"] = [[float("%.5g" % v) for v in row[:6]] for row in R[lo:k + 1]]
+    if a.numerics:
+        out["numerics"] = numerics_table(st, blocks)
     if a.snap and first_bad is not None:
         out["replay"] = replay_from(a, st, xs, nz, snaps, first_bad, n0)
     return out
+
+
+def numerics_table(st, blocks):
+    """--numerics: per step, the BatchNorm-backward stores sat16 clipped / NaNs it stored (all layers), the clamp and
+    non-finite counts of the consumed gradients, the latent range exponents; steps with nothing to report are
+    summarised by their count."""
+    from fmri_hip import monitor
+    rows, quiet = [], 0
+    for i, b in enumerate(blocks):
+        d = monitor.decode(b.cpu().numpy(), st.mon.layout)
+        sat = sum(v["saturated"] for v in d["bn_backward"].values())
+        nan = sum(v["nonfinite"] for v in d["bn_backward"].values())
+        clamped = sum(v["clamped"] or 0 for v in d["grad"].values())
+        gnf = sum(v["nonfinite"] or 0 for v in d["grad"].values())
+        rexp = [int(e) for e in d["latent"]["range_exp"]]
+        if sat or nan or clamped or gnf or any(rexp) or not d["losses_finite"]:
+            layers = {k: v for k, v in d["bn_backward"].items() if v["saturated"] or v["nonfinite"]}
+            rows.append(dict(step=i, bn_saturated=sat, bn_nan=nan, bn_layers=layers, grad_clamped=clamped,
+                             grad_nonfinite=gnf, range_exp=rexp, losses_finite=d["losses_finite"],
+                             grad_norm={k: v["norm"] for k, v in d["grad"].items()}))
+        else:
+            quiet += 1
+    return dict(steps_quiet=quiet, events=rows)
 
 
 def replay_from(a, st, xs, nz, snaps, k, n0):
@@ -276,6 +304,8 @@ def main():
     ap.add_argument("--det", action="store_true")
     ap.add_argument("--diag", action="store_true")
     ap.add_argument("--snap", action="store_true")
+    ap.add_argument("--numerics", action="store_true",
+                    help="stage1: run with monitor=True and report per-step saturation / clamp / range counts")
     ap.add_argument("--gate-skip", action="store_true", help="engine default (bench headline runs with it off)")
     ap.add_argument("--tag", default="")
     a = ap.parse_args()
