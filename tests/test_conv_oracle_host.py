@@ -1,0 +1,161 @@
+"""Host side of tests/test_fullbatch_conv_gpu.py, no GPU needed: the float64 slicing-and-matmul reference
+(tests/conv_oracle.py) against torch's float64 convolutions and autograd on the CPU, and the weight-gradient route table
+of the GPU module against the library's own host functions, with the conditions the table as a whole has to cover."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import conv_oracle as CO
+import test_fullbatch_conv_gpu as T
+
+RTOL = 1e-12
+
+
+def _rel(got, ref):
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got - ref).abs().max() / ref.abs().max())
+
+
+SIZES = [(9, 11), (13, 7), (16, 16), (25, 25)]
+
+
+@pytest.mark.parametrize("chunk", [None, 1, 2])
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("H,W", SIZES)
+def test_conv_oracle_matches_float64_torch(H, W, stride, chunk):
+    torch.manual_seed(H * 31 + W + stride)
+    N, cin, cout = 3, 5, 7
+    x = torch.randn(N, cin, H, W, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(cout, cin, 5, 5, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(x, w, None, stride, 2)
+    dy = torch.randn_like(y)
+    y.backward(dy)
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous()
+    assert _rel(CO.conv_fwd(nhwc(x), w.detach(), stride, 2, chunk), nhwc(y)) <= RTOL
+    assert _rel(CO.conv_dgrad(nhwc(dy), w.detach(), stride, 2, H, W, chunk), nhwc(x.grad)) <= RTOL
+    assert _rel(CO.conv_wgrad(nhwc(x), nhwc(dy), 5, stride, 2, chunk), w.grad) <= RTOL
+    assert _rel(CO.bias_grad(nhwc(dy)), dy.sum((0, 2, 3))) <= RTOL
+
+
+@pytest.mark.parametrize("chunk", [None, 1, 2])
+@pytest.mark.parametrize("out_pad", [0, 1])
+@pytest.mark.parametrize("H,W", SIZES)
+def test_deconv_oracle_matches_float64_torch(H, W, out_pad, chunk):
+    torch.manual_seed(H * 17 + W + out_pad)
+    N, cin, cout = 3, 6, 4
+    x = torch.randn(N, cin, H, W, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(cin, cout, 5, 5, dtype=torch.float64, requires_grad=True)
+    y = F.conv_transpose2d(x, w, None, 2, 2, output_padding=out_pad)
+    dy = torch.randn_like(y)
+    y.backward(dy)
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous()
+    assert y.shape[2] == CO.deconv_out_size(H, 5, 2, 2, out_pad) and y.shape[3] == CO.deconv_out_size(W, 5, 2, 2, out_pad)
+    assert _rel(CO.deconv_fwd(nhwc(x), w.detach(), 2, 2, out_pad, chunk), nhwc(y)) <= RTOL
+    assert _rel(CO.deconv_dgrad(nhwc(dy), w.detach(), 2, 2, chunk), nhwc(x.grad)) <= RTOL
+    assert _rel(CO.deconv_wgrad(nhwc(x), nhwc(dy), 5, 2, 2, chunk), w.grad) <= RTOL
+
+
+def test_chunks_keep_the_temporaries_of_the_largest_layers_near_one_gib():
+    for name, (kind, cin, cout, stride, H, op, N) in T.CASES:
+        Ho = T.geometry(kind, cin, cout, stride, H, op, N)["Ho"]
+        n = T._chunk((kind, cin, cout, stride, H, op, N), Ho)
+        big_hw, big_c, small_hw, small_c = ((H, cin, Ho, cout) if kind == "conv" else (Ho, cout, H, cin))
+        worst = 8 * n * max((big_hw + 4) ** 2 * big_c, small_hw ** 2 * max(big_c, small_c))
+        assert 1 <= n <= N and (worst <= 2 ** 30 or n == 1), (name, n, worst)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the route table
+# ---------------------------------------------------------------------------------------------------------------------
+def test_plane_pieces_restatement_agrees_with_the_library():
+    """max over the planes of T.plane_pieces == fmri_wgrad_slabs, over a sweep of tile counts and budgets."""
+    from fmri_hip import lib
+    L = lib.load()
+    for N in list(range(1, 70)) + [96, 128, 256, 512, 768, 1000]:
+        for Yc in (2, 8, 13, 16, 32):
+            ntiles = N * ((Yc + 7) // 8) ** 2
+            for splits in (1, 4, 5, 8, 10, 16, 20, 32, 40, 64, 80, 128, 160, 256):
+                assert max(T.plane_pieces(ntiles, splits)[1]) == L.fmri_wgrad_slabs(N, Yc, Yc, 5, 2, splits), \
+                    (N, Yc, splits)
+
+
+def test_route_table_is_what_the_library_and_run_wgrad_give():
+    """ROUTES, written out in the GPU module, equals the restated conditions of ops.run_wgrad; the slab counts behind
+    it are the library's (fmri_wgrad_slabs, fmri_wgrad_narrow_blocks); the constants the restatement uses are ops'."""
+    from fmri_hip import lib, ops
+    L = lib.load()
+    assert (ops._WW_SLABS, ops._WW_SIDE_BLOCKS, ops._WW_BLOCKS, ops._WW_ON, ops._WN_ON) == (24, 160, 0, True, True)
+    assert set(T.ROUTES) == {name for name, _ in T.CASES} and len(T.CASES) == 22
+    for name, case in T.CASES:
+        kind, cin, cout, stride, H, op, N = case
+        g = T.geometry(*case)
+        for si, setting in enumerate(T.SETTINGS):
+            route = T.wgrad_route(case, setting)
+            assert T.ROUTES[name][si] == route, (name, setting, T.ROUTES[name][si], route)
+            kern, mode, splits, detail = route
+            print(f"[fullbatch-conv] route {name:28s} {setting:16s} {kern:8s} atomic={mode} splits={splits:3d} {detail}")
+            if kern == "win":
+                assert max(detail) == L.fmri_wgrad_slabs(N, g["Yc"], g["Yc"], 5, 2, splits), (name, setting)
+                assert (mode == 2) == (max(detail) <= 24 or setting == "deterministic")
+            elif kern == "narrow":
+                assert detail == (L.fmri_wgrad_narrow_blocks(N, g["Yc"], g["Yc"]) if setting == "deterministic" else 4)
+            else:
+                assert mode in (0, 1, 4) and (mode == 4) == (setting == "deterministic" and splits > 1)
+
+
+def _win(setting_filter=None):
+    """(name, setting, mode, splits, ntiles, tiles per piece, pieces) of every window-kernel route of the table."""
+    out = []
+    for name, case in T.CASES:
+        g = T.geometry(*case)
+        ntiles = case[6] * ((g["Yc"] + 7) // 8) ** 2
+        for si, setting in enumerate(T.SETTINGS):
+            kern, mode, splits, detail = T.ROUTES[name][si]
+            if kern == "win":
+                tps, pieces = T.plane_pieces(ntiles, splits)
+                assert pieces == detail
+                out.append((name, setting, mode, splits, ntiles, tps, pieces))
+    return out
+
+
+def test_route_table_covers_the_piece_edges():
+    """What the table as a whole has to hold; a routing change that loses one of these fails here, not silently."""
+    win = _win()
+    slab = [r for r in win if r[2] == 2]
+    unequal = [r for r in slab if len(set(r[6])) > 1]
+    assert unequal, "window kernel, slab mode, unequal plane pieces"
+    # at scale: pieces of 150 - 770 tiles with a shorter last piece, 6 - 10 slabs, under both budgets
+    at_scale = [r for r in unequal if min(r[5]) >= 150 and max(r[5]) <= 770 and 6 <= max(r[6]) <= 10
+                and any(r[4] % t for t in r[5])]
+    assert {r[1] for r in at_scale} == set(T.SETTINGS), at_scale
+    assert any(r[4] == 3072 and r[5][0] == 308 and r[4] - 9 * 308 == 300 for r in at_scale), "300 of 308"
+    # a last piece of exactly one tile, on a plane with more than one piece
+    assert any(p > 1 and r[4] - (p - 1) * t == 1 for r in slab for t, p in zip(r[5], r[6])), "one-tile last piece"
+    # some planes clamped to the tile count and others not
+    clamped = [[aim > r[4] for aim in T.planned_pieces(r[4], r[3])] for r in slab]
+    assert any(any(c) and not all(c) for c in clamped), "planes clamped to ntiles beside planes that are not"
+    # atomic mode of the window kernel, on the 32- and on the 64-channel layers
+    atomic = {T.geometry(*dict(T.CASES)[r[0]])["Bc"] for r in win if r[2] == 1}
+    assert atomic == {32, 64}, atomic
+    # deterministic mode turns those into more than 24 slabs
+    assert any(r[2] == 2 and max(r[6]) > 24 and r[1] == "deterministic" for r in win)
+    routes = [(name, T.geometry(*case), T.ROUTES[name]) for name, case in T.CASES]
+    narrow = [(n, g, r) for n, g, r in routes if r[0][0] == "narrow"]
+    assert any(not g["flip"] for _, g, _ in narrow), "narrow kernel, direct"
+    assert any(g["flip"] for _, g, _ in narrow), "narrow kernel, role-exchanged"
+    assert any(g["flip"] and dict(T.CASES)[n][6] * (g["Yc"] // 8) ** 2 == 32768 for n, g, _ in narrow), "exactly 32 768 tiles"
+    assert all(r[2] == ("narrow", 3, 768, 768) for _, _, r in narrow), "one slab per block in deterministic mode"
+    generic = [r for _, _, r in routes if r[0][0] == "generic"]
+    assert any(r[0][1] == 1 and r[0][2] > 1 for r in generic), "generic kernel, K splits in atomic mode"
+    assert any(r[2][1] == 4 and r[2][3] == r[2][2] for r in generic), "generic kernel, slab mode 4, every slab stored"
+    assert any(r[2][1] == 4 and 0 < r[2][3] < r[2][2] for r in generic), "slab mode 4, fewer slabs stored than allocated"
+
+
+def test_cases_are_the_full_size_list_plus_the_edges():
+    from test_kernels_gpu import FULL_SIZE
+    assert [c for _, c in T.CASES[:19]] == list(FULL_SIZE)
+    assert len({n for n, _ in T.CASES}) == len(T.CASES)
+    # the epilogue layers are the stride-1 / stride_gan first discriminator layer and the decoder's last layer
+    for name, act in T.EPILOGUE.items():
+        kind, cin, cout = dict(T.CASES)[name][:3]
+        assert (kind, cin, cout) == (("conv", 3, 32) if act == T.RELU else ("conv", 32, 3))
