@@ -22,47 +22,10 @@
 //   * BatchNorm batch statistics of the stored values leave the block as one row of the partial-sum buffer (StatEpi).
 // Tiles: 8 x 16 output pixels of one image (Wo > 8) or 8 x 8 of two images; 4 waves (2 x 2), two blocks per CU.
 #include "kernels.h"
-#include <type_traits>
+#include "pipe.h"
 
 namespace fmri {
 
-
-namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_c(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_c<I + 1, N>(f);
-    }
-}
-
-// 16-byte buffer -> LDS DMA (see igemm_tc5.hip::bdma16)
-__device__ __forceinline__ void cdma16(v4i srd, uint32_t voff, uint32_t soff, uint32_t lds) {
-    srd.x = __builtin_amdgcn_readfirstlane(srd.x);
-    srd.y = __builtin_amdgcn_readfirstlane(srd.y);
-    srd.z = __builtin_amdgcn_readfirstlane(srd.z);
-    srd.w = __builtin_amdgcn_readfirstlane(srd.w);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(srd), "s"(soff), "s"(lds)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmc() {
-    static_assert(N >= 0 && N <= 15, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// the 25 taps in phase order: 15 taps of the even rows (ky = 0, 2, 4), then 10 of the odd rows (ky = 1, 3)
-constexpr int c5_ky(int i) { return i < 15 ? 2 * (i / 5) : 1 + 2 * ((i - 15) / 5); }
-constexpr int c5_kx(int i) { return i < 15 ? i % 5 : (i - 15) % 5; }
-
-}  // namespace
 
 // PW: tile width (16: one image, 8: two images).  STATS: 0 none, 1 BatchNorm forward statistics (StatEpi),
 // 2 BatchNorm backward statistics + ReLU mask (BnBwdEpi).
@@ -105,6 +68,7 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
     };
     tile_geom(tile0, grp, y0, x0);
 
+    // (not make_srd: changes instruction order)
     v4i srd_in, srd_w;
     srd_in.x = (int)(uint32_t)(uintptr_t)a.in;
     srd_in.y = (int)(uint32_t)((uintptr_t)a.in >> 32);
@@ -159,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
         const uint32_t so = (uint32_t)sub * 64u;
 #pragma unroll
         for (int e = lo; e < hi; ++e)
-            if (e < NSL) cdma16(srd_in, rp ? soff1[e] : soff0[e], so, lds_wave + rp * WINB + e * 4096);
+            if (e < NSL) bdma16(srd_in, rp ? soff1[e] : soff0[e], so, lds_wave + rp * WINB + e * 4096);
     };
 
     // ---- weight DMA: tap slot = [128 co][32 ch] = 8 KB, 64 rows per block instruction; chunk swizzle 2*bit2(row)
@@ -174,11 +138,11 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             if (t0 + s < 25) {
-                const int tap = c5_ky(t0 + s) * 5 + c5_kx(t0 + s);
+                const int tap = k5s2_ky(t0 + s) * 5 + k5s2_kx(t0 + s);
                 const uint32_t so = (uint32_t)(tap * Ci2 + sub * 64);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
-                    cdma16(srd_w, vw, so + i * rs64, lds_wave + WBUF0 + stg * W_BYTES + s * 8192 + i * 4096);
+                    bdma16(srd_w, vw, so + i * rs64, lds_wave + WBUF0 + stg * W_BYTES + s * 8192 + i * 4096);
             }
         }
     };
@@ -217,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
         h8 af[NS][TM], bf[NS][TN];
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const int ky = c5_ky(t0 + s), kx = c5_kx(t0 + s);
+            const int ky = k5s2_ky(t0 + s), kx = k5s2_kx(t0 + s);
             const char* Ps = smem + (ky & 1) * WINB + (ky >> 1) * (ROW * 64);
             const char* Ws = smem + stg * W_BYTES + s * 8192;
 #pragma unroll
@@ -258,16 +222,16 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
     auto run_sub = [&](auto P_, int sub, bool more, int nsubi, bool switch_tile, int ng, int ny, int nx, bool landed)
                        __attribute__((always_inline)) {
         constexpr int P = decltype(P_)::value;
-        static_for_c<0, 13>([&](auto T_) __attribute__((always_inline)) {
+        static_for<0, 13>([&](auto T_) __attribute__((always_inline)) {
             constexpr int t = decltype(T_)::value;
             constexpr int stg = (P + t) & 1;
             // window slices issued behind the weight tiles of the PREVIOUS step
             constexpr int prev_n = (t >= 1 && t <= 6) ? 1 : ((t == 9 || t == 10) ? 2 : ((t == 11 || t == 12) ? 1 : 0));
             constexpr bool prev_cond = t >= 9;             // ... only when another (tile, sub-chunk) follows
-            if constexpr (t == 0) { if (!landed) wait_vmc<0>(); }
-            else if constexpr (prev_n == 0) wait_vmc<0>();
-            else if constexpr (prev_cond) { if (more) wait_vmc<prev_n>(); else wait_vmc<0>(); }
-            else wait_vmc<prev_n>();
+            if constexpr (t == 0) { if (!landed) wait_vmcnt<0>(); }
+            else if constexpr (prev_n == 0) wait_vmcnt<0>();
+            else if constexpr (prev_cond) { if (more) wait_vmcnt<prev_n>(); else wait_vmcnt<0>(); }
+            else wait_vmcnt<prev_n>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
@@ -375,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void igemm_c5_kernel(const C5Args a) {
         ++sub;
         landed = false;
         if (last_sub) {
-            if (next_tile) { wait_vmc<0>(); landed = true; }     // the next tile's first window and weights
+            if (next_tile) { wait_vmcnt<0>(); landed = true; }     // the next tile's first window and weights
             epilogue();
 #pragma unroll
             for (int i = 0; i < TN; ++i)

@@ -24,7 +24,7 @@
 // ds_read_b128 with the chunk swizzle 2*bit2(column)), weights straight out of the [co][tap * Ci + ci] matrix, buffer
 // descriptor DMA with hardware zero fill, compile-time tap loops, eval-mode BatchNorm folded in (AffEpi).
 #include "kernels.h"
-#include <type_traits>
+#include "pipe.h"
 
 #ifndef C5W_NSTG
 #define C5W_NSTG 2      // weight ring stages (16 KB each); deeper rings measured no faster
@@ -33,39 +33,6 @@
 namespace fmri {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_w(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_w<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ void wdma(v4i srd, uint32_t voff, uint32_t soff, uint32_t lds) {
-    srd.x = __builtin_amdgcn_readfirstlane(srd.x);
-    srd.y = __builtin_amdgcn_readfirstlane(srd.y);
-    srd.z = __builtin_amdgcn_readfirstlane(srd.z);
-    srd.w = __builtin_amdgcn_readfirstlane(srd.w);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(srd), "s"(soff), "s"(lds)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmw() {
-    static_assert(N >= 0 && N <= 63, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// the 25 taps in phase order: 15 taps of the even rows (ky = 0, 2, 4), then 10 of the odd rows (ky = 1, 3)
-constexpr int w5_ky(int i) { return i < 15 ? 2 * (i / 5) : 1 + 2 * ((i - 15) / 5); }
-constexpr int w5_kx(int i) { return i < 15 ? i % 5 : (i - 15) % 5; }
 
 // ---- DMA schedule of one 32-channel sub-chunk (13 K-steps), ring of NSTG weight stages filled D = NSTG - 1 steps ahead.
 // Issued behind the barrier of step t, in this order: the 4 weight pieces of step t + D (of the next sub-chunk past step 12),
@@ -155,15 +122,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
         const int tid = threadIdx.x & 255;
         const int lw = wave - 4;
         const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-        v4i srd_in, srd_w;
-        srd_in.x = (int)(uint32_t)(uintptr_t)a.in;
-        srd_in.y = (int)(uint32_t)((uintptr_t)a.in >> 32);
-        srd_in.z = (int)a.in_bytes;
-        srd_in.w = 0x00020000;
-        srd_w.x = (int)(uint32_t)(uintptr_t)a.w;
-        srd_w.y = (int)(uint32_t)((uintptr_t)a.w >> 32);
-        srd_w.z = (int)a.w_bytes;
-        srd_w.w = 0x00020000;
+        const v4i srd_in = make_srd(a.in, a.in_bytes), srd_w = make_srd(a.w, a.w_bytes);
 
         // ---- window DMA: 16-B unit q = e*256 + tid of a window buffer holds channels 8*cc .. 8*cc+7 (of the 32-channel
         // sub-chunk) of window pixel p = q >> 2 = image ip, row j, column position ii; cc = (q & 3) ^ 2*bit2(ii) (PW = 16) or
@@ -207,7 +166,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
         // slice E of sub-chunk `sub`, phase RP, into window buffer RP
         auto load_slice = [&](auto RP_, int sub, auto E_) __attribute__((always_inline)) {
             constexpr int rp = decltype(RP_)::value, e = decltype(E_)::value;
-            if constexpr (e < NSL) wdma(srd_in, rp ? soff1[e] : soff0[e], (uint32_t)sub * 64u, lds_wave + rp * WINB + e * 4096);
+            if constexpr (e < NSL) bdma16(srd_in, rp ? soff1[e] : soff0[e], (uint32_t)sub * 64u, lds_wave + rp * WINB + e * 4096);
         };
         // ---- weight DMA: tap slot = [128 co][32 ch] = 8 KB, 64 rows per instruction of the four waves; chunk swizzle
         // 2*bit2(row)
@@ -221,9 +180,9 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
             constexpr int t0 = decltype(T0_)::value, pc = decltype(PC_)::value;
             constexpr int s = pc >> 1, i = pc & 1;
             if constexpr (t0 + s < 25) {
-                constexpr int tap = w5_ky(t0 + s) * 5 + w5_kx(t0 + s);
+                constexpr int tap = k5s2_ky(t0 + s) * 5 + k5s2_kx(t0 + s);
                 const uint32_t so = (uint32_t)(tap * Ci2 + sub * 64);
-                wdma(srd_w, vw, so + i * rs64, lds_wave + WBUF0 + stg * W_BYTES + s * 8192 + i * 4096);
+                bdma16(srd_w, vw, so + i * rs64, lds_wave + WBUF0 + stg * W_BYTES + s * 8192 + i * 4096);
             }
         };
         // ---- outputs: the compute waves hand a finished tile over through LDS in two rounds (tile rows 0-7, 8-15; pixel
@@ -281,21 +240,21 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
         // behind the DMA of steps 0-11 (and may stay in flight over the next barrier, like the window slices)
         auto feed_sub = [&](int sub, bool more, int nsubi, bool switch_tile, int ng, int ny, int nx, bool outs)
                             __attribute__((always_inline)) {
-            static_for_w<0, 13>([&](auto T_) __attribute__((always_inline)) {
+            static_for<0, 13>([&](auto T_) __attribute__((always_inline)) {
                 constexpr int t = decltype(T_)::value;
                 constexpr int n_more = w5_allow(t, true, D, NSL), n_last = w5_allow(t, false, D, NSL);
                 constexpr int ns_prev = t > 0 ? w5_nst(t - 1) : 0;
                 static_assert(D == 1 || C5W_NSTG == 2, "the store allowance below assumes one step of weights in flight");
                 if (outs) {
-                    if (more) wait_vmw<n_more + ns_prev>(); else wait_vmw<n_last + ns_prev>();
+                    if (more) wait_vmcnt<n_more + ns_prev>(); else wait_vmcnt<n_last + ns_prev>();
                 } else {
-                    if (more) wait_vmw<n_more>(); else wait_vmw<n_last>();
+                    if (more) wait_vmcnt<n_more>(); else wait_vmcnt<n_last>();
                 }
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 int sd = stg + D;
                 if (sd >= NSTG) sd -= NSTG;
-                static_for_w<0, 4>([&](auto K_) __attribute__((always_inline)) {
+                static_for<0, 4>([&](auto K_) __attribute__((always_inline)) {
                     if constexpr (t + D < 13) {
                         load_w_piece(sd, std::integral_constant<int, 2 * (t + D)>{}, K_, sub);
                     } else {
@@ -303,32 +262,32 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
                     }
                 });
                 if constexpr (t <= 4) {
-                    static_for_w<0, w5_od_n(t, NSL)>([&](auto J_) __attribute__((always_inline)) {
+                    static_for<0, w5_od_n(t, NSL)>([&](auto J_) __attribute__((always_inline)) {
                         load_slice(std::integral_constant<int, 1>{}, sub, std::integral_constant<int, w5_od_0(t, NSL) + decltype(J_)::value>{});
                     });
                 } else if constexpr (t == 6) {
                     if (switch_tile) tile_offsets(ng, ny, nx);
                 } else if constexpr (w5_ev_n(t, NSL) > 0) {
                     if (more)
-                        static_for_w<0, w5_ev_n(t, NSL)>([&](auto J_) __attribute__((always_inline)) {
+                        static_for<0, w5_ev_n(t, NSL)>([&](auto J_) __attribute__((always_inline)) {
                             load_slice(std::integral_constant<int, 0>{}, nsubi, std::integral_constant<int, w5_ev_0(t, NSL) + decltype(J_)::value>{});
                         });
                 }
                 if constexpr (w5_nst(t) > 0) {
-                    if (outs) static_for_w<w5_st0(t), w5_st0(t) + w5_nst(t)>([&](auto I_) __attribute__((always_inline)) { put(I_); });
+                    if (outs) static_for<w5_st0(t), w5_st0(t) + w5_nst(t)>([&](auto I_) __attribute__((always_inline)) { put(I_); });
                 }
                 stg = stg + 1 == NSTG ? 0 : stg + 1;
                 __builtin_amdgcn_sched_barrier(0);
             });
         };
         // prologue: even-row window of the first tile's sub-chunk 0 and the weights of the first D steps, all landed
-        static_for_w<0, NSL>([&](auto E_) __attribute__((always_inline)) { load_slice(std::integral_constant<int, 0>{}, 0, E_); });
-        static_for_w<0, D>([&](auto S_) __attribute__((always_inline)) {
-            static_for_w<0, 4>([&](auto K_) __attribute__((always_inline)) {
+        static_for<0, NSL>([&](auto E_) __attribute__((always_inline)) { load_slice(std::integral_constant<int, 0>{}, 0, E_); });
+        static_for<0, D>([&](auto S_) __attribute__((always_inline)) {
+            static_for<0, 4>([&](auto K_) __attribute__((always_inline)) {
                 load_w_piece(decltype(S_)::value, std::integral_constant<int, 2 * decltype(S_)::value>{}, K_, 0);
             });
         });
-        wait_vmw<0>();
+        wait_vmcnt<0>();
         int tile = tile0, sub = 0;
         int cg = grp0, cy = ty0, cx = tx0;        // the tile being computed
         int ng = 0, ny = 0, nx = 0;
@@ -346,7 +305,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
                 if (tile + 1 < tile1) tile_geom(tile + 1, ng, ny, nx);
             }
         }
-        static_for_w<0, 16>([&](auto I_) __attribute__((always_inline)) { put(I_); });
+        static_for<0, 16>([&](auto I_) __attribute__((always_inline)) { put(I_); });
     } else {
         // =====================================================================================================
         // compute waves: LDS fragment reads and MFMAs only
@@ -367,7 +326,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
         // ---- B fragment address (row = wn*64 + tn*16 + frow)
         const uint32_t boff = (uint32_t)(WBUF0 + (wn * (BN / WN) + frow) * 64 + ((fq ^ (((frow >> 2) & 1) << 1)) << 4));
 
-        f4 acc[TN][TM];
+        f4 acc[TN][TM];       // (zeroed in place, not by zero_acc: changes instruction order)
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -375,22 +334,12 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
 
         // ---- the pending second tap slot of the previous K-step (all zeros: nothing pending)
         h8 paf[TM], pbf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) paf[i] = (h8)(half_t)0.f;
-#pragma unroll
-        for (int i = 0; i < TN; ++i) pbf[i] = (h8)(half_t)0.f;
-        auto pending_mfmas = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pbf[tn], paf[tm], acc[tn][tm], 0, 0, 0);
-        };
+        clear_frags(paf);
+        clear_frags(pbf);
+        auto pending_mfmas = [&]() __attribute__((always_inline)) { mfma_tiles(acc, pbf, paf); };
         auto clear_pending = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) paf[i] = (h8)(half_t)0.f;
-#pragma unroll
-            for (int i = 0; i < TN; ++i) pbf[i] = (h8)(half_t)0.f;
+            clear_frags(paf);
+            clear_frags(pbf);
         };
 
         // one K-step: taps T0, T0 + 1 (those < 25), weights in ring stage STG.  The first slot's 12 fragment reads go out
@@ -400,7 +349,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
             constexpr int NS = t0 + 1 < 25 ? 2 : 1;
             h8 af0[TM], bf0[TN];
             {
-                constexpr int ky = w5_ky(t0), kx = w5_kx(t0);
+                constexpr int ky = k5s2_ky(t0), kx = k5s2_kx(t0);
                 const char* Ps = smem + (ky & 1) * WINB + (ky >> 1) * (ROW * 64);
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm) af0[tm] = *(const h8*)(Ps + abase[kx] + tm * (ROW * 64));
@@ -410,18 +359,10 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
             // (t0 == 0: the previous step was the lone 25th tap or the start of the kernel -- nothing is pending, and 32 MFMAs
             // on zeros would only cover the first slot's read latency at twice its price)
             if constexpr (t0 != 0) pending_mfmas();
-            if constexpr (t0 != 0) {
-                // the reads one by one between the first MFMAs, not as a burst in front of them
-#pragma unroll
-                for (int i = 0; i < TM + TN; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - 2 * (TM + TN), 0);
-            }
+            if constexpr (t0 != 0) interleave_reads<TM, TN>();
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (NS == 2) {
-                constexpr int ky = w5_ky(t0 + 1), kx = w5_kx(t0 + 1);
+                constexpr int ky = k5s2_ky(t0 + 1), kx = k5s2_kx(t0 + 1);
                 const char* Ps = smem + (ky & 1) * WINB + (ky >> 1) * (ROW * 64);
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm) paf[tm] = *(const h8*)(Ps + abase[kx] + tm * (ROW * 64));
@@ -430,24 +371,13 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
             } else {
                 clear_pending();
             }
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf0[tn], af0[tm], acc[tn][tm], 0, 0, 0);
-            if constexpr (NS == 2) {
-#pragma unroll
-                for (int i = 0; i < TM + TN; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - 2 * (TM + TN), 0);
-            }
+            mfma_tiles(acc, bf0, af0);
+            if constexpr (NS == 2) interleave_reads<TM, TN>();
             __builtin_amdgcn_sched_barrier(0);
         };
         int stg = 0;                              // ring stage of the current step (wave-uniform)
         auto run_sub = [&]() __attribute__((always_inline)) {
-            static_for_w<0, 13>([&](auto T_) __attribute__((always_inline)) {
+            static_for<0, 13>([&](auto T_) __attribute__((always_inline)) {
                 constexpr int t = decltype(T_)::value;
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -519,10 +449,7 @@ __global__ __launch_bounds__(512, 1) void igemm_c5w_kernel(const C5Args a) {
             if (last_sub) {
                 epilogue();
                 clear_pending();
-#pragma unroll
-                for (int i = 0; i < TN; ++i)
-#pragma unroll
-                    for (int j = 0; j < TM; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
+                zero_acc(acc);
                 grp = ng; y0 = ny; x0 = nx;
                 sub = 0;
                 ++tile;

@@ -5,7 +5,8 @@
 // decoder.conv.0/1 (:46-53, :112-116) and the data gradient of every Conv2d(k5, s2, p2) with >= 128 output channels
 // (encoder.conv.1/2 :18-20, discriminator.conv.2/3 :149-153).
 //
-// igemm_win.hip ran one parity class per block (grid.z = class): every class streamed the input again from HBM
+// Its predecessor (igemm_win.hip, removed since) ran one parity class per block (grid.z = class): every class streamed
+// the input again from HBM
 // (4.3 x input re-read measured) and its K loop spent ~5.5 scalar / vector instructions per MFMA on tap bookkeeping,
 // swizzled window addresses recomputed per tap and 64-bit DMA addresses -- two waves per SIMD could not keep the
 // matrix pipe fed (60 % of what a bare MFMA loop sustains).  Here
@@ -22,47 +23,9 @@
 //   * BatchNorm batch statistics (sum x, sum x^2 per output channel over the valid pixels of all four classes) are
 //     accumulated in registers across the classes and leave the block as one row of a partial-sum buffer.
 #include "kernels.h"
-#include <type_traits>
+#include "pipe.h"
 
 namespace fmri {
-
-namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// 16-byte buffer -> LDS DMA: LDS destination = wave-uniform `lds` + lane*16, source = descriptor base + voff + soff.
-// Offsets >= num_records read as zero.  Issued from inline asm so that the compiler does not serialise later LDS reads
-// behind it (see glds16_raw in common.h); the caller owns the vmcnt / barrier protocol.
-__device__ __forceinline__ void bdma16(v4i srd, uint32_t voff, uint32_t soff, uint32_t lds) {
-    // under scalar-register pressure the compiler parks the descriptor in vector registers and would hand those to the
-    // "s" operand: name every word wave-uniform (free when it already sits in SGPRs)
-    srd.x = __builtin_amdgcn_readfirstlane(srd.x);
-    srd.y = __builtin_amdgcn_readfirstlane(srd.y);
-    srd.z = __builtin_amdgcn_readfirstlane(srd.z);
-    srd.w = __builtin_amdgcn_readfirstlane(srd.w);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(srd), "s"(soff), "s"(lds)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-}
-
-}  // namespace
 
 // NSL = 4 KB DMA slices per window chunk: 6 -> two window buffers (80 KB LDS with the 128-row weight ring),
 // 7 (two 10 x 10 image windows per tile) -> one buffer, reloaded between chunks; 4 -> dense 8 x 8 windows (see DENSE).
@@ -103,7 +66,8 @@ __global__ __launch_bounds__(256, 2) void igemm_tc5_kernel(const Tc5Args a) {
     const int y0 = tyi * a.PH, x0 = txi * PW;
     const int IHW = a.IH * a.IW;
 
-    // ---- descriptors
+    // ---- descriptors (pipe.h: bdma16)
+    // (not make_srd: changes instruction order)
     v4i srd_in, srd_w;
     srd_in.x = (int)(uint32_t)(uintptr_t)a.in;
     srd_in.y = (int)(uint32_t)((uintptr_t)a.in >> 32);
@@ -115,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void igemm_tc5_kernel(const Tc5Args a) {
     srd_w.w = 0x00020000;
 
     // ---- window DMA: slice e covers LDS bytes [e*4096, +4096) of a window buffer; 16-B unit q = e*256 + tid holds
-    // channels 8*cc .. 8*cc+7 of window pixel q >> 3, cc = (q & 7) ^ (pixel & 6)  (conflict-free for every tap shift,
-    // see igemm_win.hip).  Window origin = tile origin - 1 (the union window of the four classes).
+    // channels 8*cc .. 8*cc+7 of window pixel q >> 3, cc = (q & 7) ^ (pixel & 6)  (conflict-free for every tap
+    // shift).  Window origin = tile origin - 1 (the union window of the four classes).
     uint32_t soff[NSL];
     {
         const FastDiv fIHW = a.fdIHW, fIW = a.fdIW;
@@ -169,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void igemm_tc5_kernel(const Tc5Args a) {
     const int wm = wave >> 1, wn = wave & 1;
     const int frow = lane & 15, fq = lane >> 4;
     const int tp_log2 = a.pw_log2 + a.ph_log2;
-    // GEMM row rr of an image's tile -> tile column (8-wide tiles: rows rotated by -y*IW, see igemm_win.hip)
+    // GEMM row rr of an image's tile -> tile column (8-wide tiles: rows rotated by -y*IW)
     const int rotIW = (a.pw_log2 == 3 && !DENSE) ? a.IW : 0;     // dense 8-pixel rows are conflict-free as they are
     auto tile_x = [&](int rr) __attribute__((always_inline)) { return (rr - (rr >> 3) * rotIW) & (PW - 1); };
 
@@ -251,8 +215,8 @@ __global__ __launch_bounds__(256, 2) void igemm_tc5_kernel(const Tc5Args a) {
     };
 
     // ---- epilogue of one class: D[i = co][j = class-grid position] -> output pixel (2y + cy, 2x + cx).  No bias /
-    // activation here: every layer of this geometry is followed by BatchNorm or is a data gradient (the launcher routes
-    // anything else to igemm_win.hip).
+    // activation here: every layer of this geometry is followed by BatchNorm or is a data gradient (the launcher declines
+    // anything else).
     const int sgrp = (STATS != 0 && a.st.group_n > 0) ? (grp * a.IPB) / a.st.group_n : 0;     // statistics group of the tile
     auto epilogue = [&](int cls) __attribute__((always_inline)) {
         const int cy = cls >> 1, cx = cls & 1;
@@ -354,9 +318,10 @@ __global__ __launch_bounds__(256, 2) void igemm_tc5_kernel(const Tc5Args a) {
                                                   : ((prev_lo >= NSL) ? 0 : ((prev_lo + SPT > NSL ? NSL : prev_lo + SPT) - prev_lo));
                     // weights of this step landed; at the first tap of a chunk the whole window must have landed too
                     // (in the last (class, chunk) no window follows: nothing was issued behind the weight tile)
-                    if constexpr (t == 0 || PBUFS == 1 || prev_n == 0) wait_vm<0>();
-                    else if constexpr (LAST) { if (more_win) wait_vm<prev_n>(); else wait_vm<0>(); }
-                    else wait_vm<prev_n>();
+                    static_assert(prev_n <= 2, "at most SPT = 2 slices behind a weight tile");
+                    if constexpr (t == 0 || PBUFS == 1 || prev_n == 0) wait_vmcnt<0>();
+                    else if constexpr (LAST) { if (more_win) wait_vmcnt<prev_n>(); else wait_vmcnt<0>(); }
+                    else wait_vmcnt<prev_n>();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);

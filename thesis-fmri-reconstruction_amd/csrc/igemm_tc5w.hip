@@ -21,45 +21,16 @@
 // the same (16 + 2)^2 window of 64-channel chunks (double-buffered), weights straight out of the per-class packed
 // matrices, BatchNorm forward statistics of the stored values summed over the four classes (StatEpi).
 #include "kernels.h"
-#include <type_traits>
+#include "pipe.h"
 
 namespace fmri {
 
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 // output stores of the previous class issued behind the DMA of step J of a class with T taps (first chunk pair: 2T steps, 16 items)
 constexpr int t5_nst(int j, int T) { return 16 / (2 * T) + (j < 16 % (2 * T) ? 1 : 0); }
 constexpr int t5_st0(int j, int T) { return j * (16 / (2 * T)) + (j < 16 % (2 * T) ? j : 16 % (2 * T)); }
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_t(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_t<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ void tdma(v4i srd, uint32_t voff, uint32_t soff, uint32_t lds) {
-    srd.x = __builtin_amdgcn_readfirstlane(srd.x);
-    srd.y = __builtin_amdgcn_readfirstlane(srd.y);
-    srd.z = __builtin_amdgcn_readfirstlane(srd.z);
-    srd.w = __builtin_amdgcn_readfirstlane(srd.w);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 ::"v"(voff), "s"(srd), "s"(soff), "s"(lds)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 }  // namespace
 
@@ -119,6 +90,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
         const int tid = threadIdx.x & 255;
         const int lw = wave - 4;
         const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
+        // (not make_srd: changes instruction order)
         v4i srd_in, srd_w;
         srd_in.x = (int)(uint32_t)(uintptr_t)a.in;
         srd_in.y = (int)(uint32_t)((uintptr_t)a.in >> 32);
@@ -151,9 +123,9 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
         auto load_slices = [&](auto BUF_, int chunk, auto LO_, auto HI_) __attribute__((always_inline)) {
             constexpr int buf = decltype(BUF_)::value, lo = decltype(LO_)::value, hi = decltype(HI_)::value;
             const uint32_t so = (uint32_t)chunk * 128u;
-            static_for_t<lo, (hi < NSL ? hi : NSL)>([&](auto E_) __attribute__((always_inline)) {
+            static_for<lo, (hi < NSL ? hi : NSL)>([&](auto E_) __attribute__((always_inline)) {
                 constexpr int e = decltype(E_)::value;
-                tdma(srd_in, soff[e], so, lds_wave + buf * WINB + e * 4096);
+                bdma16(srd_in, soff[e], so, lds_wave + buf * WINB + e * 4096);
             });
         };
         // ---- weight tile DMA (rows = co, 64 k-values per step), XOR swizzled like igemm.hip.  Per class: per-lane offset
@@ -170,7 +142,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
             constexpr int stg = decltype(STG_)::value;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                tdma(srd_w, vw, so + i * rs, lds_wave + WBUF0 + stg * W_BYTES + i * 4096);
+                bdma16(srd_w, vw, so + i * rs, lds_wave + WBUF0 + stg * W_BYTES + i * 4096);
             }
         };
         const int Ci2 = a.Ci * 2;
@@ -238,12 +210,12 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
             uint32_t vwn = 0, swn = 0, rsn = 0;
             if constexpr (!LAST) class_w(cls + 1, vwn, swn, rsn);
             for (int chunk = 0; chunk < nch; chunk += 2) {
-                static_for_t<0, 2>([&](auto PB_) __attribute__((always_inline)) {
+                static_for<0, 2>([&](auto PB_) __attribute__((always_inline)) {
                     constexpr int pb = decltype(PB_)::value;
                     const int ch = chunk + pb;
                     const bool last_chunk = ch + 1 >= nch;
                     const bool more_win = !(LAST && last_chunk);       // another (class, chunk) window follows
-                    static_for_t<0, T>([&](auto TAP_) __attribute__((always_inline)) {
+                    static_for<0, T>([&](auto TAP_) __attribute__((always_inline)) {
                         constexpr int t = decltype(TAP_)::value;
                         constexpr int stg = (pb * T + t) & 1;
                         // slices issued behind the weight tile of the PREVIOUS step (window of the next chunk)
@@ -254,11 +226,11 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
                         // In flight may stay: the slices and the output stores issued behind the previous step's weights
                         constexpr int j = pb * T + t;
                         constexpr int ns_prev = (cls > 0 && t > 0) ? t5_nst(j - 1, T) : 0;
-                        if constexpr (t == 0) wait_vmt<0>();
+                        if constexpr (t == 0) wait_vmcnt<0>();
                         else {
                             const bool win_prev = !LAST || more_win;
-                            if (chunk == 0 && !solo) { if (win_prev) wait_vmt<prev_n + ns_prev>(); else wait_vmt<ns_prev>(); }
-                            else { if (win_prev) wait_vmt<prev_n>(); else wait_vmt<0>(); }
+                            if (chunk == 0 && !solo) { if (win_prev) wait_vmcnt<prev_n + ns_prev>(); else wait_vmcnt<ns_prev>(); }
+                            else { if (win_prev) wait_vmcnt<prev_n>(); else wait_vmcnt<0>(); }
                         }
                         __builtin_amdgcn_s_barrier();
                         __builtin_amdgcn_sched_barrier(0);
@@ -276,7 +248,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
                         // outputs of the previous class
                         if constexpr (cls > 0) {
                             if (chunk == 0 && !solo)
-                                static_for_t<t5_st0(j, T), t5_st0(j, T) + t5_nst(j, T)>([&](auto I_) __attribute__((always_inline)) { put(I_); });
+                                static_for<t5_st0(j, T), t5_st0(j, T) + t5_nst(j, T)>([&](auto I_) __attribute__((always_inline)) { put(I_); });
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     });
@@ -300,7 +272,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
             feed_class(std::integral_constant<int, 2>{});
             feed_class(std::integral_constant<int, 3>{});
         }
-        static_for_t<0, 16>([&](auto I_) __attribute__((always_inline)) { put(I_); });
+        static_for<0, 16>([&](auto I_) __attribute__((always_inline)) { put(I_); });
     } else {
         // =====================================================================================================
         // compute waves: LDS fragment reads and MFMAs only
@@ -320,39 +292,17 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
         const uint32_t boff = (uint32_t)(WBUF0 + (wn * (BN / WN) + frow) * 128 + ((fq ^ ((frow >> 1) & 7)) << 4));
 
         f4 acc[TN][TM];
-        auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TM; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
-        };
-        zero_acc();
+        auto zero = [&]() __attribute__((always_inline)) { zero_acc(acc); };
+        zero();
 
         // ---- the pending second half of the previous K-step (all zeros: nothing pending)
         h8 paf[TM], pbf[TN];
         auto clear_pending = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) paf[i] = (h8)(half_t)0.f;
-#pragma unroll
-            for (int i = 0; i < TN; ++i) pbf[i] = (h8)(half_t)0.f;
+            clear_frags(paf);
+            clear_frags(pbf);
         };
         clear_pending();
-        auto pending_mfmas = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pbf[tn], paf[tm], acc[tn][tm], 0, 0, 0);
-        };
-        auto interleave = [&]() __attribute__((always_inline)) {
-            // the 12 fragment reads one by one between the first MFMAs
-#pragma unroll
-            for (int i = 0; i < TM + TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - 2 * (TM + TN), 0);
-        };
+        auto pending_mfmas = [&]() __attribute__((always_inline)) { mfma_tiles(acc, pbf, paf); };
 
         // one K-step: window shift (SY, SX), window buffer PB, ring stage STG
         auto step = [&](auto SY_, auto SX_, auto PB_, auto STG_) __attribute__((always_inline)) {
@@ -365,7 +315,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) bf0[tn] = *(const h8*)(Ws + (boff + tn * 2048));
             pending_mfmas();
-            interleave();
+            interleave_reads<TM, TN>();
             __builtin_amdgcn_sched_barrier(0);
             {
                 // the second half: one XOR each (volatile: the compiler would otherwise keep both address sets live)
@@ -377,12 +327,8 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn) pbf[tn] = *(const h8*)(Ws + (bxo + tn * 2048));
             }
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf0[tn], af0[tm], acc[tn][tm], 0, 0, 0);
-            interleave();
+            mfma_tiles(acc, bf0, af0);
+            interleave_reads<TM, TN>();
             __builtin_amdgcn_sched_barrier(0);
         };
 
@@ -448,9 +394,9 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
             constexpr int cls = decltype(CLS_)::value;
             constexpr int TH = (cls >> 1) ? 2 : 3, TW = (cls & 1) ? 2 : 3, T = TH * TW;
             for (int chunk = 0; chunk < nch; chunk += 2) {
-                static_for_t<0, 2>([&](auto PB_) __attribute__((always_inline)) {
+                static_for<0, 2>([&](auto PB_) __attribute__((always_inline)) {
                     constexpr int pb = decltype(PB_)::value;
-                    static_for_t<0, T>([&](auto TAP_) __attribute__((always_inline)) {
+                    static_for<0, T>([&](auto TAP_) __attribute__((always_inline)) {
                         constexpr int t = decltype(TAP_)::value;
                         constexpr int ty = t / TW, tx = t % TW;
                         constexpr int stg = (pb * T + t) & 1;
@@ -465,7 +411,7 @@ __global__ __launch_bounds__(512, 1) void igemm_tc5w_kernel(const Tc5Args a) {
             pending_mfmas();                                     // the last step's second half
             hand_over(cls);
             clear_pending();
-            zero_acc();
+            zero();
         };
         if constexpr (solo) {
             if (cls0 == 0) run_class(std::integral_constant<int, 0>{});

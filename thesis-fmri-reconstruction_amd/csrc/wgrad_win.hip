@@ -12,34 +12,10 @@
 // 32 KB per 2.1 MFLOP.  The MFMA K index is the pixel, so both operands are read with transposing LDS reads
 // (ds_read_b64_tr_b16); the window fragments of a shift are the same reads at a compile-time byte offset.
 #include "kernels.h"
-#include <type_traits>
-
+#include "pipe.h"
 
 namespace fmri {
 
-
-namespace {
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_g(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_g<I + 1, N>(f);
-    }
-}
-
-// 16-byte buffer -> LDS DMA (see igemm_tc5.hip::bdma16): offsets >= num_records read as zero
-__device__ __forceinline__ void wdma16(v4i srd, uint32_t voff, uint32_t lds) {
-    srd.x = __builtin_amdgcn_readfirstlane(srd.x);
-    srd.y = __builtin_amdgcn_readfirstlane(srd.y);
-    srd.z = __builtin_amdgcn_readfirstlane(srd.z);
-    srd.w = __builtin_amdgcn_readfirstlane(srd.w);
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(srd), "s"(lds)
-                 : "memory");
-}
-}  // namespace
 
 // P tile: 64 m-rows x 256 B, swizzled exactly like wgrad.hip.  Window: WH x WW pixels x 64 B, linear.
 template <int NSY, int NSX, bool SLABS>
@@ -91,15 +67,8 @@ __device__ __forceinline__ void wgrad_win_body(const WgradWinArgs& a, char* smem
         wi[e] = pix - wj[e] * WW;
         lane_q[e] = (uint32_t)(((2 * wj[e] * a.Wq + 2 * wi[e]) * a.Bc + b0 + (tid & 3) * 8) * 2);
     }
-    v4i srdP, srdQ;
-    srdP.x = (int)(uint32_t)(uintptr_t)a.P;
-    srdP.y = (int)(uint32_t)((uintptr_t)a.P >> 32);
-    srdP.z = (int)((uint32_t)a.N * (uint32_t)a.Yc * (uint32_t)a.Xc * (uint32_t)a.A * 2u);
-    srdP.w = 0x00020000;
-    srdQ.x = (int)(uint32_t)(uintptr_t)a.Q;
-    srdQ.y = (int)(uint32_t)((uintptr_t)a.Q >> 32);
-    srdQ.z = (int)((uint32_t)a.N * (uint32_t)a.Hq * (uint32_t)a.Wq * (uint32_t)a.Bc * 2u);
-    srdQ.w = 0x00020000;
+    const v4i srdP = make_srd(a.P, (uint32_t)a.N * (uint32_t)a.Yc * (uint32_t)a.Xc * (uint32_t)a.A * 2u);
+    const v4i srdQ = make_srd(a.Q, (uint32_t)a.N * (uint32_t)a.Hq * (uint32_t)a.Wq * (uint32_t)a.Bc * 2u);
 
     // the K range (8x8 pixel tiles) is cut into equal pieces, the same for every plane (see api.hip)
     const int tps = a.plane_tps[py * 2 + px];
@@ -132,7 +101,7 @@ __device__ __forceinline__ void wgrad_win_body(const WgradWinArgs& a, char* smem
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool ok = pcol_ok && y0 + prow + 2 * i < kYc;
-            wdma16(srdP, ok ? tile_p + lane_p + i * prow_step : 0x80000000u, dstP + i * (16 * 256));
+            bdma16(srdP, ok ? tile_p + lane_p + i * prow_step : 0x80000000u, dstP + i * (16 * 256));
         }
         // window origin in Q (may lie outside the image: the per-lane checks below) and its byte offset (signed)
         const int by = 2 * (y0 + tminy) + py, bx = 2 * (x0 + tminx) + px;
@@ -143,7 +112,7 @@ __device__ __forceinline__ void wgrad_win_body(const WgradWinArgs& a, char* smem
             if (e * 4096 + wave * 1024 < W_BYTES) {      // wave-uniform
                 const int iy = by + 2 * wj[e], ix = bx + 2 * wi[e];
                 const bool ok = won[e] && (unsigned)iy < (unsigned)kHq && (unsigned)ix < (unsigned)kWq;
-                wdma16(srdQ, ok ? (uint32_t)(tile_q + (int)lane_q[e]) : 0x80000000u, dstW + e * 4096);
+                bdma16(srdQ, ok ? (uint32_t)(tile_q + (int)lane_q[e]) : 0x80000000u, dstW + e * 4096);
             }
         }
     };
@@ -194,7 +163,7 @@ __device__ __forceinline__ void wgrad_win_body(const WgradWinArgs& a, char* smem
         wf[0] = read_w(0);
         wf[1] = read_w(1);
         __builtin_amdgcn_sched_barrier(0);
-        static_for_g<0, NI>([&](auto I_) __attribute__((always_inline)) {
+        static_for<0, NI>([&](auto I_) __attribute__((always_inline)) {
             constexpr int i = decltype(I_)::value;
             constexpr int ks = i / NS, sh = i % NS;
             constexpr bool rd_w = i + 2 < NI, rd_a = i >= NS - TA && i < NS;
