@@ -409,6 +409,34 @@ int fmri_compose_gate_dev(float* scal, int* flags, float batch, float nfeat, flo
                           int gate_on, int force_dis, int force_dec, void* stream);
 /* *counter_dev += 1 (the step count fmri_adam_dev derives its bias corrections from) */
 int fmri_counter_inc(int* counter_dev, void* stream);
+/* ---- counter-based random numbers (csrc/rng.hip; fmri_hip/rng.py) ---------------------------------------------------
+ * What the reference draws on the host each batch -- `normal_()` in `reparameterize` (models/vae_gan.py), `randn` for z_p,
+ * `0.5 * randn` for z_fake (train/train_wae_stage1.py:276) -- and the flip / shift draws of fmri_ingest_u8, made on the
+ * device by Philox4x32-10 (Random123: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten
+ * rounds).  state: device int64[2] = [seed, offset], 8-byte aligned; key = (low, high 32 bits of seed); offset = Philox
+ * blocks consumed so far, read on the DEVICE (a replayed HIP graph draws fresh numbers) and moved by fmri_rng_advance only.
+ * Element e of a draw on stream id sid >= 0 is output word e % 4 of the block with counter
+ *     (lo32(offset + e / 4), hi32(offset + e / 4), sid, 0).
+ * Draws that share an offset must use different sids.  Enqueue-only, no allocation, no global state.
+ *
+ * fmri_rng_normal: out[r * ld + c] (fp32, r < rows, c < cols <= ld; columns >= cols are not touched) = scale * N(0, 1)
+ *   for e = (row0 + r) * cols + c, row0 >= 0 the caller's first GLOBAL row: rank k of a data-parallel run passes
+ *   row0 = k * rows and gets the rows the one-rank run at the global batch would have got.  Uniforms
+ *   u = ((w >> 8) + 0.5) * 2^-24 in (0, 1); Box-Muller on (w0, w1) -> words 0, 1 and (w2, w3) -> words 2, 3:
+ *   scale * sqrt(-2 ln u_a) * {cos, sin}(2 pi u_b), precise logf / log1pf / sincosf / sqrtf (the upper half of (0, 1) is
+ *   evaluated through 1 - u, which fp32 holds exactly where it does not hold u).  |value| <= scale * sqrt(-2 ln 2^-25)
+ *   ~ 5.89 * scale; max abs error against the real-valued map <= 1e-5 * scale.  rows * cols >= 2^31 or row0 > 2^40:
+ *   FMRI_E_UNSUPPORTED.
+ * fmri_rng_u32: out[i] (int32, i < n) = lo + (((uint64) w_i * (hi - lo + 1)) >> 32) in [lo, hi], w_i = word i % 4 of
+ *   block i / 4 (lo = 0, hi = 1: flips; lo = -s, hi = s: shifts; lo = INT32_MIN, hi = INT32_MAX: the raw words).  A value's
+ *   probability differs from 1 / (hi - lo + 1) by less than 2^-32, i.e. the relative bias is at most (hi - lo + 1) * 2^-32.
+ *   n > 2^40: FMRI_E_UNSUPPORTED.
+ * fmri_rng_advance: offset += nblocks (>= 0), one thread, a launch of its own behind the draws that share the offset
+ *   (stream order keeps it behind their reads).  A draw of n elements from row0 = 0 consumes ceil(n / 4) blocks. */
+int fmri_rng_normal(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
+                    void* stream);
+int fmri_rng_u32(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, void* stream);
+int fmri_rng_advance(int64_t* state, int64_t nblocks, void* stream);
 /* starting cotangents of the two back-propagated streams, fp16, multiplied by gscale * (*norm) (norm: device float) */
 int fmri_gan_head_bwd(const float* logit, int ldl, int B, void* dlogit, int ldg, float gscale, const float* norm,
                       void* stream);

@@ -1124,6 +1124,22 @@ int fmri_counter_inc(int* counter_dev, void* stream) {
     if (!counter_dev) return FMRI_E_BADARG;
     return counter_inc_launch(counter_dev, S(stream));
 }
+int fmri_rng_normal(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
+                    void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !out || ((uintptr_t)out & 3) || rows < 1 || cols < 1 || ld < cols ||
+        row0 < 0 || sid < 0)
+        return FMRI_E_BADARG;
+    return rng_normal_launch(state, out, rows, cols, ld, row0, sid, scale, S(stream));
+}
+int fmri_rng_u32(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !out || ((uintptr_t)out & 3) || n < 1 || sid < 0 || hi < lo)
+        return FMRI_E_BADARG;
+    return rng_u32_launch(state, out, n, sid, lo, hi, S(stream));
+}
+int fmri_rng_advance(int64_t* state, int64_t nblocks, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || nblocks < 0) return FMRI_E_BADARG;
+    return rng_advance_launch(state, nblocks, S(stream));
+}
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream) {
     if (!x || !out || (n & 7)) return FMRI_E_BADARG;

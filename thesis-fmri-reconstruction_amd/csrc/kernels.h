@@ -266,6 +266,10 @@ int compose_gate_launch(float* scal, int* flags, float batch, float nfeat, float
                         float equilibrium, float margin, float beta, const float* hp_dev, int mode, int gate_on,
                         int force_dis, int force_dec, hipStream_t st);
 int counter_inc_launch(int* t, hipStream_t st);
+int rng_normal_launch(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
+                      hipStream_t st);
+int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, hipStream_t st);
+int rng_advance_launch(int64_t* state, int64_t nblocks, hipStream_t st);
 int axpby_f16_launch(const half_t* x, const half_t* y, half_t* out, int64_t n, float a, float b, const float* pa,
                      const float* pb, hipStream_t st);
 int sumsq_launch(const float* x, int64_t n, float* acc, hipStream_t st);

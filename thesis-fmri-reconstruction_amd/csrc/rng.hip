@@ -1,0 +1,163 @@
+// Counter-based random numbers for the fused steps: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as
+// 1, 2, 3", SC 2011; the Random123 constants), the latent noise (eps, z_p, z_fake) and the augmentation draws of
+// fmri_ingest_u8 made on the device (include/fmri_hip.h fmri_rng_normal for the counter layout).
+//
+//   rng_normal_kernel   thread t owns Philox block b0 + t of the draw: one Philox call, two Box-Muller pairs, and the up
+//                       to four elements of the block that fall inside the caller's rows -- one 16-byte store when all
+//                       four lie in one row at an aligned address, single stores otherwise (first / last block of a draw
+//                       whose row0 * cols is no multiple of 4, rows with cols % 4 != 0, ld % 4 != 0).
+//   rng_u32_kernel      thread t owns block t: four words mapped to [lo, hi] by multiply-high.
+//   rng_advance_kernel  offset += nblocks, one thread, a plain store.
+//
+// The state [seed, offset] is read from device memory by every thread (two scalar loads): the host never knows the
+// offset, so a step recorded into a HIP graph draws fresh numbers at every replay.  A number depends on (seed, offset,
+// global row, column, stream id) only -- not on the launch shape, the rank or the vector / scalar store path.
+#include "kernels.h"
+
+namespace fmri {
+
+namespace {
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+struct u32x4 {
+    uint32_t w[4];
+};
+
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                               uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += PHILOX_W0;
+        k1 += PHILOX_W1;
+    }
+    return u32x4{{c0, c1, c2, c3}};
+}
+
+// Philox block `blk` of stream `sid` at the state's seed and offset
+__device__ __forceinline__ u32x4 rng_block(const int64_t* __restrict__ state, uint64_t blk, uint32_t sid) {
+    const uint64_t seed = (uint64_t)state[0];
+    const uint64_t ctr = (uint64_t)state[1] + blk;
+    return philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), sid, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// u = (k + 0.5) * 2^-24 with k = w >> 8 is no fp32 number for k >= 2^23 (25 significant bits), and near u = 1 the half
+// step it would be rounded by moves sqrt(-2 ln u) by far more than an ulp.  1 - u = ((2^24 - 1 - k) + 0.5) * 2^-24 IS one
+// there, so the upper half of the interval goes through its complement: ln u = log1p(-(1 - u)), and the angle 2 pi u is
+// taken as -2 pi (1 - u) (cos is even, sin odd).  Both halves evaluate the same real-valued map.
+__device__ __forceinline__ float neg2_log_u(uint32_t w) {
+    const uint32_t k = w >> 8;
+    if (k < (1u << 23)) return -2.f * logf(((float)k + 0.5f) * 0x1p-24f);
+    return -2.f * log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f));
+}
+
+__device__ __forceinline__ void sincos_2pi_u(uint32_t w, float& s, float& c) {
+    const uint32_t k = w >> 8;
+    const float two_pi = 6.28318530717958647692f;
+    if (k < (1u << 23)) {
+        sincosf(two_pi * (((float)k + 0.5f) * 0x1p-24f), &s, &c);
+    } else {
+        sincosf(two_pi * (((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f), &s, &c);
+        s = -s;
+    }
+}
+
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float scale, float& z0, float& z1) {
+    const float r = scale * sqrtf(neg2_log_u(wa));
+    float s, c;
+    sincos_2pi_u(wb, s, c);
+    z0 = r * c;
+    z1 = r * s;
+}
+
+// e0 = row0 * cols: first global element of the caller's rows; n = rows * cols (< 2^31); b0 = e0 / 4
+__global__ __launch_bounds__(256) void rng_normal_kernel(const int64_t* __restrict__ state, float* __restrict__ out,
+                                                         uint64_t e0, uint32_t n, uint64_t b0, uint32_t nblk,
+                                                         uint32_t cols, uint32_t ld, uint32_t sid, float scale,
+                                                         int vec_ok) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= nblk) return;
+    const uint64_t blk = b0 + t;
+    const u32x4 x = rng_block(state, blk, sid);
+    float z[4];
+    box_muller(x.w[0], x.w[1], scale, z[0], z[1]);
+    box_muller(x.w[2], x.w[3], scale, z[2], z[3]);
+    // local index of the block's first element; "negative" (wraps) only for the first block when e0 % 4 != 0
+    const int64_t l0 = (int64_t)(4 * blk - e0);
+    if (l0 >= 0 && l0 + 3 < (int64_t)n) {
+        const uint32_t l = (uint32_t)l0, r = l / cols, c = l - r * cols;
+        const uint64_t at = (uint64_t)r * ld + c;
+        if (vec_ok && c + 3 < cols && (at & 3) == 0) {
+            *(float4*)(out + at) = make_float4(z[0], z[1], z[2], z[3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t lk = l0 + k;
+        if (lk < 0 || lk >= (int64_t)n) continue;
+        const uint32_t l = (uint32_t)lk, r = l / cols, c = l - r * cols;
+        out[(uint64_t)r * ld + c] = z[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void rng_u32_kernel(const int64_t* __restrict__ state, int32_t* __restrict__ out,
+                                                      uint64_t n, uint32_t sid, int64_t lo, uint64_t span, int vec_ok) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (4 * t >= n) return;
+    const u32x4 x = rng_block(state, t, sid);
+    int32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = (int32_t)(lo + (int64_t)(((uint64_t)x.w[k] * span) >> 32));
+    if (vec_ok && 4 * t + 3 < n) {
+        *(int4*)(out + 4 * t) = make_int4(v[0], v[1], v[2], v[3]);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * t + k < n) out[4 * t + k] = v[k];
+}
+
+__global__ void rng_advance_kernel(int64_t* state, int64_t nblocks) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) state[1] = (int64_t)((uint64_t)state[1] + (uint64_t)nblocks);
+}
+
+#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? OK : E_LAUNCH)
+
+}  // namespace
+
+int rng_normal_launch(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
+                      hipStream_t st) {
+    const int64_t n = (int64_t)rows * cols;
+    // one thread per Philox block with 32-bit local indices; global rows up to 2^40 keep (row0 + rows) * cols in 64 bits
+    if (n > INT32_MAX || row0 > (1ll << 40)) return E_UNSUPPORTED;
+    const uint64_t e0 = (uint64_t)row0 * (uint64_t)cols, e1 = e0 + (uint64_t)n;
+    const uint64_t b0 = e0 / 4, b1 = (e1 - 1) / 4;
+    const uint32_t nblk = (uint32_t)(b1 - b0 + 1);
+    hipLaunchKernelGGL(rng_normal_kernel, dim3((nblk + 255) / 256), dim3(256), 0, st, state, out, e0, (uint32_t)n, b0,
+                       nblk, (uint32_t)cols, (uint32_t)ld, (uint32_t)sid, scale, ((uintptr_t)out & 15) == 0 ? 1 : 0);
+    return LAUNCH_OK();
+}
+
+int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, hipStream_t st) {
+    if (n > (1ll << 40)) return E_UNSUPPORTED;           // 2^31 - 1 thread blocks of 1024 numbers at most
+    const uint64_t nblk = ((uint64_t)n + 3) / 4;
+    hipLaunchKernelGGL(rng_u32_kernel, dim3((uint32_t)((nblk + 255) / 256)), dim3(256), 0, st, state, out, (uint64_t)n,
+                       (uint32_t)sid, (int64_t)lo, (uint64_t)((int64_t)hi - (int64_t)lo + 1),
+                       ((uintptr_t)out & 15) == 0 ? 1 : 0);
+    return LAUNCH_OK();
+}
+
+int rng_advance_launch(int64_t* state, int64_t nblocks, hipStream_t st) {
+    hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, st, state, nblocks);
+    return LAUNCH_OK();
+}
+
+}  // namespace fmri

@@ -94,6 +94,9 @@ _SIGS = {
     "fmri_axpby2_f16": [_p, _p, _p, _l, _f, _f, _p, _p, _p],
     "fmri_compose_gate_dev": [_p, _p, _f, _f, _f, _p, _i, _i, _i, _i, _p],
     "fmri_counter_inc": [_p, _p],
+    "fmri_rng_normal": [_p, _p, _i, _i, _i, _l, _i, _f, _p],
+    "fmri_rng_u32": [_p, _p, _l, _i, _i, _i, _p],
+    "fmri_rng_advance": [_p, _l, _p],
     "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
     "fmri_sumsq": [_p, _l, _p, _p],

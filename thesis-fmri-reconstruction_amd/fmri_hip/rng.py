@@ -1,0 +1,125 @@
+"""Device-side random numbers for the fused steps (csrc/rng.hip; include/fmri_hip.h fmri_rng_normal).
+
+A counter-based generator (Philox4x32-10) whose state -- ``[seed, offset]``, int64 -- lives in device memory: the same
+(seed, offset, global row, column, stream id) gives the same number on any launch shape, on any rank and in any replay of
+a recorded step.  Draws never move the offset; ``advance`` does, as a launch of its own behind the draws that share it.
+Draws made at one offset must use different stream ids (the ``SID_*`` constants below are the ones the steps use).
+
+Nothing here synchronises with the host except ``offset()`` / ``state()``.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import lib
+
+_P = lib.ptr
+
+# stream ids: third counter word of the Philox block
+SID_EPS = 0            # reparameterisation noise of the trained encoder
+SID_ZP = 1             # prior sample z_p
+SID_EPS_TEACHER = 2    # reparameterisation noise of the Stage-II teacher
+SID_ZFAKE = 3          # WAE prior sample (before the factor 0.5)
+SID_FLIP = 8           # per-image horizontal flip
+SID_SHIFT = 9          # per-image (rows, cols) shift
+
+_I64 = (1 << 64) - 1
+
+
+def _wrap64(v: int) -> int:
+    """Python int -> the int64 with the same low 64 bits."""
+    v &= _I64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def blocks(n: int) -> int:
+    """Philox blocks a draw of ``n`` elements from global row 0 consumes."""
+    return (int(n) + 3) // 4
+
+
+class DeviceRng:
+    def __init__(self, seed: int, device):
+        self.device = torch.device(device)
+        self._state = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.seed(seed)
+
+    # ---- state -------------------------------------------------------------------------------------------------------
+    def seed(self, seed: int, offset: int = 0):
+        self._state.copy_(torch.tensor([_wrap64(seed), _wrap64(offset)], dtype=torch.int64))
+
+    def state(self) -> Tuple[int, int]:
+        """(seed, offset) as unsigned Python ints -- syncs."""
+        s, o = self._state.tolist()
+        return s & _I64, o & _I64
+
+    def set_state(self, state):
+        self.seed(int(state[0]), int(state[1]))
+
+    def offset(self) -> int:
+        """Philox blocks consumed so far -- the only call of the draw interface that syncs."""
+        return self._state[1].item() & _I64
+
+    def advance(self, nblocks: int):
+        lib.call("fmri_rng_advance", _P(self._state), int(nblocks))
+
+    # ---- draws -------------------------------------------------------------------------------------------------------
+    def normal(self, rows: int, cols: int, sid: int, row0: int = 0, scale: float = 1.0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 [rows, cols] of scale * N(0, 1): global rows row0 .. row0 + rows of stream ``sid`` at the current offset.
+        ``out``: a 2-D fp32 device tensor with unit column stride whose row stride may exceed ``cols`` (the columns
+        behind ``cols`` are left as they are)."""
+        if out is None:
+            out = torch.empty(rows, cols, dtype=torch.float32, device=self.device)
+        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < cols
+                or out.stride(1) != 1 or out.device != self._state.device):
+            raise ValueError("DeviceRng.normal: out must be fp32 [rows, >= cols] with unit column stride on the "
+                             "generator's device")
+        ld = out.stride(0) if rows > 1 else max(out.stride(0), cols)
+        lib.call("fmri_rng_normal", _P(self._state), _P(out), rows, cols, ld, int(row0), sid, float(scale))
+        return out
+
+    def integers(self, n: int, lo: int, hi: int, sid: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n] in [lo, hi] (both inclusive) of stream ``sid`` at the current offset."""
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.device)
+        if (out.dtype != torch.int32 or out.numel() != n or not out.is_contiguous()
+                or out.device != self._state.device):
+            raise ValueError("DeviceRng.integers: out must be a contiguous int32 tensor of n elements on the "
+                             "generator's device")
+        lib.call("fmri_rng_u32", _P(self._state), _P(out), n, sid, int(lo), int(hi))
+        return out
+
+    def flips(self, n: int) -> torch.Tensor:
+        """int32 [n] of 0 / 1: the ``flip`` argument of ``ops.ingest_u8``."""
+        return self.integers(n, 0, 1, SID_FLIP)
+
+    def shifts(self, n: int, max_shift: int) -> torch.Tensor:
+        """int32 [n, 2] (rows, cols) in [-max_shift, max_shift]: the ``shift`` argument of ``ops.ingest_u8``."""
+        return self.integers(2 * n, -int(max_shift), int(max_shift), SID_SHIFT).view(n, 2)
+
+
+class StepNoise:
+    """The noise buffers a fused step fills for itself: persistent fp32 [B, Z] tensors (so that a recorded step writes
+    and reads the same memory at every replay), drawn at global rows rank * B .. and followed by ONE advance per step
+    by the block count of the largest draw at the global batch."""
+
+    def __init__(self, rng: DeviceRng):
+        self.rng = rng
+        self.bufs = {}
+        self.last = {}
+
+    def begin(self):
+        self.last = {}
+
+    def draw(self, name: str, sid: int, B: int, Z: int, rank: int) -> torch.Tensor:
+        buf = self.bufs.get(name)
+        if buf is None or buf.shape != (B, Z):
+            buf = self.bufs[name] = torch.empty(B, Z, dtype=torch.float32, device=self.rng.device)
+        self.rng.normal(B, Z, sid, row0=rank * B, out=buf)
+        self.last[name] = buf
+        return buf
+
+    def end(self, B_global: int, Z: int):
+        self.rng.advance(blocks(B_global * Z))

@@ -29,6 +29,7 @@ from .nets import (CognitiveEncoderNet, DecoderNet, DiscriminatorNet, EncoderNet
                    refresh_net)
 from .ops import axpby, images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
+from .rng import SID_EPS, SID_EPS_TEACHER, SID_ZP, DeviceRng, StepNoise
 
 _P = lib.ptr
 
@@ -290,6 +291,38 @@ class _GanStepBase(Monitored):
         _attach_reducers(nets, self.dd)
         self.fw: Dict[str, object] = {}
 
+    def _init_rng(self, rng: Optional[DeviceRng]):
+        self.rng = rng
+        self._noise = StepNoise(rng) if rng is not None else None
+        self._last_noise: Dict[str, torch.Tensor] = {}
+
+    def _resolve_noise(self, B: int, wanted):
+        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
+        the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
+        [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
+        draws, by the block count of a [global batch, latent_dim] draw.  Returns the tensors in the order asked for."""
+        missing = [name for name, _, t in wanted if t is None]
+        if missing and self._noise is None:
+            raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
+                             "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
+        Z = self.cfg.latent_dim
+        dd = self.dd
+        rank = dd.dist.get_rank() if dd.on else 0
+        if missing:
+            self._noise.begin()
+        out = {}
+        for name, sid, t in wanted:
+            out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
+        if missing:
+            self._noise.end(B * dd.world, Z)
+        self._last_noise = out
+        return list(out.values())
+
+    def last_noise(self) -> Dict[str, torch.Tensor]:
+        """The noise tensors the last step used, by argument name in the order ``step`` takes them (the step's own
+        buffers where it drew them: clone what has to outlive the next step)."""
+        return dict(self._last_noise)
+
     def _reduce_async(self, group, part=None):
         """Data parallel: the sub-network's deferred weight gradients -> reference layout (one launch), then the
         asynchronous SUM all-reduce of the gradient buffer (or of ``part`` of it).  Nothing on one GPU: the gradients
@@ -459,8 +492,11 @@ class Stage1Step(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
-                 monitor: bool = False):
+                 monitor: bool = False, rng: Optional[DeviceRng] = None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps`` and ``z_p`` on the device (``last_noise()``)
+        and a step recorded with ``capture(x)`` draws fresh noise at every replay.  Noise passed to ``step`` is used as
+        it is, with or without ``rng``.
         ``mode``: the loss composition of train_vgan_stage1.py:359-388 -- 'vae-gan' (default), 'beta-vae' (KL weight
         hp.beta / batch), 'dcgan' (pixel nle, encoder not trained), 'vae' (pixel nle, discriminator not trained unless
         the gate re-arms both).  ``gate_skip``: in ``step`` the weight-gradient GEMMs of the decoder / discriminator are
@@ -477,6 +513,7 @@ class Stage1Step(_GanStepBase):
         self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self.dis = DiscriminatorNet(cfg, device)
         self._init_common(device, hp, scales, distributed, sync_bn, (self.enc, self.dec, self.dis))
+        self._init_rng(rng)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.enc.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -506,10 +543,11 @@ class Stage1Step(_GanStepBase):
         self.dis.group.load_state_dict(sd, "discriminator.")
 
     # ---- the step ---------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, eps: torch.Tensor, z_p: torch.Tensor):
+    def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, z_p: Optional[torch.Tensor] = None):
         require_gpu(x)
         cfg = self.cfg
         B, _, H, W = x.shape
+        eps, z_p = self._resolve_noise(B, [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)])
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = x.device
         self.scal.zero_()
@@ -707,7 +745,7 @@ class Stage1Step(_GanStepBase):
         self.opt_dec.step(self.flags[1:2], gdev=self._slot(S_GDEC))
         self.opt_dis.step(self.flags[0:1], gdev=self._slot(S_NA))
 
-    def capture_forward(self, x, eps, z_p, warmup: int = 2):
+    def capture_forward(self, x, eps=None, z_p=None, warmup: int = 2):
         """Hybrid launch mode (one GPU): the forward pass + gate -- a dependent chain with nothing to overlap -- is
         recorded into a HIP graph, the backward pass and the updates stay eagerly issued launches on two streams
         (``ops.side_run``).  Halves the Python work per step, which is what decides whether a slow host can keep the
@@ -756,8 +794,9 @@ class Stage1Step(_GanStepBase):
         self._fwd_graph = graph
         return run
 
-    def step(self, x, eps, z_p):
-        """One full training step; returns the device scalar block (see LOG_KEYS) without syncing."""
+    def step(self, x, eps=None, z_p=None):
+        """One full training step; returns the device scalar block (see LOG_KEYS) without syncing.  ``eps`` / ``z_p``
+        left out: drawn by the step's ``rng`` (ValueError without one)."""
         fw = self.forward(x, eps, z_p)
         self.gate(fw["B"] * self.dd.world)
         self.backward(early_apply=True)
@@ -799,8 +838,11 @@ class CognitiveStep(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False):
+                 gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
+                 rng: Optional[DeviceRng] = None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``rng``: a fmri_hip.rng.DeviceRng; ``step(fmri, image)`` then draws ``eps``, ``z_p`` and -- where the teacher
+        samples (stage 2, mode 'vae-gan') -- ``eps_teacher`` on the device (see Stage1Step).
         ``mode``: 'vae-gan' (default) or 'vae' -- the scripts' `--mode vae` (train_vgan_stage2.py:234-238,362-366;
         train_vgan_stage3.py:370-374): no teacher net (the discriminator's "real" slot is the ground-truth image), the
         reconstruction term is the PIXEL nle instead of the feature mse, the discriminator loss bce_orig + bce_sampled.
@@ -820,6 +862,7 @@ class CognitiveStep(_GanStepBase):
         self.teacher_enc = EncoderNet(cfg, device) if (stage == 2 and mode != "vae") else None
         nets = [self.cog, self.dec, self.dis] + ([self.teacher_enc] if self.teacher_enc is not None else [])
         self._init_common(device, hp, scales, distributed, sync_bn, nets)
+        self._init_rng(rng)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -866,11 +909,17 @@ class CognitiveStep(_GanStepBase):
         self.dec.group.load_state_dict(sd, "decoder.")
         self.dis.group.load_state_dict(sd, "discriminator.")
 
-    def forward(self, fmri: torch.Tensor, image: torch.Tensor, eps: torch.Tensor, z_p: torch.Tensor,
-                eps_teacher: Optional[torch.Tensor] = None):
+    def forward(self, fmri: torch.Tensor, image: torch.Tensor, eps: Optional[torch.Tensor] = None,
+                z_p: Optional[torch.Tensor] = None, eps_teacher: Optional[torch.Tensor] = None):
         require_gpu(fmri)
         cfg = self.cfg
         B, _, H, W = image.shape
+        wanted = [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)]
+        if self.teacher_enc is not None:
+            wanted.append(("eps_teacher", SID_EPS_TEACHER, eps_teacher))
+        eps, z_p, *rest = self._resolve_noise(B, wanted)
+        if rest:
+            eps_teacher = rest[0]
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         self.scal.zero_()
@@ -998,7 +1047,7 @@ class CognitiveStep(_GanStepBase):
             self.opt_dec.step(self.flags[1:2], clamp=1.0, gdev=self._slot(S_GDEC))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))
 
-    def step(self, fmri, image, eps, z_p, eps_teacher=None):
+    def step(self, fmri, image, eps=None, z_p=None, eps_teacher=None):
         fw = self.forward(fmri, image, eps, z_p, eps_teacher)
         self.gate(fw["B"] * self.dd.world)
         self.backward(fuse=True)

@@ -33,6 +33,7 @@ from .mmd import mmd_imq
 from .ops import images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
 from .monitor import Monitored
+from .rng import SID_EPS, SID_ZFAKE, SID_ZP, DeviceRng
 from .steps import (LOG_KEYS, S_ESQ, S_NA, S_NB, S_NE, GanHyper, Scales, Stage1Step, _attach_reducers, _Dist,
                     _GanStepBase, _Optim)
 
@@ -104,8 +105,10 @@ class WaeStep(_LatentDiscPhase, Monitored):
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 penalty: str = "gan", monitor: bool = False):
-        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py)."""
+                 penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None):
+        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``rng``: a fmri_hip.rng.DeviceRng; Stage I's ``step(x)`` then draws ``z_fake_noise`` on the device (see
+        steps.Stage1Step; Stages II / III take no noise)."""
         assert stage in (1, 2, 3)
         if penalty not in ("gan", "mmd"):
             raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
@@ -129,6 +132,7 @@ class WaeStep(_LatentDiscPhase, Monitored):
         self.opt_dec = _Optim(self.dec.group, "adam", hp_.lr_dec, betas=hp_.betas)
         self.opt_dis = _Optim(self.wd.group, "adam", hp_.lr_dis, betas=hp_.betas)
         self.fw = {}
+        self._init_rng(rng)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.wd)], 1)
 
@@ -157,11 +161,13 @@ class WaeStep(_LatentDiscPhase, Monitored):
     # ---- the step --------------------------------------------------------------------------------------------
     def step(self, image: torch.Tensor, z_fake_noise: Optional[torch.Tensor] = None,
              fmri: Optional[torch.Tensor] = None):
-        """Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276).
-        Stage II/III: step(image, fmri=fmri)."""
+        """Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276); step(x) draws the noise
+        with the step's ``rng``.  Stage II/III: step(image, fmri=fmri)."""
         require_gpu(image)
         cfg, hp, sc, st = self.cfg, self.hp, self.sc, self.stage
         B, _, H, W = image.shape
+        if st == 1:
+            z_fake_noise, = self._resolve_noise(B, [("z_fake_noise", SID_ZFAKE, z_fake_noise)])
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         Bg = B * self.dd.world
@@ -279,6 +285,9 @@ class WaeStep(_LatentDiscPhase, Monitored):
     capture = _GanStepBase.capture
     _capture = _GanStepBase._capture
     _versioned = _GanStepBase._versioned
+    _init_rng = _GanStepBase._init_rng
+    _resolve_noise = _GanStepBase._resolve_noise
+    last_noise = _GanStepBase.last_noise
 
     def _renorm(self, x32: torch.Tensor, scale: float, rows_global: int):
         n = x32.numel()
@@ -330,8 +339,10 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
-                 mode: str = "vae-gan", monitor: bool = False):
-        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode)
+                 mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None):
+        """``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
+        (see Stage1Step)."""
+        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng)
         hp = self.hp
         self.lam = lam
         self.torch14 = torch14_zero_grad
@@ -357,8 +368,12 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         sd.update(self.wd.group.state_dict("wae_discriminator."))
         return sd
 
-    def step(self, x, eps, z_p, z_fake_noise):
+    def step(self, x, eps=None, z_p=None, z_fake_noise=None):
+        eps, z_p, z_fake_noise = self._resolve_noise(x.shape[0], [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
+                                                                  ("z_fake_noise", SID_ZFAKE, z_fake_noise)])
+        noise = self._last_noise
         fw = self.forward(x, eps, z_p)
+        self._last_noise = noise             # (forward records its two)
         self.gate(fw["B"] * self.dd.world)
         B, Z = fw["B"], self.cfg.latent_dim
         zp = pad8(Z)
