@@ -178,6 +178,20 @@ int fmri_get_deterministic(void);
 int fmri_ingest_u8(const uint8_t* src, int N, int H, int W, int C, const int* flip_dev, const int* shift_dev,
                    float mean0, float mean1, float mean2, float std0, float std1, float std2, void* dst16,
                    float* dst32, void* stream);
+/* The same for a batch read out of a device-resident pool by index (fmri_hip/feed.py): image n of the output is
+ * src[idx_dev[n]] of the pool src [N_pool][H][W][C] (idx_dev: int32 [N], e.g. from fmri_sampler_indices) passed through
+ * the same flip (flip_dev[n]) / shift (shift_dev[2n], [2n+1]) / /255 / grey -> RGB / normalise; dst16 (fp16 NHWC8, 16-byte
+ * aligned) and dst32 (fp32 NCHW) are bit-identical to fmri_ingest_u8 on the gathered images.  One pass: the pool is read
+ * in place, no gathered uint8 batch is written.  An index outside [0, N_pool) is never dereferenced: it is clamped into
+ * the range, and err_dev (device int, may be NULL, caller-zeroed, added to) counts the images it happened to. */
+int fmri_ingest_u8_gather(const uint8_t* src, const int32_t* idx_dev, int N_pool, int N, int H, int W, int C,
+                          const int* flip_dev, const int* shift_dev, float mean0, float mean1, float mean2, float std0,
+                          float std1, float std2, void* dst16, float* dst32, int* err_dev, void* stream);
+/* Row gather of the same feed: src [N_pool][V] fp32 (the fMRI of the dataset) -> dst32 [B][V] = src[idx_dev[b]] and / or
+ * dst16 [B][pad8(V)] (16-byte aligned) = fp16 of it, round to nearest even as fmri_rows_f32_to_f16 at scale 1, the columns
+ * from V on zero.  Either may be NULL.  Indices are clamped and counted as above (once per row). */
+int fmri_gather_rows_f32(const float* src, int N_pool, int V, const int32_t* idx_dev, int B, float* dst32, void* dst16,
+                         int* err_dev, void* stream);
 
 /* ---- CenterCrop((crop, crop)) + Resize((S, S)) of a ragged batch of decoded uint8 images, the head of the COCO
  * pipeline (train/train_vgan_stage1.py:162-165: torchvision 0.5.0 transforms on PIL images).  Bit-exact with
@@ -432,11 +446,57 @@ int fmri_counter_inc(int* counter_dev, void* stream);
  *   probability differs from 1 / (hi - lo + 1) by less than 2^-32, i.e. the relative bias is at most (hi - lo + 1) * 2^-32.
  *   n > 2^40: FMRI_E_UNSUPPORTED.
  * fmri_rng_advance: offset += nblocks (>= 0), one thread, a launch of its own behind the draws that share the offset
- *   (stream order keeps it behind their reads).  A draw of n elements from row0 = 0 consumes ceil(n / 4) blocks. */
+ *   (stream order keeps it behind their reads).  A draw of n elements from row0 = 0 consumes ceil(n / 4) blocks.
+ * fmri_rng_u32_at: fmri_rng_u32 for the elements start .. start + n - 1 (start >= 0) of the same stream: out[i] is made
+ *   from w_(start + i), word (start + i) % 4 of block (start + i) / 4.  Rank k of a data-parallel run passes start = k * n
+ *   (flips) or 2 * k * n (shifts) and gets its slice of the one-rank draw at the global batch; start = 0 is fmri_rng_u32,
+ *   bit for bit.  n or start > 2^40: FMRI_E_UNSUPPORTED. */
 int fmri_rng_normal(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
                     void* stream);
 int fmri_rng_u32(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, void* stream);
 int fmri_rng_advance(int64_t* state, int64_t nblocks, void* stream);
+int fmri_rng_u32_at(const int64_t* state, int32_t* out, int64_t n, int64_t start, int sid, int lo, int hi,
+                    void* stream);
+/* ---- epoch sampler of a device-resident dataset (csrc/rng.hip; fmri_hip/feed.py) --------------------------------------
+ * What `DataLoader(dataset, batch_size, shuffle=True)` does on the host for every batch of the reference's loops
+ * (train/train_vgan_stage1.py:316 ff.): a fresh permutation of the N samples per epoch, B of them per step.  Here the
+ * permutation is a keyed bijection evaluated per index on the device -- no buffer of N elements, no sort -- and the
+ * position lives in device memory, so a step recorded into a HIP graph walks through whole epochs with no host work.
+ *
+ * pi(seed, epoch) on [0, N), 1 <= N < 2^31.  N = 1: pi(0) = 0.  Otherwise, with b = the bit length of N - 1,
+ * k = ceil(b / 2) (1 .. 16), mask = 2^k - 1 (the domain 2^(2k) holds N and is below 4 N):
+ *     x = i
+ *     repeat:  L = x >> k,  R = x & mask
+ *              for r = 0 .. 5:   f = output word 0 of Philox4x32-10 with key (lo32(seed), hi32(seed)) and counter
+ *                                    ((r << 16) | R,  lo32(epoch),  16,  0x80000000 | hi32(epoch))
+ *                                (L, R) = (R, L ^ (f & mask))
+ *              x = (L << k) | R
+ *     until x < N;   pi(i) = x
+ * One pass of the loop body is a balanced Feistel network, a bijection of [0, 2^(2k)) whatever the round function is;
+ * repeating it until the value falls below N ("cycle walking") follows the cycle of that bijection through i back into
+ * [0, N) and therefore restricts it to a bijection of [0, N) -- fewer than 4 passes on average.  The fourth counter word
+ * has its top bit set: fmri_rng_normal / fmri_rng_u32 always have 0 there, so no draw of theirs shares a block with the
+ * sampler, whatever stream id a caller picks (16 is SID_PERM, kept apart from the steps' ids as well); epoch < 2^63.
+ * Six rounds: with independent random round functions three rounds already make a Feistel network indistinguishable
+ * from a random permutation for a reader of well under 2^(k/2) values and four do so for chosen inputs AND outputs
+ * (Luby & Rackoff 1988), but an epoch reads the whole table, 2^(2k) values, where four rounds are known to show
+ * (Patarin, "Generic attacks on Feistel schemes", 2001: order 2^k known values for four rounds, order 2^(2k) -- the
+ * table itself -- from six on); two more rounds cost six instead of four Philox blocks per pass for B indices per
+ * step -- a few hundred blocks where one noise draw takes thousands.  pi is a pure function of (seed, epoch, i, N).
+ *
+ * state: device int64[3] = [seed, epoch, cursor], 8-byte aligned, read on the device.
+ * fmri_sampler_indices: idx_out[i] (int32, i < B) = pi(seed, epoch)((cursor + row0 + i) mod N).  row0 >= 0 is the
+ *   caller's first row of the GLOBAL batch: rank k of W passes row0 = k * B and gets rows k * B .. of the one-rank batch
+ *   of W * B.  row0 + B > N: FMRI_E_UNSUPPORTED.  Does not move the state.
+ * fmri_sampler_advance: cursor += B_global; then, if fewer than B_global positions are left (N - cursor < B_global),
+ *   epoch += 1 and cursor = 0.  One thread, a launch of its own behind the reads of the state (stream order), like
+ *   fmri_rng_advance.  Drop-last: every batch has B_global samples and an epoch visits floor(N / B_global) * B_global
+ *   DISTINCT samples; the N mod B_global positions at the end of the permutation are skipped in that epoch (another
+ *   permutation, so other samples, in the next).  The reference's DataLoader (drop_last=False) runs a short last batch
+ *   instead; a recorded step has a fixed batch size and cannot.  N < B_global: FMRI_E_UNSUPPORTED.
+ * Both: enqueue-only, no allocation, no global state.  (seed, epoch, cursor) reproduces a run. */
+int fmri_sampler_indices(const int64_t* state, int N, int B, int64_t row0, int32_t* idx_out, void* stream);
+int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream);
 /* starting cotangents of the two back-propagated streams, fp16, multiplied by gscale * (*norm) (norm: device float) */
 int fmri_gan_head_bwd(const float* logit, int ldl, int B, void* dlogit, int ldg, float gscale, const float* norm,
                       void* stream);

@@ -67,6 +67,26 @@ int fmri_ingest_u8(const uint8_t* src, int N, int H, int W, int C, const int* fl
     return ingest_u8_launch(src, N, H, W, C, flip_dev, shift_dev, m, sd, (half_t*)dst16, dst32, S(stream));
 }
 
+/* ---- the same out of a device-resident pool, by index (fmri_hip/feed.py) ---- */
+int fmri_ingest_u8_gather(const uint8_t* src, const int32_t* idx_dev, int N_pool, int N, int H, int W, int C,
+                          const int* flip_dev, const int* shift_dev, float mean0, float mean1, float mean2, float std0,
+                          float std1, float std2, void* dst16, float* dst32, int* err_dev, void* stream) {
+    if (!src || !idx_dev || N_pool < 1 || N < 1 || H < 1 || W < 1 || (C != 1 && C != 3) || (!dst16 && !dst32) ||
+        std0 == 0.f || std1 == 0.f || std2 == 0.f || ((uintptr_t)dst16 & 15) || ((uintptr_t)dst32 & 3) ||
+        ((uintptr_t)idx_dev & 3) || ((uintptr_t)err_dev & 3))
+        return FMRI_E_BADARG;
+    const float m[3] = {mean0, mean1, mean2}, sd[3] = {std0, std1, std2};
+    return ingest_u8_gather_launch(src, idx_dev, N_pool, N, H, W, C, flip_dev, shift_dev, m, sd, (half_t*)dst16, dst32,
+                                   err_dev, S(stream));
+}
+int fmri_gather_rows_f32(const float* src, int N_pool, int V, const int32_t* idx_dev, int B, float* dst32, void* dst16,
+                         int* err_dev, void* stream) {
+    if (!src || !idx_dev || N_pool < 1 || V < 1 || B < 1 || (!dst16 && !dst32) || ((uintptr_t)src & 3) ||
+        ((uintptr_t)dst32 & 3) || ((uintptr_t)dst16 & 15) || ((uintptr_t)idx_dev & 3) || ((uintptr_t)err_dev & 3))
+        return FMRI_E_BADARG;
+    return gather_rows_launch(src, N_pool, V, idx_dev, B, dst32, (half_t*)dst16, err_dev, S(stream));
+}
+
 /* ---- head of the image transforms: CenterCrop + Resize (train_vgan_stage1.py:162-165) --------------------------- */
 int fmri_resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* coef, int ksize_cap) {
     if (in_size < 1 || out_size < 1 || !bounds || !coef || ksize_cap < 1) return FMRI_E_BADARG;
@@ -1134,11 +1154,28 @@ int fmri_rng_normal(const int64_t* state, float* out, int rows, int cols, int ld
 int fmri_rng_u32(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, void* stream) {
     if (!state || ((uintptr_t)state & 7) || !out || ((uintptr_t)out & 3) || n < 1 || sid < 0 || hi < lo)
         return FMRI_E_BADARG;
-    return rng_u32_launch(state, out, n, sid, lo, hi, S(stream));
+    return rng_u32_launch(state, out, n, 0, sid, lo, hi, S(stream));
+}
+int fmri_rng_u32_at(const int64_t* state, int32_t* out, int64_t n, int64_t start, int sid, int lo, int hi,
+                    void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !out || ((uintptr_t)out & 3) || n < 1 || start < 0 || sid < 0 || hi < lo)
+        return FMRI_E_BADARG;
+    return rng_u32_launch(state, out, n, start, sid, lo, hi, S(stream));
 }
 int fmri_rng_advance(int64_t* state, int64_t nblocks, void* stream) {
     if (!state || ((uintptr_t)state & 7) || nblocks < 0) return FMRI_E_BADARG;
     return rng_advance_launch(state, nblocks, S(stream));
+}
+int fmri_sampler_indices(const int64_t* state, int N, int B, int64_t row0, int32_t* idx_out, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !idx_out || ((uintptr_t)idx_out & 3) || N < 1 || B < 1 || row0 < 0)
+        return FMRI_E_BADARG;
+    if (row0 + B > N) return FMRI_E_UNSUPPORTED;
+    return sampler_indices_launch(state, N, B, row0, idx_out, S(stream));
+}
+int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || N < 1 || B_global < 1) return FMRI_E_BADARG;
+    if (N < B_global) return FMRI_E_UNSUPPORTED;
+    return sampler_advance_launch(state, N, B_global, S(stream));
 }
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream) {

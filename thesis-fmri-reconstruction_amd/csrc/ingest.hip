@@ -5,19 +5,33 @@
 //   (data_loader.py:374-401: 1 -> 3 channels)  ->  Normalize(mean, std) (train_vgan_stage1.py:169).
 // The random draws (flip flag, shift) are made by the caller and passed per image, so the kernel is deterministic.
 // One 16-byte store per pixel; HBM bound and tiny (256 images of 64x64: 3 MB in, 8 MB out).
+// The gathering forms (fmri_ingest_u8_gather, fmri_gather_rows_f32) read the batch out of a device-resident dataset by
+// index: the feed of the fused steps (fmri_hip/feed.py).
 #include "kernels.h"
 
 namespace fmri {
 
+// GATHER: image n of the batch is image idx[n] of a resident pool of N_pool images (fmri_hip/feed.py: the batch an epoch
+// sampler drew), read in place -- the gathered uint8 batch never exists.  An index outside [0, N_pool) is clamped before
+// it is used and counted into *err (one add per image, by the thread of its first pixel).  Same arithmetic, same stores.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ src, int N, int H, int W, int C,
                                                         const int* __restrict__ flip, const int* __restrict__ shift,
                                                         float m0, float m1, float m2, float r0, float r1, float r2,
-                                                        half_t* __restrict__ dst16, float* __restrict__ dst32) {
+                                                        half_t* __restrict__ dst16, float* __restrict__ dst32,
+                                                        const int32_t* __restrict__ idx, int N_pool,
+                                                        int* __restrict__ err) {
     const int64_t total = (int64_t)N * H * W;
     for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int x = (int)(i % W);
         const int y = (int)((i / W) % H);
         const int n = (int)(i / ((int64_t)W * H));
+        int ns = n;
+        if (GATHER) {
+            const int j = idx[n];
+            ns = j < 0 ? 0 : (j >= N_pool ? N_pool - 1 : j);
+            if (err && ns != j && x == 0 && y == 0) atomicAdd(err, 1);
+        }
         // output pixel (y, x) of the shifted image = input pixel (y - sy, x - sx), clamped to the edge ('nearest');
         // the flip is applied before the shift (transform order of the scripts)
         int sy = 0, sx = 0;
@@ -26,7 +40,7 @@ __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restric
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
         xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
         if (flip && flip[n]) xx = W - 1 - xx;
-        const uint8_t* p = src + ((int64_t)(n * H + yy) * W + xx) * C;
+        const uint8_t* p = src + (((int64_t)ns * H + yy) * W + xx) * C;
         const float v0 = p[0] * (1.f / 255.f);
         const float v1 = C == 3 ? p[1] * (1.f / 255.f) : v0;
         const float v2 = C == 3 ? p[2] * (1.f / 255.f) : v0;
@@ -43,13 +57,89 @@ __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restric
     }
 }
 
+namespace {
+int ingest_blocks(int64_t total) {
+    int blocks = (int)((total + 255) / 256);
+    return blocks > 4096 ? 4096 : blocks;
+}
+}  // namespace
+
 int ingest_u8_launch(const uint8_t* src, int N, int H, int W, int C, const int* flip, const int* shift,
                      const float* mean3, const float* std3, half_t* dst16, float* dst32, hipStream_t st) {
-    const int64_t total = (int64_t)N * H * W;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(ingest_u8_kernel, dim3(blocks), dim3(256), 0, st, src, N, H, W, C, flip, shift, mean3[0],
-                       mean3[1], mean3[2], 1.f / std3[0], 1.f / std3[1], 1.f / std3[2], dst16, dst32);
+    hipLaunchKernelGGL(ingest_u8_kernel<false>, dim3(ingest_blocks((int64_t)N * H * W)), dim3(256), 0, st, src, N, H, W,
+                       C, flip, shift, mean3[0], mean3[1], mean3[2], 1.f / std3[0], 1.f / std3[1], 1.f / std3[2], dst16,
+                       dst32, nullptr, 0, nullptr);
+    return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
+}
+
+int ingest_u8_gather_launch(const uint8_t* src, const int32_t* idx, int N_pool, int N, int H, int W, int C,
+                            const int* flip, const int* shift, const float* mean3, const float* std3, half_t* dst16,
+                            float* dst32, int* err, hipStream_t st) {
+    hipLaunchKernelGGL(ingest_u8_kernel<true>, dim3(ingest_blocks((int64_t)N * H * W)), dim3(256), 0, st, src, N, H, W,
+                       C, flip, shift, mean3[0], mean3[1], mean3[2], 1.f / std3[0], 1.f / std3[1], 1.f / std3[2], dst16,
+                       dst32, idx, N_pool, err);
+    return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
+}
+
+// dst32[b][0 .. V) = src[idx[b]][0 .. V) and / or dst16[b][0 .. Vp) = fp16 of it, the columns from V on zero (the engine's
+// fp16 rows: rows_f32_to_f16_kernel at scale 1, csrc/layout.hip): the fMRI rows of the batch the sampler drew.  One
+// thread per 8 columns: two 16-byte loads (V % 4 == 0 and aligned rows; single loads otherwise), two 16-byte fp32 stores,
+// one 16-byte fp16 store.  Indices are clamped and counted as above (the thread of a row's first chunk counts).
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int N_pool, int V, int Vp,
+                                                          const int32_t* __restrict__ idx, int B,
+                                                          float* __restrict__ dst32, half_t* __restrict__ dst16,
+                                                          int* __restrict__ err) {
+    const int chunks = Vp / 8;
+    const int64_t total = (int64_t)B * chunks;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int ch = (int)(i % chunks);
+        const int b = (int)(i / chunks);
+        const int j = idx[b];
+        const int r = j < 0 ? 0 : (j >= N_pool ? N_pool - 1 : j);
+        if (err && r != j && ch == 0) atomicAdd(err, 1);
+        const int c0 = ch * 8;
+        const float* s = src + (int64_t)r * V + c0;
+        float v[8];
+        if (VEC) {                                               // V % 4 == 0: each group of four lies inside or outside
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 a = c0 < V ? *(const float4*)s : z;
+            const float4 c = c0 + 4 < V ? *(const float4*)(s + 4) : z;
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+            if (dst32) {
+                float* d = dst32 + (int64_t)b * V + c0;
+                if (c0 < V) *(float4*)d = a;
+                if (c0 + 4 < V) *(float4*)(d + 4) = c;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = c0 + k < V ? s[k] : 0.f;
+            if (dst32) {
+                float* d = dst32 + (int64_t)b * V + c0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (c0 + k < V) d[k] = v[k];
+            }
+        }
+        if (dst16) {
+            h8 o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3], (half_t)v[4], (half_t)v[5], (half_t)v[6],
+                    (half_t)v[7]};
+            *(h8*)(dst16 + (int64_t)b * Vp + c0) = o;
+        }
+    }
+}
+
+int gather_rows_launch(const float* src, int N_pool, int V, const int32_t* idx, int B, float* dst32, half_t* dst16,
+                       int* err, hipStream_t st) {
+    const int Vp = (V + 7) / 8 * 8;
+    const int blocks = ingest_blocks((int64_t)B * (Vp / 8));
+    const bool vec = V % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst32 & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(blocks), dim3(256), 0, st, src, N_pool, V, Vp, idx, B, dst32,
+                           dst16, err);
+    else
+        hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(blocks), dim3(256), 0, st, src, N_pool, V, Vp, idx, B, dst32,
+                           dst16, err);
     return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
 }
 

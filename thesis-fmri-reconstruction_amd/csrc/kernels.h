@@ -268,8 +268,11 @@ int compose_gate_launch(float* scal, int* flags, float batch, float nfeat, float
 int counter_inc_launch(int* t, hipStream_t st);
 int rng_normal_launch(const int64_t* state, float* out, int rows, int cols, int ld, int64_t row0, int sid, float scale,
                       hipStream_t st);
-int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int sid, int lo, int hi, hipStream_t st);
+int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int64_t start, int sid, int lo, int hi,
+                   hipStream_t st);
 int rng_advance_launch(int64_t* state, int64_t nblocks, hipStream_t st);
+int sampler_indices_launch(const int64_t* state, int N, int B, int64_t row0, int32_t* idx, hipStream_t st);
+int sampler_advance_launch(int64_t* state, int64_t N, int64_t B_global, hipStream_t st);
 int axpby_f16_launch(const half_t* x, const half_t* y, half_t* out, int64_t n, float a, float b, const float* pa,
                      const float* pb, hipStream_t st);
 int sumsq_launch(const float* x, int64_t n, float* acc, hipStream_t st);
@@ -286,6 +289,11 @@ int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float l
 
 int ingest_u8_launch(const uint8_t* src, int N, int H, int W, int C, const int* flip, const int* shift,
                      const float* mean3, const float* std3, half_t* dst16, float* dst32, hipStream_t st);
+int ingest_u8_gather_launch(const uint8_t* src, const int32_t* idx, int N_pool, int N, int H, int W, int C,
+                            const int* flip, const int* shift, const float* mean3, const float* std3, half_t* dst16,
+                            float* dst32, int* err, hipStream_t st);
+int gather_rows_launch(const float* src, int N_pool, int V, const int32_t* idx, int B, float* dst32, half_t* dst16,
+                       int* err, hipStream_t st);
 int resize_coeffs(int in_size, int out_size, int32_t* bounds, int32_t* coef, int ksize_cap);
 int crop_resize_u8_launch(const uint8_t* pool, const int64_t* offsets, const int32_t* dims, int N, int crop, int S,
                           const int32_t* hb, const int32_t* hk, int hks, const int32_t* vb, const int32_t* vk, int vks,

@@ -33,6 +33,8 @@ _SIGS = {
     "fmri_transpose_f16": [_p, _p, _i, _i, _i, _i, _i, _p],
     "fmri_apply_batch": [_p, _i, _i, _i, _p, _f, _f, _f, _p, _f, _p, _i, _p],
     "fmri_ingest_u8": [_p, _i, _i, _i, _i, _p, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p],
+    "fmri_ingest_u8_gather": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p],
+    "fmri_gather_rows_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p],
     "fmri_crop_resize_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p],
     "fmri_pcc": [_p, _p, _l, _p, _p, _p],
     "fmri_ssim": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
@@ -96,7 +98,10 @@ _SIGS = {
     "fmri_counter_inc": [_p, _p],
     "fmri_rng_normal": [_p, _p, _i, _i, _i, _l, _i, _f, _p],
     "fmri_rng_u32": [_p, _p, _l, _i, _i, _i, _p],
+    "fmri_rng_u32_at": [_p, _p, _l, _l, _i, _i, _i, _p],
     "fmri_rng_advance": [_p, _l, _p],
+    "fmri_sampler_indices": [_p, _i, _i, _l, _p, _p],
+    "fmri_sampler_advance": [_p, _i, _i, _p],
     "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
     "fmri_sumsq": [_p, _l, _p, _p],

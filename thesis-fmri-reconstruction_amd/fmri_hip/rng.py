@@ -24,6 +24,7 @@ SID_EPS_TEACHER = 2    # reparameterisation noise of the Stage-II teacher
 SID_ZFAKE = 3          # WAE prior sample (before the factor 0.5)
 SID_FLIP = 8           # per-image horizontal flip
 SID_SHIFT = 9          # per-image (rows, cols) shift
+SID_PERM = 16          # the epoch sampler's round function (fmri_sampler_indices; a counter layout of its own)
 
 _I64 = (1 << 64) - 1
 
@@ -80,24 +81,30 @@ class DeviceRng:
         lib.call("fmri_rng_normal", _P(self._state), _P(out), rows, cols, ld, int(row0), sid, float(scale))
         return out
 
-    def integers(self, n: int, lo: int, hi: int, sid: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """int32 [n] in [lo, hi] (both inclusive) of stream ``sid`` at the current offset."""
+    def integers(self, n: int, lo: int, hi: int, sid: int, out: Optional[torch.Tensor] = None,
+                 start: int = 0) -> torch.Tensor:
+        """int32 [n] in [lo, hi] (both inclusive): elements start .. start + n of stream ``sid`` at the current offset
+        (``start``: a rank's slice of a draw made at the global batch)."""
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.device)
         if (out.dtype != torch.int32 or out.numel() != n or not out.is_contiguous()
                 or out.device != self._state.device):
             raise ValueError("DeviceRng.integers: out must be a contiguous int32 tensor of n elements on the "
                              "generator's device")
-        lib.call("fmri_rng_u32", _P(self._state), _P(out), n, sid, int(lo), int(hi))
+        if start:
+            lib.call("fmri_rng_u32_at", _P(self._state), _P(out), n, int(start), sid, int(lo), int(hi))
+        else:
+            lib.call("fmri_rng_u32", _P(self._state), _P(out), n, sid, int(lo), int(hi))
         return out
 
-    def flips(self, n: int) -> torch.Tensor:
-        """int32 [n] of 0 / 1: the ``flip`` argument of ``ops.ingest_u8``."""
-        return self.integers(n, 0, 1, SID_FLIP)
+    def flips(self, n: int, start: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n] of 0 / 1: the ``flip`` argument of ``ops.ingest_u8``, for images start .. start + n of the draw."""
+        return self.integers(n, 0, 1, SID_FLIP, out=out, start=start)
 
-    def shifts(self, n: int, max_shift: int) -> torch.Tensor:
-        """int32 [n, 2] (rows, cols) in [-max_shift, max_shift]: the ``shift`` argument of ``ops.ingest_u8``."""
-        return self.integers(2 * n, -int(max_shift), int(max_shift), SID_SHIFT).view(n, 2)
+    def shifts(self, n: int, max_shift: int, start: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n, 2] (rows, cols) in [-max_shift, max_shift]: the ``shift`` argument of ``ops.ingest_u8``, for images
+        start .. start + n of the draw (elements 2 * start .. of the stream)."""
+        return self.integers(2 * n, -int(max_shift), int(max_shift), SID_SHIFT, out=out, start=2 * start).view(n, 2)
 
 
 class StepNoise:
@@ -121,5 +128,7 @@ class StepNoise:
         self.last[name] = buf
         return buf
 
-    def end(self, B_global: int, Z: int):
-        self.rng.advance(blocks(B_global * Z))
+    def end(self, B_global: int, Z: int, at_least: int = 0):
+        """``at_least``: blocks of other draws made at the same offset (the augmentation draws of a feed that shares
+        the generator): the one advance covers the largest."""
+        self.rng.advance(max(blocks(B_global * Z), int(at_least)))

@@ -291,16 +291,46 @@ class _GanStepBase(Monitored):
         _attach_reducers(nets, self.dd)
         self.fw: Dict[str, object] = {}
 
-    def _init_rng(self, rng: Optional[DeviceRng]):
+    def _init_rng(self, rng: Optional[DeviceRng], feed=None):
         self.rng = rng
         self._noise = StepNoise(rng) if rng is not None else None
         self._last_noise: Dict[str, torch.Tensor] = {}
+        self.feed = feed             # fmri_hip.feed.DeviceFeed or None
+        self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
+
+    def _fed(self, *given):
+        """The batch of a step.  Without a feed: ``given`` (the caller's batch tensors) must all be there; returns None.
+        With a feed: none may be; the feed enqueues its next batch (fmri_hip/feed.py) -- the first launches of the step,
+        so they sit in the one graph of a recording, or in the first segment of a data-parallel one -- and its buffers
+        (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
+        generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
+        the noise and the augmentation draws."""
+        feed = self.feed
+        if feed is None:
+            if any(g is None for g in given):
+                raise ValueError(f"{type(self).__name__}: no batch given and the step has no feed (pass the batch, or "
+                                 "construct the step with feed=DeviceFeed(...))")
+            return None
+        if any(g is not None for g in given):
+            raise ValueError(f"{type(self).__name__}: the step has a feed and draws its own batch: step() takes no "
+                             "batch arguments")
+        shared = feed.rng is not None and feed.rng is self.rng
+        x, fm, _ = feed.next(advance_rng=not shared)
+        self._feed_blocks = feed.rng_blocks() if shared else 0
+        return x, fm, feed.fmri16
+
+    def _feed_advance(self):
+        """The shared generator's advance for a step that drew no noise after its feed drew augmentation."""
+        if self._feed_blocks:
+            self.rng.advance(self._feed_blocks)
+            self._feed_blocks = 0
 
     def _resolve_noise(self, B: int, wanted):
         """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
         the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
         [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
-        draws, by the block count of a [global batch, latent_dim] draw.  Returns the tensors in the order asked for."""
+        draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
+        the same generator in this step, if that is larger.  Returns the tensors in the order asked for."""
         missing = [name for name, _, t in wanted if t is None]
         if missing and self._noise is None:
             raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
@@ -314,7 +344,10 @@ class _GanStepBase(Monitored):
         for name, sid, t in wanted:
             out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
         if missing:
-            self._noise.end(B * dd.world, Z)
+            self._noise.end(B * dd.world, Z, at_least=self._feed_blocks)
+            self._feed_blocks = 0
+        else:
+            self._feed_advance()
         self._last_noise = out
         return list(out.values())
 
@@ -492,11 +525,15 @@ class Stage1Step(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
-                 monitor: bool = False, rng: Optional[DeviceRng] = None):
+                 monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps`` and ``z_p`` on the device (``last_noise()``)
         and a step recorded with ``capture(x)`` draws fresh noise at every replay.  Noise passed to ``step`` is used as
         it is, with or without ``rng``.
+        ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then takes no batch -- the feed draws the next shuffled,
+        augmented batch of its device-resident dataset as the step's first launches -- and ``capture()`` records a step
+        that replays whole epochs with no host work (a batch passed to such a step is a ValueError, as is none passed
+        to a step without a feed).
         ``mode``: the loss composition of train_vgan_stage1.py:359-388 -- 'vae-gan' (default), 'beta-vae' (KL weight
         hp.beta / batch), 'dcgan' (pixel nle, encoder not trained), 'vae' (pixel nle, discriminator not trained unless
         the gate re-arms both).  ``gate_skip``: in ``step`` the weight-gradient GEMMs of the decoder / discriminator are
@@ -513,7 +550,7 @@ class Stage1Step(_GanStepBase):
         self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self.dis = DiscriminatorNet(cfg, device)
         self._init_common(device, hp, scales, distributed, sync_bn, (self.enc, self.dec, self.dis))
-        self._init_rng(rng)
+        self._init_rng(rng, feed)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.enc.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -794,9 +831,12 @@ class Stage1Step(_GanStepBase):
         self._fwd_graph = graph
         return run
 
-    def step(self, x, eps=None, z_p=None):
+    def step(self, x=None, eps=None, z_p=None):
         """One full training step; returns the device scalar block (see LOG_KEYS) without syncing.  ``eps`` / ``z_p``
-        left out: drawn by the step's ``rng`` (ValueError without one)."""
+        left out: drawn by the step's ``rng`` (ValueError without one).  ``x`` left out: the step's ``feed`` draws it."""
+        fed = self._fed(x)
+        if fed is not None:
+            x = fed[0]
         fw = self.forward(x, eps, z_p)
         self.gate(fw["B"] * self.dd.world)
         self.backward(early_apply=True)
@@ -839,10 +879,12 @@ class CognitiveStep(_GanStepBase):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
-                 rng: Optional[DeviceRng] = None):
+                 rng: Optional[DeviceRng] = None, feed=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(fmri, image)`` then draws ``eps``, ``z_p`` and -- where the teacher
         samples (stage 2, mode 'vae-gan') -- ``eps_teacher`` on the device (see Stage1Step).
+        ``feed``: a fmri_hip.feed.DeviceFeed over a dataset with fMRI rows; ``step()`` then draws the image and the fMRI
+        row of the same samples itself (see Stage1Step).
         ``mode``: 'vae-gan' (default) or 'vae' -- the scripts' `--mode vae` (train_vgan_stage2.py:234-238,362-366;
         train_vgan_stage3.py:370-374): no teacher net (the discriminator's "real" slot is the ground-truth image), the
         reconstruction term is the PIXEL nle instead of the feature mse, the discriminator loss bce_orig + bce_sampled.
@@ -862,7 +904,9 @@ class CognitiveStep(_GanStepBase):
         self.teacher_enc = EncoderNet(cfg, device) if (stage == 2 and mode != "vae") else None
         nets = [self.cog, self.dec, self.dis] + ([self.teacher_enc] if self.teacher_enc is not None else [])
         self._init_common(device, hp, scales, distributed, sync_bn, nets)
-        self._init_rng(rng)
+        if feed is not None and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
+            raise ValueError("CognitiveStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
+        self._init_rng(rng, feed)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -910,7 +954,10 @@ class CognitiveStep(_GanStepBase):
         self.dis.group.load_state_dict(sd, "discriminator.")
 
     def forward(self, fmri: torch.Tensor, image: torch.Tensor, eps: Optional[torch.Tensor] = None,
-                z_p: Optional[torch.Tensor] = None, eps_teacher: Optional[torch.Tensor] = None):
+                z_p: Optional[torch.Tensor] = None, eps_teacher: Optional[torch.Tensor] = None,
+                fmri16: Optional[torch.Tensor] = None):
+        """``fmri16``: the fp16 [B, pad8(V)] rows of ``fmri`` where the caller already has them (a feed's gather pass
+        writes both); otherwise they are made here."""
         require_gpu(fmri)
         cfg = self.cfg
         B, _, H, W = image.shape
@@ -926,7 +973,8 @@ class CognitiveStep(_GanStepBase):
         if self.mon is not None:
             self.mon.zero()
         disc_in = torch.empty(3 * B, H, W, 8, dtype=torch.float16, device=dev)
-        fmri16 = rows_to_f16(fmri)
+        if fmri16 is None:
+            fmri16 = rows_to_f16(fmri)
         head32, cctx = self.cog.forward(fmri16)
         eps = eps.contiguous().float()
         if self.teacher_enc is not None:
@@ -1047,8 +1095,12 @@ class CognitiveStep(_GanStepBase):
             self.opt_dec.step(self.flags[1:2], clamp=1.0, gdev=self._slot(S_GDEC))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))
 
-    def step(self, fmri, image, eps=None, z_p=None, eps_teacher=None):
-        fw = self.forward(fmri, image, eps, z_p, eps_teacher)
+    def step(self, fmri=None, image=None, eps=None, z_p=None, eps_teacher=None):
+        fed = self._fed(fmri, image)
+        fmri16 = None
+        if fed is not None:
+            image, fmri, fmri16 = fed
+        fw = self.forward(fmri, image, eps, z_p, eps_teacher, fmri16=fmri16)
         self.gate(fw["B"] * self.dd.world)
         self.backward(fuse=True)
         self.apply()

@@ -105,10 +105,12 @@ class WaeStep(_LatentDiscPhase, Monitored):
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None):
+                 penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``rng``: a fmri_hip.rng.DeviceRng; Stage I's ``step(x)`` then draws ``z_fake_noise`` on the device (see
-        steps.Stage1Step; Stages II / III take no noise)."""
+        steps.Stage1Step; Stages II / III take no noise).
+        ``feed``: a fmri_hip.feed.DeviceFeed (Stages II / III: over a dataset with fMRI rows); ``step()`` then draws its
+        batch itself (see steps.Stage1Step)."""
         assert stage in (1, 2, 3)
         if penalty not in ("gan", "mmd"):
             raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
@@ -132,7 +134,9 @@ class WaeStep(_LatentDiscPhase, Monitored):
         self.opt_dec = _Optim(self.dec.group, "adam", hp_.lr_dec, betas=hp_.betas)
         self.opt_dis = _Optim(self.wd.group, "adam", hp_.lr_dis, betas=hp_.betas)
         self.fw = {}
-        self._init_rng(rng)
+        if feed is not None and stage > 1 and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
+            raise ValueError("WaeStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
+        self._init_rng(rng, feed)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.wd)], 1)
 
@@ -159,15 +163,22 @@ class WaeStep(_LatentDiscPhase, Monitored):
         return sd
 
     # ---- the step --------------------------------------------------------------------------------------------
-    def step(self, image: torch.Tensor, z_fake_noise: Optional[torch.Tensor] = None,
+    def step(self, image: Optional[torch.Tensor] = None, z_fake_noise: Optional[torch.Tensor] = None,
              fmri: Optional[torch.Tensor] = None):
         """Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276); step(x) draws the noise
-        with the step's ``rng``.  Stage II/III: step(image, fmri=fmri)."""
+        with the step's ``rng``.  Stage II/III: step(image, fmri=fmri).  With a ``feed``: step() / step(None, noise)."""
+        st = self.stage
+        fed = self._fed(image) if st == 1 else self._fed(image, fmri)
+        fmri16 = None
+        if fed is not None:
+            image, fmri, fmri16 = fed
         require_gpu(image)
-        cfg, hp, sc, st = self.cfg, self.hp, self.sc, self.stage
+        cfg, hp, sc = self.cfg, self.hp, self.sc
         B, _, H, W = image.shape
         if st == 1:
             z_fake_noise, = self._resolve_noise(B, [("z_fake_noise", SID_ZFAKE, z_fake_noise)])
+        else:
+            self._feed_advance()
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         Bg = B * self.dd.world
@@ -194,7 +205,7 @@ class WaeStep(_LatentDiscPhase, Monitored):
         else:
             head_t, _ = self.img_enc.forward(x16, updates=2 if st == 2 else 1)        # stage 2: :284,:293; 3: :312
             z_t16 = latent16(head_t) if gan or st == 2 else None
-            head32, ectx = self.cog.forward(rows_to_f16(fmri), updates=2)             # :292,:314 / :311,:333
+            head32, ectx = self.cog.forward(rows_to_f16(fmri) if fmri16 is None else fmri16, updates=2)             # :292,:314 / :311,:333
             z16 = latent16(head32)
             z_real16, z_fake16 = z_t16, z16
             p32 = head_t
@@ -287,6 +298,8 @@ class WaeStep(_LatentDiscPhase, Monitored):
     _versioned = _GanStepBase._versioned
     _init_rng = _GanStepBase._init_rng
     _resolve_noise = _GanStepBase._resolve_noise
+    _fed = _GanStepBase._fed
+    _feed_advance = _GanStepBase._feed_advance
     last_noise = _GanStepBase.last_noise
 
     def _renorm(self, x32: torch.Tensor, scale: float, rows_global: int):
@@ -339,10 +352,10 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
-                 mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None):
+                 mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
         """``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
-        (see Stage1Step)."""
-        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng)
+        (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step)."""
+        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng, feed=feed)
         hp = self.hp
         self.lam = lam
         self.torch14 = torch14_zero_grad
@@ -368,7 +381,10 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         sd.update(self.wd.group.state_dict("wae_discriminator."))
         return sd
 
-    def step(self, x, eps=None, z_p=None, z_fake_noise=None):
+    def step(self, x=None, eps=None, z_p=None, z_fake_noise=None):
+        fed = self._fed(x)
+        if fed is not None:
+            x = fed[0]
         eps, z_p, z_fake_noise = self._resolve_noise(x.shape[0], [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
                                                                   ("z_fake_noise", SID_ZFAKE, z_fake_noise)])
         noise = self._last_noise
