@@ -389,16 +389,21 @@ int fmri_mmd_imq(const float* q, int ldq, const float* p, int ldp, int n, int d,
                  int nscales, float w, float* total, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
                  void* stream);
 /* ---- the WAE latent discriminator (models/vae_gan.py:499-529: Linear(z,H) ReLU [Linear(H,H) ReLU] x 3 Linear(H,1),
- * sigmoid left to fmri_wae_logloss) as one launch forward and one for the backward chain (H = 512, Zp a multiple of 64
- * <= 256; anything else: FMRI_E_UNSUPPORTED, use fmri_igemm layer by layer).
+ * sigmoid left to fmri_wae_logloss) as one launch forward and one for the backward chain.  H = 512; Zp a multiple of
+ * 64, 64 <= Zp <= 512 for fmri_mlp_fwd and 64 <= Zp <= 256 for fmri_mlp_bwd; anything else: FMRI_E_UNSUPPORTED, nothing
+ * launched (use fmri_igemm layer by layer).  NULL w5[i] / hs4[i] / delta4[i], kp5[0] < Zp, kp5[i] / kpd4[i] < H, Z > Zp,
+ * ldl < 1, M < 1: FMRI_E_BADARG.
  * fmri_mlp_fwd: z16 [M][Zp] fp16; w5[i] = layer i's packed fp16 weights in the forward orientation ([rows_pad][kp5[i]],
  *   row = output feature: what fmri_pack_weight produces for fmri_igemm), bias5[i] fp32 (may be NULL); hs4[i] receives
  *   the hidden activations h_{i+1} [M][H] fp16 (the backward pass needs them), logit [M] fp32 the pre-sigmoid output.
+ *   hs4[i] and logit are written for rows [0, M) only: the four hs4 may be one [4][M][H] allocation.
  * fmri_mlp_bwd: dlogit16 [M][ldl] (column 0) -> delta4[i] = cotangent of the pre-activation of h_{i+1} ([M][H] fp16:
- *   the P operands of the layers' fmri_wgrad calls), dbias5[i] += inv_scale * column sums (NULL dbias5 or entry: skip),
- *   dz32 [M][Z] fp32 = inv_scale * (delta1 . W0) (NULL: skip).  w4row = row 0 of the output layer's forward-orientation
- *   matrix; wd4[i] = layer i's packed weights in the data-gradient orientation ([rows_pad][kpd4[i]], row = input
- *   feature); wd4[0] is read only when dz32 is given.  Replaces the autograd data path of
+ *   the P operands of the layers' fmri_wgrad calls; written for rows [0, M) only, as is dz32), dbias5[i] += inv_scale *
+ *   column sums (NULL dbias5 or entry: skip), dz32 [M][Z] fp32 = inv_scale * (delta1 . W0) (NULL: skip).  w4row = row 0
+ *   of the output layer's forward-orientation matrix; wd4[i] = layer i's packed weights in the data-gradient
+ *   orientation ([rows_pad][kpd4[i]], row = input feature); wd4[0] is read only when dz32 is given, and then its rows
+ *   [0, Zp) are read whatever Z is: it must have at least Zp rows (only columns [0, Z) of the product
+ *   are stored).  Replaces the autograd data path of
  *   train/train_wae_stage1.py:278-303.  Determinism: delta4 and dz32 are plain stores (bit-reproducible); the five
  *   dbias5 vectors are accumulated with fp32 atomics across the 32-row blocks, so their last bits depend on the
  *   arrival order of the blocks (run-to-run spread ~1e-7 relative; every other gradient of the engine is reduced in a

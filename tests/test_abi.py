@@ -106,6 +106,39 @@ def test_latent_range_scale_and_its_argument_checks(lib):
     assert L.fmri_sumsq_f64(z, 16, ctypes.c_void_p(12), 1, None) == -1                                      # misaligned double
 
 
+def test_fused_mlp_argument_checks(lib):
+    """fmri_mlp_fwd / fmri_mlp_bwd (include/fmri_hip.h) refuse bad arguments, and the widths their kernels do not cover,
+    on the host: nothing is launched.  The forward takes Zp up to 512, the backward up to 256."""
+    z = ctypes.c_void_p(16)
+    ptrs = lambda n, null=None: (ctypes.c_void_p * n)(*[None if i == null else 16 for i in range(n)])
+    ints = lambda *v: (ctypes.c_int * len(v))(*v)
+    kp, kpd = ints(128, 512, 512, 512, 512), ints(512, 512, 512, 512)
+
+    def fwd(M=8, Zp=128, H=512, w5=None, kp5=kp, hs4=None):
+        return lib.fmri_mlp_fwd(z, M, Zp, H, w5 or ptrs(5), kp5, ptrs(5), hs4 or ptrs(4), z, None)
+
+    def bwd(ldl=8, M=8, Zp=128, Z=128, H=512, hs4=None, wd4=None, kpd4=kpd, delta4=None, dz=z):
+        return lib.fmri_mlp_bwd(z, ldl, M, Zp, Z, H, hs4 or ptrs(4), z, wd4 or ptrs(4), kpd4, delta4 or ptrs(4), None, dz,
+                                1.0, None)
+    for i in range(5):
+        assert fwd(w5=ptrs(5, null=i)) == -1, i                     # NULL w5[i]
+    assert fwd(hs4=ptrs(4, null=2)) == -1
+    assert fwd(Zp=192) == -1                                          # kp5[0] < Zp
+    assert fwd(kp5=ints(128, 512, 448, 512, 512)) == -1               # kp5[i] < H
+    assert fwd(M=0) == -1 and bwd(M=0) == -1
+    assert bwd(Z=136) == -1                                           # Z > Zp
+    assert bwd(ldl=0) == -1
+    assert bwd(hs4=ptrs(4, null=0)) == -1 and bwd(delta4=ptrs(4, null=3)) == -1
+    assert bwd(wd4=ptrs(4, null=1)) == -1 and bwd(kpd4=ints(512, 512, 256, 512)) == -1
+    assert bwd(wd4=ptrs(4, null=0)) == -1                             # wd4[0] is needed for dz32 ...
+    # unsupported widths
+    big = ints(512, 512, 512, 512, 512)
+    assert fwd(Zp=100) == -2 and fwd(Zp=32) == -2 and fwd(Zp=576, kp5=ints(576, 512, 512, 512, 512)) == -2
+    assert fwd(H=256) == -2 and bwd(H=256) == -2
+    assert bwd(Zp=320, Z=320) == -2 and bwd(Zp=100, Z=100) == -2 and bwd(Zp=512, Z=512) == -2
+    assert fwd(Zp=100, kp5=big) == -2
+
+
 def _scanner():
     import importlib.util
     spec = importlib.util.spec_from_file_location("scan_store_hazard", os.path.join(ROOT, "tools", "scan_store_hazard.py"))
