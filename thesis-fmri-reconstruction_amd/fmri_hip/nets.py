@@ -134,8 +134,20 @@ class _Versioned:
         return self._g.version
 
 
+class _JoinedBackward:
+    """Mixin of the networks: the public ``backward`` around each network's ``_backward``."""
+
+    def backward(self, *args, join: bool = True, **kwargs):
+        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
+        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
+        out = self._backward(*args, **kwargs)
+        if join:
+            join_side()
+        return out
+
+
 # ------------------------------------------------------------------------------------------------
-class EncoderNet:
+class EncoderNet(_JoinedBackward):
     def __init__(self, cfg: ArchConfig, device, channel_in: int = 3):
         self.cfg = cfg
         self.group = FlatGroup(encoder_spec(cfg, channel_in), device)
@@ -183,14 +195,6 @@ class EncoderNet:
         head32 = self.heads.forward(hfc)
         return head32, dict(acts=acts, raws=raws, svs=svs, flat=flat, raw_fc=raw_fc, hfc=hfc, svfc=svfc)
 
-    def backward(self, *args, join: bool = True, **kwargs):
-        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
-        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
-        out = self._backward(*args, **kwargs)
-        if join:
-            join_side()
-        return out
-
     def _backward(self, ctx, dhead16: torch.Tensor, scale: float, after_fc=None, after_fc_join: bool = True):
         """Accumulate encoder parameter gradients of (1/scale)*<dhead16, head>.  ``after_fc`` is called once the
         gradients of fc.0 / fc.1 / l_mu / l_var -- the tail of the flat buffer from ``fc.0.weight`` on, 93 % of its
@@ -221,7 +225,7 @@ class EncoderNet:
             self.convs[i].wgrad(ctx["acts"][i], draw, scale)
 
 
-class CognitiveEncoderNet:
+class CognitiveEncoderNet(_JoinedBackward):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device):
         self.cfg, self.n_voxels = cfg, n_voxels
         self.group = FlatGroup(cognitive_encoder_spec(cfg, n_voxels), device)
@@ -239,14 +243,6 @@ class CognitiveEncoderNet:
         h, sv = self.fc1_bn.forward(raw, relu=True, updates=upd)
         return self.heads.forward(h), dict(x=fmri16, raw=raw, h=h, sv=sv)
 
-    def backward(self, *args, join: bool = True, **kwargs):
-        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
-        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
-        out = self._backward(*args, **kwargs)
-        if join:
-            join_side()
-        return out
-
     def _backward(self, ctx, dhead16, scale):
         dh = self.heads.backward(ctx["h"], dhead16, scale)
         draw, _ = self.fc1_bn.backward(ctx["raw"], dh, ctx["sv"], True, scale)
@@ -254,7 +250,7 @@ class CognitiveEncoderNet:
 
 
 # ------------------------------------------------------------------------------------------------
-class DecoderNet:
+class DecoderNet(_JoinedBackward):
     def __init__(self, cfg: ArchConfig, device, size: Optional[int] = None):
         self.cfg = cfg
         size = cfg.encoder_channels[2] if size is None else size
@@ -316,14 +312,6 @@ class DecoderNet:
         y = self.c3.forward(h, ACT_TANH, out=out)
         return y, dict(z=z16, raw_fc=raw_fc, sv_fc=sv_fc, acts=acts, raws=raws, svs=svs, y=y, B=B, groups=groups,
                        zscale=zscale)
-
-    def backward(self, *args, join: bool = True, **kwargs):
-        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
-        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
-        out = self._backward(*args, **kwargs)
-        if join:
-            join_side()
-        return out
 
     def _backward(self, ctx, cot: torch.Tensor, entries: List[dict]):
         """cot [E*B,H,W,8] fp16 stacks E cotangent blocks w.r.t. the decoder output; entries[e] =
@@ -423,7 +411,7 @@ class DecoderNet:
 
 
 # ------------------------------------------------------------------------------------------------
-class DiscriminatorNet:
+class DiscriminatorNet(_JoinedBackward):
     def __init__(self, cfg: ArchConfig, device, recon_level: int = 3):
         # models/vae_gan.py:139-173: the 'REC' output is the RAW convolution output of block ``recon_level``.  Block 0 is
         # an nn.Sequential, which does not take the reference's ``lay(ten, True)`` call (TypeError), and a level past
@@ -503,14 +491,6 @@ class DiscriminatorNet:
         for bn, sv in zip(self.bns, ctx["svs"]):
             if sv is not None:
                 bn.update_running_again(sv, updates)
-
-    def backward(self, *args, join: bool = True, **kwargs):
-        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
-        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
-        out = self._backward(*args, **kwargs)
-        if join:
-            join_side()
-        return out
 
     def _backward(self, ctx, dlogit16: Optional[torch.Tensor], scale_a: float, dfeat16: Optional[torch.Tensor],
                  scale_b: float, train: bool, img_rows: Optional[slice], img_streams=(True, True),
@@ -646,7 +626,7 @@ class DiscriminatorNet:
 
 
 # ------------------------------------------------------------------------------------------------
-class WaeDiscriminatorNet:
+class WaeDiscriminatorNet(_JoinedBackward):
     """Latent-space discriminator MLP z -> 512 -> 512 -> 512 -> 512 -> 1 (models/vae_gan.py:499-529)."""
 
     def __init__(self, cfg: ArchConfig, device, dim_h: int = 512):
@@ -693,14 +673,6 @@ class WaeDiscriminatorNet:
             hs.append(h)
         _, logit32 = self.layers[-1].forward(h, ACT_NONE, want16=False, want32=True)
         return logit32, dict(hs=hs)
-
-    def backward(self, *args, join: bool = True, **kwargs):
-        """``_backward`` + join of the side stream its weight gradients were issued on (ops.side_run).  ``join=False``
-        leaves them in flight (the caller joins with ops.join_side() before the gradients are read)."""
-        out = self._backward(*args, **kwargs)
-        if join:
-            join_side()
-        return out
 
     def _backward(self, ctx, dlogit16, scale, train: bool, need_dz: bool):
         if ctx.get("fused"):

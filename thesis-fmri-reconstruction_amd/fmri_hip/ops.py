@@ -1261,49 +1261,7 @@ class BatchNorm:
         ``phase`` 1 = the reduction only (into ``sums``, a caller-owned [2][C] view), 2 = the apply pass only (``sums``
         already exchanged), 3 = both with this call's own SyncBN exchange in between: a caller with several calls that are
         ready together (the decoder's call groups of one layer) runs all phase-1 calls, ONE exchange, all phase-2 calls."""
-        C = self.C
-        x2 = raw.reshape(-1, C)
-        g2 = dy.reshape(-1, C)
-        M = x2.shape[0]
-        gamma, beta, _, _ = self._params()
-        if sums is None:
-            sums = torch.empty(2, C, dtype=torch.float32, device=raw.device)
-        # gamma/beta gradients come from the LOCAL sums (the SUM all-reduce of the gradients adds the other ranks); the
-        # fold kernel of the reduction accumulates them, the permuted (C,H,W)-ordered BN1d needs the scatter kernel
-        direct = param_scale is not None and not self.perm
-        if phase == 3 and stat is None and self.reducer is None and M <= _BN_COLS_ROWS:
-            # few rows: reduction, parameter gradients and dx in ONE launch
-            if out is None:
-                out = torch.empty_like(dy)
-            lib.note(bytes=10.0 * M * C)
-            self._call_counted("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 1, sv.count, _P(sv.mean), _P(sv.rstd),
-                               _P(gamma), _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if direct else None,
-                               _P(self.ggamma) if direct else None, (1.0 / param_scale) if direct else 0.0, 0)
-            if param_scale is not None and self.perm:
-                self.accumulate_param_grads(sums, param_scale)
-            return out, sums
-        if phase & 1:
-            if stat is not None:
-                assert not self.perm
-                self._fold_bwd(stat, stat_group, 1, sums, param_scale, 0)
-            else:
-                ws = _reduce_ws(M, C, raw.device)
-                lib.note(bytes=4.0 * M * C)
-                lib.call("fmri_bn_bwd_reduce", _P(x2), _P(g2), M, C, _P(sv.mean), _P(sv.rstd), _P(gamma), _P(beta),
-                         1 if relu else 0, _P(sums), _P(ws), ws.numel(), _P(self.gbeta) if direct else None,
-                         _P(self.ggamma) if direct else None, (1.0 / param_scale) if direct else 0.0)
-            if param_scale is not None and self.perm:
-                self.accumulate_param_grads(sums, param_scale)
-        if phase == 3 and self.reducer is not None:
-            self.reducer(sums)
-        if not phase & 2:
-            return None, sums
-        if out is None:
-            out = torch.empty_like(dy)
-        lib.note(bytes=6.0 * M * C)
-        self._call_counted("fmri_bn_bwd_apply", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd),
-                           _P(gamma), _P(beta), 1 if relu else 0, _P(sums))
-        return out, sums
+        return self._backward(1, raw, dy, sv, relu, param_scale, out, 0, stat, stat_group, sums, phase)
 
     def backward2(self, raw: torch.Tensor, dy2: torch.Tensor, sv: BNSaved, relu: bool = True,
                   param_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, param_stream: int = 0,
@@ -1312,46 +1270,58 @@ class BatchNorm:
         as ``raw``): the forward tensor, xhat and the ReLU mask are read / computed once for both.  gamma / beta
         gradients (``param_scale``) are taken from ONE stream (``param_stream``: 0 = A, 1 = B).  ``sums`` ([4][C]) /
         ``phase``: as in ``backward``."""
+        return self._backward(2, raw, dy2, sv, relu, param_scale, out, int(param_stream), stat, stat_group, sums, phase)
+
+    def _backward(self, n: int, raw, dy, sv: BNSaved, relu, param_scale, out, param_stream: int, stat, stat_group,
+                  sums, phase):
+        """``backward`` (n = 1) / ``backward2`` (n = 2): ``dy`` stacks n cotangent streams of M rows each, ``sums`` is
+        [2n][C] (rows 2s, 2s+1 of stream s), the two-stream kernels carry the suffix "2" and take ``param_stream``."""
         C = self.C
         x2 = raw.reshape(-1, C)
-        g2 = dy2.reshape(-1, C)
+        g2 = dy.reshape(-1, C)
         M = x2.shape[0]
-        assert g2.shape[0] == 2 * M
+        assert n == 1 or g2.shape[0] == 2 * M
+        two = ("", "2")[n - 1]
+        which = (param_stream,) * (n - 1)       # trailing argument of the two-stream reduction
         gamma, beta, _, _ = self._params()
         if sums is None:
-            sums = torch.empty(4, C, dtype=torch.float32, device=raw.device)
-        pg = param_scale is not None and not self.perm     # (C,H,W)-permuted BN1d: scattered below
+            sums = torch.empty(2 * n, C, dtype=torch.float32, device=raw.device)
+        # gamma/beta gradients come from the LOCAL sums (the SUM all-reduce of the gradients adds the other ranks); the
+        # fold kernel of the reduction accumulates them, the permuted (C,H,W)-ordered BN1d needs the scatter kernel
+        direct = param_scale is not None and not self.perm
+        pgrads = (_P(self.gbeta) if direct else None, _P(self.ggamma) if direct else None,
+                  (1.0 / param_scale) if direct else 0.0)
+        scatter = param_scale is not None and self.perm
         if phase == 3 and stat is None and self.reducer is None and M <= _BN_COLS_ROWS:
+            # few rows: reduction, parameter gradients and dx in ONE launch
             if out is None:
-                out = torch.empty_like(dy2)
-            lib.note(bytes=16.0 * M * C)
-            self._call_counted("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, 2, sv.count, _P(sv.mean), _P(sv.rstd),
-                               _P(gamma), _P(beta), 1 if relu else 0, _P(sums), _P(self.gbeta) if pg else None,
-                               _P(self.ggamma) if pg else None, (1.0 / param_scale) if pg else 0.0, int(param_stream))
-            if param_scale is not None and self.perm:
-                self.accumulate_param_grads(sums[2 * int(param_stream):2 * int(param_stream) + 2], param_scale)
+                out = torch.empty_like(dy)
+            lib.note(bytes=(10.0, 16.0)[n - 1] * M * C)
+            self._call_counted("fmri_bn_cols_bwd", _P(x2), _P(g2), _P(out), M, C, n, sv.count, _P(sv.mean), _P(sv.rstd),
+                               _P(gamma), _P(beta), 1 if relu else 0, _P(sums), *pgrads, param_stream)
+            if scatter:
+                self.accumulate_param_grads(sums[2 * param_stream:2 * param_stream + 2], param_scale)
             return out, sums
         if phase & 1:
             if stat is not None:
-                # groups stat_group, stat_group + 1 of the producing data gradient's epilogue rows (dy2 is ReLU-masked)
+                # groups stat_group .. stat_group + n - 1 of the producing data gradient's epilogue rows
                 assert not self.perm
-                self._fold_bwd(stat, stat_group, 2, sums, param_scale, int(param_stream))
+                self._fold_bwd(stat, stat_group, n, sums, param_scale, param_stream)
             else:
-                ws = torch.empty(2 * lib.load().fmri_bn_ws_floats(M, C), dtype=torch.float32, device=raw.device)
-                lib.note(bytes=6.0 * M * C)
-                lib.call("fmri_bn_bwd_reduce2", _P(x2), _P(g2), M, C, _P(sv.mean), _P(sv.rstd), _P(gamma), _P(beta),
-                         1 if relu else 0, _P(sums), _P(ws), ws.numel(), _P(self.gbeta) if pg else None,
-                         _P(self.ggamma) if pg else None, (1.0 / param_scale) if pg else 0.0, int(param_stream))
-            if param_scale is not None and self.perm:
-                self.accumulate_param_grads(sums[2 * int(param_stream):2 * int(param_stream) + 2], param_scale)
+                ws = torch.empty(n * lib.load().fmri_bn_ws_floats(M, C), dtype=torch.float32, device=raw.device)
+                lib.note(bytes=(4.0, 6.0)[n - 1] * M * C)
+                lib.call("fmri_bn_bwd_reduce" + two, _P(x2), _P(g2), M, C, _P(sv.mean), _P(sv.rstd), _P(gamma),
+                         _P(beta), 1 if relu else 0, _P(sums), _P(ws), ws.numel(), *pgrads, *which)
+            if scatter:
+                self.accumulate_param_grads(sums[2 * param_stream:2 * param_stream + 2], param_scale)
         if phase == 3 and self.reducer is not None:
             self.reducer(sums)
         if not phase & 2:
             return None, sums
         if out is None:
-            out = torch.empty_like(dy2)
-        lib.note(bytes=10.0 * M * C)
-        self._call_counted("fmri_bn_bwd_apply2", _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd),
+            out = torch.empty_like(dy)
+        lib.note(bytes=(6.0, 10.0)[n - 1] * M * C)
+        self._call_counted("fmri_bn_bwd_apply" + two, _P(x2), _P(g2), _P(out), M, C, sv.count, _P(sv.mean), _P(sv.rstd),
                            _P(gamma), _P(beta), 1 if relu else 0, _P(sums))
         return out, sums
 

@@ -1,0 +1,395 @@
+"""What every fused step is built on (steps.py, wae_steps.py): the fused optimizers, the data-parallel glue with its
+graph-segment recorder, and ``_StepBase`` -- scalar block, device RNG and feed, noise resolution, the unit-RMS
+re-normalisation of the encoder cotangent, HIP-graph capture and replay.  Nothing here knows a loss."""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional
+
+import torch
+
+from . import lib, ops
+from .monitor import Monitored
+from .rng import DeviceRng, StepNoise
+
+_P = lib.ptr
+
+# slots of the fp32 scalar block (csrc/loss.hip enum Slot)
+(S_BCE_O, S_BCE_P, S_BCE_S, S_KL, S_MSE, S_NLE, S_LENC, S_LDIS, S_LDEC, S_DL2, S_NA, S_NB, S_RATIO,
+ S_ONE, S_ESQ, S_NE, S_NP, S_C1, S_C2, S_C3, S_GDEC, S_KLW) = range(22)
+S_ZMAX = 22         # slots [22, 26): max |z| of the latent batch of decoder group 0..3 (ops.latent_ranged; zero at step start)
+
+
+class _Optim:
+    """Fused RMSprop / Adam over a FlatGroup, optionally gated by a device flag; ``gdev`` is the device
+    normalisation factor still carried by the gradients (divided out inside the kernel).  The learning rate (and
+    Adam's step count) live in device memory: ``set_lr`` -- the per-epoch ExponentialLR / StepLR of the scripts
+    (train_vgan_stage1.py:448-450) -- reaches a step that was recorded into a HIP graph."""
+
+    def __init__(self, group, kind="rmsprop", lr=1e-4, alpha=0.9, eps=1e-8, betas=(0.5, 0.999)):
+        self.g, self.kind, self.alpha, self.eps, self.betas = group, kind, alpha, eps, betas
+        self.s1 = torch.zeros_like(group.data)
+        self.s2 = torch.zeros_like(group.data) if kind == "adam" else None
+        self.t = 0
+        self._lr = float(lr)
+        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=group.device)
+        self.t_dev = torch.zeros(1, dtype=torch.int32, device=group.device) if kind == "adam" else None
+        self.stats = None        # (monitor.Monitor, device address of its record pair): set by a monitored step
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    def set_lr(self, lr: float):
+        self._lr = float(lr)
+        self.lr_dev.fill_(float(lr))
+
+    def step(self, flag: Optional[torch.Tensor] = None, clamp: float = 0.0, gdev: Optional[torch.Tensor] = None):
+        g = self.g
+        mon, rec = self.stats if self.stats is not None else (None, None)
+        if self.kind == "rmsprop" and ops.apply_group(g, self.s1, self.lr_dev, self.alpha, self.eps, flag, gdev, clamp,
+                                                      stats=rec):
+            return                               # deferred gradients: update + fp16 copies in one launch (ops.begin_grads)
+        if self.kind != "rmsprop":
+            ops.flush_pending(g)                 # (Adam has no fused form: deferred gradients -> reference layout)
+        if mon is not None:
+            mon.grad_stats(g.grad, gdev, clamp, flag, rec)
+        if self.kind == "rmsprop":
+            lib.note(bytes=20.0 * g.numel)       # read p, g, v; write p, v
+            lib.call("fmri_rmsprop_dev", _P(g.data), _P(g.grad), _P(self.s1), g.numel, _P(self.lr_dev), self.alpha,
+                     self.eps, 1.0, _P(gdev), clamp, _P(flag))
+        else:
+            self.t += 1
+            b1, b2 = self.betas
+            lib.call("fmri_counter_inc", _P(self.t_dev))
+            lib.note(bytes=28.0 * g.numel)       # read p, g, m, v; write p, m, v
+            lib.call("fmri_adam_dev", _P(g.data), _P(g.grad), _P(self.s1), _P(self.s2), g.numel, _P(self.lr_dev), b1, b2,
+                     self.eps, _P(self.t_dev), 1.0, _P(gdev), clamp, _P(flag))
+        if mon is not None:
+            mon.param_stats(g.data, flag, rec)
+        g.version += 1
+
+
+class _SegmentRecorder:
+    """Records a step as an alternating list of HIP graphs and eagerly issued collectives.
+
+    Collectives stay outside the graphs (they are issued exactly as in the eager step, RCCL sees nothing new); every
+    run of kernel launches between two collectives becomes one graph.  A data-parallel step is then ~37 graph launches
+    + 36 collective calls on the host instead of ~400 kernel launches."""
+
+    def __init__(self):
+        self.pool = torch.cuda.graph_pool_handle()
+        self.items = []          # torch.cuda.CUDAGraph or a zero-argument callable
+        self.cur = None
+        # The collectives run on a stream of their own, never on the one being recorded: the backend records its work
+        # events on the stream a blocking collective is issued from, its watchdog THREAD polls them, and HIP refuses to
+        # query an event whose stream has meanwhile entered capture (hipErrorCapturedEvent) -- the watchdog then
+        # takes the process down (seen once in ~6 runs of the one-rank RCCL test, at the capture that follows a
+        # SyncBN exchange).
+        self.comm = torch.cuda.Stream()
+
+    def _on_comm(self, fn):
+        cur = torch.cuda.current_stream()
+        self.comm.wait_stream(cur)
+        with torch.cuda.stream(self.comm):
+            fn()
+        cur.wait_stream(self.comm)
+
+    def begin(self):
+        self.cur = torch.cuda.CUDAGraph()
+        self.cur.capture_begin(pool=self.pool, capture_error_mode="thread_local")
+
+    def end(self):
+        ops.join_side()          # a capture cannot end with forked side-stream work (weight gradients) un-joined
+        self.cur.capture_end()
+        self.items.append(self.cur)
+        self.cur = None
+
+    def collective(self, fn):
+        self.end()
+        run = lambda: self._on_comm(fn)
+        run()                    # communicator warm, same call order as at replay; operates on not-yet-computed data
+        self.items.append(run)
+        self.begin()
+
+    def replay(self):
+        for it in self.items:
+            if isinstance(it, torch.cuda.CUDAGraph):
+                it.replay()
+            else:
+                it()
+
+
+_SMALL_GROUP = {}
+
+
+def _small_group(dist):
+    """The second communicator (small messages), created once per process and default group -- not once per step object."""
+    key = id(dist.group.WORLD)
+    if key not in _SMALL_GROUP:
+        _SMALL_GROUP.clear()
+        _SMALL_GROUP[key] = dist.new_group()
+    return _SMALL_GROUP[key]
+
+
+class _Dist:
+    """Data-parallel glue (one process per GPU, RCCL): SUM all-reduce of flat gradients / loss scalars and
+    the SyncBN statistic exchange.  Inactive (world size 1) unless torch.distributed is initialised."""
+
+    def __init__(self, enabled: bool, sync_bn: bool = True):
+        import torch.distributed as dist
+        self.dist = dist
+        # FMRI_FORCE_DIST=1: take the collective path even with one rank (single-GPU rehearsal of the RCCL calls)
+        force = os.environ.get("FMRI_FORCE_DIST") == "1"
+        self.on = enabled and dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or force)
+        self.world = dist.get_world_size() if self.on else 1
+        self.sync_bn = sync_bn
+        self.pending = []
+        # A communicator of its own for the SMALL collectives of the main stream (loss scalars, the stream-norm scalar,
+        # SyncBN sums).  Collectives of one communicator run in issue order on its stream: behind a 44 MB gradient
+        # all-reduce that is itself waiting for the side stream's weight gradients, a 40-byte all-reduce of the main
+        # stream would stall the whole backward pass (head-of-line blocking); on a second communicator it does not.
+        # FMRI_SMALL_COMM=off: everything on the default communicator (collectives then run in issue order, the order of
+        # the program on every rank) -- the fallback should two communicators driven from two streams ever misbehave on a
+        # real multi-GPU node; costs the head-of-line blocking described above
+        self.small = _small_group(dist) if (self.on and os.environ.get("FMRI_SMALL_COMM") != "off") else None
+        self.recorder: Optional[_SegmentRecorder] = None     # set while a step is recorded into graph segments
+
+    SMALL = 1 << 16          # elements: at most this many go through the small-message communicator
+
+    def all_reduce(self, t: torch.Tensor):
+        """Blocking SUM all-reduce on the CURRENT stream (the host does not wait): scalars / statistics on the
+        small-message communicator, gradient buffers on the default one."""
+        if not self.on:
+            return
+        grp = self.small if t.numel() <= self.SMALL else None
+        if self.recorder is not None:
+            self.recorder.collective(lambda: self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=grp))
+        else:
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=grp)
+
+    def all_reduce_max(self, t: torch.Tensor):
+        """Blocking MAX all-reduce of a few scalars on the current stream (the latent range of a SyncBN step)."""
+        if not self.on:
+            return
+        fn = lambda: self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.small)
+        if self.recorder is not None:
+            self.recorder.collective(fn)
+        else:
+            fn()
+
+    def all_reduce_async(self, t: torch.Tensor):
+        """Start a SUM all-reduce (same communicator, so it queues behind / ahead of the blocking ones in program
+        order on every rank) and return immediately; `wait_all` joins it with the compute stream."""
+        if not self.on:
+            return
+
+        def issue():
+            self.pending.append(self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, async_op=True))
+        if self.recorder is not None:
+            self.recorder.collective(issue)
+        else:
+            issue()
+
+    def wait_all(self):
+        if not self.on:
+            return
+
+        def join():
+            for h in self.pending:
+                h.wait()
+            self.pending.clear()
+        if self.recorder is not None:
+            self.recorder.collective(join)
+        else:
+            join()
+
+    def bn_reducer(self):
+        if not (self.on and self.sync_bn):
+            return None
+
+        def red(sums):
+            self.all_reduce(sums)
+            return self.world
+        return red
+
+
+def _attach_reducers(nets, d: _Dist):
+    r = d.bn_reducer()
+    for n in nets:
+        for bn in n.all_bns():
+            bn.reducer = r
+
+
+class _StepBase(Monitored):
+    """What every step uses; a subclass sets ``cfg``, builds its networks, calls ``_init_step`` and ``_init_rng``,
+    registers its optimizers in ``optims`` and defines ``step``."""
+
+    def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
+        self.device = torch.device(device)
+        self.scal = torch.zeros(32, dtype=torch.float32, device=device)
+        self.esq64 = torch.zeros(1, dtype=torch.float64, device=device)      # sum of squares of _renorm
+        self.dd = _Dist(distributed, sync_bn)
+        _attach_reducers(nets, self.dd)
+        self.fw: Dict[str, object] = {}
+        self.optims: List[_Optim] = []       # in the order encoder, decoder, discriminator(, latent discriminator)
+        self._pre_replay = []                # zero-argument hooks run before every replay of a recorded step
+
+    def _init_rng(self, rng: Optional[DeviceRng], feed=None):
+        self.rng = rng
+        self._noise = StepNoise(rng) if rng is not None else None
+        self._last_noise: Dict[str, torch.Tensor] = {}
+        self.feed = feed             # fmri_hip.feed.DeviceFeed or None
+        self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
+
+    def _fed(self, *given):
+        """The batch of a step.  Without a feed: ``given`` (the caller's batch tensors) must all be there; returns None.
+        With a feed: none may be; the feed enqueues its next batch (fmri_hip/feed.py) -- the first launches of the step,
+        so they sit in the one graph of a recording, or in the first segment of a data-parallel one -- and its buffers
+        (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
+        generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
+        the noise and the augmentation draws."""
+        feed = self.feed
+        if feed is None:
+            if any(g is None for g in given):
+                raise ValueError(f"{type(self).__name__}: no batch given and the step has no feed (pass the batch, or "
+                                 "construct the step with feed=DeviceFeed(...))")
+            return None
+        if any(g is not None for g in given):
+            raise ValueError(f"{type(self).__name__}: the step has a feed and draws its own batch: step() takes no "
+                             "batch arguments")
+        shared = feed.rng is not None and feed.rng is self.rng
+        x, fm, _ = feed.next(advance_rng=not shared)
+        self._feed_blocks = feed.rng_blocks() if shared else 0
+        return x, fm, feed.fmri16
+
+    def _feed_advance(self):
+        """The shared generator's advance for a step that drew no noise after its feed drew augmentation."""
+        if self._feed_blocks:
+            self.rng.advance(self._feed_blocks)
+            self._feed_blocks = 0
+
+    def _resolve_noise(self, B: int, wanted):
+        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
+        the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
+        [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
+        draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
+        the same generator in this step, if that is larger.  Returns the tensors in the order asked for."""
+        missing = [name for name, _, t in wanted if t is None]
+        if missing and self._noise is None:
+            raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
+                             "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
+        Z = self.cfg.latent_dim
+        dd = self.dd
+        rank = dd.dist.get_rank() if dd.on else 0
+        if missing:
+            self._noise.begin()
+        out = {}
+        for name, sid, t in wanted:
+            out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
+        if missing:
+            self._noise.end(B * dd.world, Z, at_least=self._feed_blocks)
+            self._feed_blocks = 0
+        else:
+            self._feed_advance()
+        self._last_noise = out
+        return list(out.values())
+
+    def last_noise(self) -> Dict[str, torch.Tensor]:
+        """The noise tensors the last step used, by argument name in the order ``step`` takes them (the step's own
+        buffers where it drew them: clone what has to outlive the next step)."""
+        return dict(self._last_noise)
+
+    def _reduce_async(self, group, part=None):
+        """Data parallel: the sub-network's deferred weight gradients -> reference layout (one launch), then the
+        asynchronous SUM all-reduce of the gradient buffer (or of ``part`` of it).  Nothing on one GPU: the gradients
+        stay deferred until the update (ops.apply_group)."""
+        if self.dd.on:
+            ops.materialize_grads(group)
+            self.dd.all_reduce_async(group.grad if part is None else part)
+
+    def _slot(self, i):
+        return self.scal[i:i + 1]
+
+    def _renorm(self, x32: torch.Tensor, scale: float, factor_in, rows_global: int):
+        """fp32 cotangent -> unit-RMS fp16 (times ``scale``); S_NE <- (*factor_in) / rms (``factor_in`` None: 1 / rms).
+        The sum of squares is all-reduced so that every data-parallel rank applies the same factor."""
+        n = x32.numel()
+        # the sum of squares in double precision (the KL term's 0.5 * (exp(logvar) - 1), squared, leaves fp32 at
+        # logvar > 44), cleared by the launch itself: a second backward() after one gate() starts from zero as well
+        esq = self.esq64
+        lib.call("fmri_sumsq_f64", _P(x32), n, _P(esq), 1)
+        self.dd.all_reduce(esq)
+        out = torch.empty(x32.shape, dtype=torch.float16, device=x32.device)
+        count = float(rows_global) * (n // x32.shape[0])
+        lib.call("fmri_renorm_f64", _P(x32), _P(out), n, float(scale), _P(esq), count, _P(factor_in),
+                 _P(self._slot(S_NE)))
+        return out
+
+    def capture(self, *static_inputs, warmup: int = 2):
+        """Record one ``step(*static_inputs)`` into a HIP graph and return a zero-argument callable that replays it.
+
+        Every launch of a step is enqueue-only and nothing inside a step synchronises with the host (the equilibrium
+        gate, the stream normalisation and the optimizer gating all live on the device), so the ~370 launches of a
+        step can be replayed as one graph: the step time then no longer depends on how fast the host can issue them.
+        Inputs are read from ``static_inputs`` at every replay -- copy each new batch into those tensors.  Learning
+        rates, lambda, margin, equilibrium and beta are device-resident (``set_lr`` / ``set_hyper``): a replayed step follows
+        their schedules (Adam's step count of the WAE steps lives on the device too, ``wae_steps``).  In a data-parallel run the collectives
+        are kept out of the graphs (see _SegmentRecorder)."""
+        # The weight-gradient side stream (ops.side_run) is switched off while recording: a replayed HIP graph runs
+        # its parallel branches no faster than a chain (measured 8.8 ms chained, 9.0-9.5 ms with the fork/join
+        # branches, 8.4 ms eager with two streams), so the recorded step keeps everything on one stream.
+        side_was = ops._SIDE["on"]
+        ops.join_side()
+        ops._SIDE["on"] = False
+        try:
+            return self._capture(static_inputs, warmup)
+        finally:
+            ops._SIDE["on"] = side_was
+
+    def _capture(self, static_inputs, warmup):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self.step(*static_inputs)
+        torch.cuda.current_stream().wait_stream(side)
+        if self.dd.on:
+            # data-parallel: the collectives stay eager, the launches between them become graphs
+            rec = _SegmentRecorder()
+            self.dd.recorder = rec
+            try:
+                with torch.cuda.stream(side):
+                    rec.begin()
+                    self.step(*static_inputs)
+                    rec.end()
+            except BaseException:
+                if rec.cur is not None:          # leave no stream capture open behind a failed recording
+                    try:
+                        rec.cur.capture_end()
+                    except Exception:
+                        pass
+                raise
+            finally:
+                self.dd.recorder = None
+            torch.cuda.current_stream().wait_stream(side)
+            self._graph = rec
+            return self._versioned(rec.replay)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.step(*static_inputs)
+        self._graph = graph
+        return self._versioned(graph.replay)
+
+    def _versioned(self, replay):
+        """A replay updates the master weights without passing through ``_Optim.step``: bump the groups' version
+        counters so that the first eager step afterwards re-packs its fp16 weights."""
+        groups = [o.g for o in self.optims]
+
+        def run():
+            for h in self._pre_replay:
+                h()
+            replay()
+            for g in groups:
+                g.version += 1
+        return run

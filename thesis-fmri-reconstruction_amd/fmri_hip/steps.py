@@ -3,7 +3,8 @@
     Stage1Step   train/train_vgan_stage1.py:316-432   (mode 'vae-gan')
     Stage2Step   train/train_vgan_stage2.py:321-407
     Stage3Step   train/train_vgan_stage3.py:324-411
-    (WAE Stage I/II/III and the Dual WAE+VAE/GAN step live in wae_steps.py)
+    (WAE Stage I/II/III and the Dual WAE+VAE/GAN step live in wae_steps.py; what every step is built on -- the
+     optimizers, the data-parallel glue and its graph-segment recorder, noise / feed / capture -- in step_base.py)
 
 Contract: one forward -> the three gradient sets, each of its own loss w.r.t. its own
 sub-network, all evaluated at the pre-update weights -> gated optimizer steps.  The discriminator is run
@@ -16,27 +17,24 @@ kernels divide out again.
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import lib, ops
-from .monitor import Monitored
 from .nets import (CognitiveEncoderNet, DecoderNet, DiscriminatorNet, EncoderNet, WaeDiscriminatorNet,
                    refresh_net)
 from .ops import axpby, images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
-from .rng import SID_EPS, SID_EPS_TEACHER, SID_ZP, DeviceRng, StepNoise
+from .rng import SID_EPS, SID_EPS_TEACHER, SID_ZP, DeviceRng
+from .step_base import (S_BCE_O, S_BCE_P, S_BCE_S, S_KL, S_MSE, S_NLE, S_LENC, S_LDIS, S_LDEC, S_DL2, S_NA, S_NB,  # noqa: F401
+                        S_RATIO, S_ONE, S_ESQ, S_NE, S_NP, S_C1, S_C2, S_C3, S_GDEC, S_KLW, S_ZMAX, _attach_reducers,
+                        _Dist, _Optim, _SegmentRecorder, _small_group, _SMALL_GROUP, _StepBase)
 
 _P = lib.ptr
 
-# slots of the fp32 scalar block (csrc/loss.hip enum Slot)
-(S_BCE_O, S_BCE_P, S_BCE_S, S_KL, S_MSE, S_NLE, S_LENC, S_LDIS, S_LDEC, S_DL2, S_NA, S_NB, S_RATIO,
- S_ONE, S_ESQ, S_NE, S_NP, S_C1, S_C2, S_C3, S_GDEC, S_KLW) = range(22)
-S_ZMAX = 22         # slots [22, 26): max |z| of the latent batch of decoder group 0..3 (ops.latent_ranged; zero at step start)
 # loss compositions of train/train_vgan_stage1.py:359-388 (csrc/loss.hip enum Mode)
 MODES = {"vae-gan": 0, "beta-vae": 1, "dcgan": 2, "vae": 3}
 N_REDUCED = 10      # slots [0, N_REDUCED) are sums over the batch -> all-reduced in data-parallel runs
@@ -67,217 +65,16 @@ class Scales:
     p: float = 16.0        # d nle / d x_tilde through the decoder (mode 'vae'; carries norm nP)
 
 
-class _Optim:
-    """Fused RMSprop / Adam over a FlatGroup, optionally gated by a device flag; ``gdev`` is the device
-    normalisation factor still carried by the gradients (divided out inside the kernel).  The learning rate (and
-    Adam's step count) live in device memory: ``set_lr`` -- the per-epoch ExponentialLR / StepLR of the scripts
-    (train_vgan_stage1.py:448-450) -- reaches a step that was recorded into a HIP graph."""
-
-    def __init__(self, group, kind="rmsprop", lr=1e-4, alpha=0.9, eps=1e-8, betas=(0.5, 0.999)):
-        self.g, self.kind, self.alpha, self.eps, self.betas = group, kind, alpha, eps, betas
-        self.s1 = torch.zeros_like(group.data)
-        self.s2 = torch.zeros_like(group.data) if kind == "adam" else None
-        self.t = 0
-        self._lr = float(lr)
-        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=group.device)
-        self.t_dev = torch.zeros(1, dtype=torch.int32, device=group.device) if kind == "adam" else None
-        self.stats = None        # (monitor.Monitor, device address of its record pair): set by a monitored step
-
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    def set_lr(self, lr: float):
-        self._lr = float(lr)
-        self.lr_dev.fill_(float(lr))
-
-    def step(self, flag: Optional[torch.Tensor] = None, clamp: float = 0.0, gdev: Optional[torch.Tensor] = None):
-        g = self.g
-        mon, rec = self.stats if self.stats is not None else (None, None)
-        if self.kind == "rmsprop" and ops.apply_group(g, self.s1, self.lr_dev, self.alpha, self.eps, flag, gdev, clamp,
-                                                      stats=rec):
-            return                               # deferred gradients: update + fp16 copies in one launch (ops.begin_grads)
-        if self.kind != "rmsprop":
-            ops.flush_pending(g)                 # (Adam has no fused form: deferred gradients -> reference layout)
-        if mon is not None:
-            mon.grad_stats(g.grad, gdev, clamp, flag, rec)
-        if self.kind == "rmsprop":
-            lib.note(bytes=20.0 * g.numel)       # read p, g, v; write p, v
-            lib.call("fmri_rmsprop_dev", _P(g.data), _P(g.grad), _P(self.s1), g.numel, _P(self.lr_dev), self.alpha,
-                     self.eps, 1.0, _P(gdev), clamp, _P(flag))
-        else:
-            self.t += 1
-            b1, b2 = self.betas
-            lib.call("fmri_counter_inc", _P(self.t_dev))
-            lib.note(bytes=28.0 * g.numel)       # read p, g, m, v; write p, m, v
-            lib.call("fmri_adam_dev", _P(g.data), _P(g.grad), _P(self.s1), _P(self.s2), g.numel, _P(self.lr_dev), b1, b2,
-                     self.eps, _P(self.t_dev), 1.0, _P(gdev), clamp, _P(flag))
-        if mon is not None:
-            mon.param_stats(g.data, flag, rec)
-        g.version += 1
-
-
-class _SegmentRecorder:
-    """Records a step as an alternating list of HIP graphs and eagerly issued collectives.
-
-    Collectives stay outside the graphs (they are issued exactly as in the eager step, RCCL sees nothing new); every
-    run of kernel launches between two collectives becomes one graph.  A data-parallel step is then ~37 graph launches
-    + 36 collective calls on the host instead of ~400 kernel launches."""
-
-    def __init__(self):
-        self.pool = torch.cuda.graph_pool_handle()
-        self.items = []          # torch.cuda.CUDAGraph or a zero-argument callable
-        self.cur = None
-        # The collectives run on a stream of their own, never on the one being recorded: the backend records its work
-        # events on the stream a blocking collective is issued from, its watchdog THREAD polls them, and HIP refuses to
-        # query an event whose stream has meanwhile entered capture (hipErrorCapturedEvent) -- the watchdog then
-        # takes the process down (seen once in ~6 runs of the one-rank RCCL test, at the capture that follows a
-        # SyncBN exchange).
-        self.comm = torch.cuda.Stream()
-
-    def _on_comm(self, fn):
-        cur = torch.cuda.current_stream()
-        self.comm.wait_stream(cur)
-        with torch.cuda.stream(self.comm):
-            fn()
-        cur.wait_stream(self.comm)
-
-    def begin(self):
-        self.cur = torch.cuda.CUDAGraph()
-        self.cur.capture_begin(pool=self.pool, capture_error_mode="thread_local")
-
-    def end(self):
-        ops.join_side()          # a capture cannot end with forked side-stream work (weight gradients) un-joined
-        self.cur.capture_end()
-        self.items.append(self.cur)
-        self.cur = None
-
-    def collective(self, fn):
-        self.end()
-        run = lambda: self._on_comm(fn)
-        run()                    # communicator warm, same call order as at replay; operates on not-yet-computed data
-        self.items.append(run)
-        self.begin()
-
-    def replay(self):
-        for it in self.items:
-            if isinstance(it, torch.cuda.CUDAGraph):
-                it.replay()
-            else:
-                it()
-
-
-_SMALL_GROUP = {}
-
-
-def _small_group(dist):
-    """The second communicator (small messages), created once per process and default group -- not once per step object."""
-    key = id(dist.group.WORLD)
-    if key not in _SMALL_GROUP:
-        _SMALL_GROUP.clear()
-        _SMALL_GROUP[key] = dist.new_group()
-    return _SMALL_GROUP[key]
-
-
-class _Dist:
-    """Data-parallel glue (one process per GPU, RCCL): SUM all-reduce of flat gradients / loss scalars and
-    the SyncBN statistic exchange.  Inactive (world size 1) unless torch.distributed is initialised."""
-
-    def __init__(self, enabled: bool, sync_bn: bool = True):
-        import torch.distributed as dist
-        self.dist = dist
-        # FMRI_FORCE_DIST=1: take the collective path even with one rank (single-GPU rehearsal of the RCCL calls)
-        force = os.environ.get("FMRI_FORCE_DIST") == "1"
-        self.on = enabled and dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or force)
-        self.world = dist.get_world_size() if self.on else 1
-        self.sync_bn = sync_bn
-        self.pending = []
-        # A communicator of its own for the SMALL collectives of the main stream (loss scalars, the stream-norm scalar,
-        # SyncBN sums).  Collectives of one communicator run in issue order on its stream: behind a 44 MB gradient
-        # all-reduce that is itself waiting for the side stream's weight gradients, a 40-byte all-reduce of the main
-        # stream would stall the whole backward pass (head-of-line blocking); on a second communicator it does not.
-        # FMRI_SMALL_COMM=off: everything on the default communicator (collectives then run in issue order, the order of
-        # the program on every rank) -- the fallback should two communicators driven from two streams ever misbehave on a
-        # real multi-GPU node (ADVICE r4); costs the head-of-line blocking described above
-        self.small = _small_group(dist) if (self.on and os.environ.get("FMRI_SMALL_COMM") != "off") else None
-        self.recorder: Optional[_SegmentRecorder] = None     # set while a step is recorded into graph segments
-
-    SMALL = 1 << 16          # elements: at most this many go through the small-message communicator
-
-    def all_reduce(self, t: torch.Tensor):
-        """Blocking SUM all-reduce on the CURRENT stream (the host does not wait): scalars / statistics on the
-        small-message communicator, gradient buffers on the default one."""
-        if not self.on:
-            return
-        grp = self.small if t.numel() <= self.SMALL else None
-        if self.recorder is not None:
-            self.recorder.collective(lambda: self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=grp))
-        else:
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=grp)
-
-    def all_reduce_max(self, t: torch.Tensor):
-        """Blocking MAX all-reduce of a few scalars on the current stream (the latent range of a SyncBN step)."""
-        if not self.on:
-            return
-        fn = lambda: self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.small)
-        if self.recorder is not None:
-            self.recorder.collective(fn)
-        else:
-            fn()
-
-    def all_reduce_async(self, t: torch.Tensor):
-        """Start a SUM all-reduce (same communicator, so it queues behind / ahead of the blocking ones in program
-        order on every rank) and return immediately; `wait_all` joins it with the compute stream."""
-        if not self.on:
-            return
-
-        def issue():
-            self.pending.append(self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, async_op=True))
-        if self.recorder is not None:
-            self.recorder.collective(issue)
-        else:
-            issue()
-
-    def wait_all(self):
-        if not self.on:
-            return
-
-        def join():
-            for h in self.pending:
-                h.wait()
-            self.pending.clear()
-        if self.recorder is not None:
-            self.recorder.collective(join)
-        else:
-            join()
-
-    def bn_reducer(self):
-        if not (self.on and self.sync_bn):
-            return None
-
-        def red(sums):
-            self.all_reduce(sums)
-            return self.world
-        return red
-
-
-def _attach_reducers(nets, d: _Dist):
-    r = d.bn_reducer()
-    for n in nets:
-        for bn in n.all_bns():
-            bn.reducer = r
-
-
-class _GanStepBase(Monitored):
-    """Shared pieces of the Stage-I/II/III steps: loss kernels, gate, scalar block, logging."""
+class _GanStepBase(_StepBase):
+    """The VAE/GAN pieces of the Stage-I/II/III steps: hyper-parameters, loss kernels, gate, starting cotangents,
+    logging."""
 
     def _init_common(self, device, hp, scales, distributed, sync_bn, nets):
+        self._init_step(device, nets, distributed, sync_bn)
         # fresh instances: GanHyper / Scales are mutable (the per-epoch decays are written as step.set_hyper(...))
         self.hp = GanHyper() if hp is None else hp
         self.sc = Scales() if scales is None else scales
         self.mode = "vae-gan"
-        self.device = torch.device(device)
-        self.scal = torch.zeros(32, dtype=torch.float32, device=device)
         # [lambda_mse, equilibrium, margin, beta] on the device: read by the gate kernel, so a recorded step follows
         # the per-epoch decays (train_vgan_stage1.py:451-458)
         self.hp_dev = torch.tensor([self.hp.lambda_mse, self.hp.equilibrium, self.hp.margin, self.hp.beta],
@@ -286,86 +83,6 @@ class _GanStepBase(Monitored):
         # per decoder call group: the power of two its latent rows are stored scaled by (ops.latent_ranged); the groups
         # fed with caller noise keep 1
         self.zs = torch.ones(4, dtype=torch.float32, device=device)
-        self.esq64 = torch.zeros(1, dtype=torch.float64, device=device)      # sum of squares of _renorm
-        self.dd = _Dist(distributed, sync_bn)
-        _attach_reducers(nets, self.dd)
-        self.fw: Dict[str, object] = {}
-
-    def _init_rng(self, rng: Optional[DeviceRng], feed=None):
-        self.rng = rng
-        self._noise = StepNoise(rng) if rng is not None else None
-        self._last_noise: Dict[str, torch.Tensor] = {}
-        self.feed = feed             # fmri_hip.feed.DeviceFeed or None
-        self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
-
-    def _fed(self, *given):
-        """The batch of a step.  Without a feed: ``given`` (the caller's batch tensors) must all be there; returns None.
-        With a feed: none may be; the feed enqueues its next batch (fmri_hip/feed.py) -- the first launches of the step,
-        so they sit in the one graph of a recording, or in the first segment of a data-parallel one -- and its buffers
-        (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
-        generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
-        the noise and the augmentation draws."""
-        feed = self.feed
-        if feed is None:
-            if any(g is None for g in given):
-                raise ValueError(f"{type(self).__name__}: no batch given and the step has no feed (pass the batch, or "
-                                 "construct the step with feed=DeviceFeed(...))")
-            return None
-        if any(g is not None for g in given):
-            raise ValueError(f"{type(self).__name__}: the step has a feed and draws its own batch: step() takes no "
-                             "batch arguments")
-        shared = feed.rng is not None and feed.rng is self.rng
-        x, fm, _ = feed.next(advance_rng=not shared)
-        self._feed_blocks = feed.rng_blocks() if shared else 0
-        return x, fm, feed.fmri16
-
-    def _feed_advance(self):
-        """The shared generator's advance for a step that drew no noise after its feed drew augmentation."""
-        if self._feed_blocks:
-            self.rng.advance(self._feed_blocks)
-            self._feed_blocks = 0
-
-    def _resolve_noise(self, B: int, wanted):
-        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
-        the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
-        [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
-        draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
-        the same generator in this step, if that is larger.  Returns the tensors in the order asked for."""
-        missing = [name for name, _, t in wanted if t is None]
-        if missing and self._noise is None:
-            raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
-                             "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
-        Z = self.cfg.latent_dim
-        dd = self.dd
-        rank = dd.dist.get_rank() if dd.on else 0
-        if missing:
-            self._noise.begin()
-        out = {}
-        for name, sid, t in wanted:
-            out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
-        if missing:
-            self._noise.end(B * dd.world, Z, at_least=self._feed_blocks)
-            self._feed_blocks = 0
-        else:
-            self._feed_advance()
-        self._last_noise = out
-        return list(out.values())
-
-    def last_noise(self) -> Dict[str, torch.Tensor]:
-        """The noise tensors the last step used, by argument name in the order ``step`` takes them (the step's own
-        buffers where it drew them: clone what has to outlive the next step)."""
-        return dict(self._last_noise)
-
-    def _reduce_async(self, group, part=None):
-        """Data parallel: the sub-network's deferred weight gradients -> reference layout (one launch), then the
-        asynchronous SUM all-reduce of the gradient buffer (or of ``part`` of it).  Nothing on one GPU: the gradients
-        stay deferred until the update (ops.apply_group)."""
-        if self.dd.on:
-            ops.materialize_grads(group)
-            self.dd.all_reduce_async(group.grad if part is None else part)
-
-    def _slot(self, i):
-        return self.scal[i:i + 1]
 
     def _latent(self, head32, eps, z16_rows, group: int, kl_slot: Optional[int]):
         """z = eps * sigma + mu of decoder call group ``group`` into ``z16_rows``, range-safe (ops.latent_ranged): the
@@ -383,9 +100,9 @@ class _GanStepBase(Monitored):
         hp = self.hp
         if lr is not None:
             hp.lr = float(lr)
-            for o in (getattr(self, n, None) for n in ("opt_enc", "opt_dec", "opt_dis")):
-                if o is not None:
-                    o.set_lr(lr)
+            # encoder, decoder, discriminator: the Dual step's latent discriminator (registered fourth) keeps its rate
+            for o in self.optims[:3]:
+                o.set_lr(lr)
         for name, v in (("lambda_mse", lambda_mse), ("equilibrium", equilibrium), ("margin", margin), ("beta", beta)):
             if v is not None:
                 setattr(hp, name, float(v))
@@ -413,12 +130,24 @@ class _GanStepBase(Monitored):
                  float(3 * fw["H"] * fw["W"]), _P(self.hp_dev), MODES[self.mode], 1 if gate_on else 0, force_dis,
                  force_dec)
 
-    def _start_cotangents(self, feat, logit32, B):
-        """fp16 starting cotangents of stream A (logits) and stream B (raw conv-3 features)."""
-        dev = feat.device
-        dlogit16 = torch.empty(3 * B, 8, dtype=torch.float16, device=dev)
+    def _gate_flag(self, i: int):
+        """The equilibrium gate's device flag i (0 = discriminator, 1 = decoder) as the condition of a sub-network's
+        weight gradients (ops.begin_grads), or None when ``gate_skip`` is off."""
+        return self.flags[i:i + 1] if self.gate_skip else None
+
+    def _logit_cotangent(self, B):
+        """fp16 starting cotangent of stream A: d L_dis / d logits of the last forward, S_NA <- its norm factor."""
+        logit32 = self.fw["logit32"]
+        dlogit16 = torch.empty(3 * B, 8, dtype=torch.float16, device=logit32.device)
         lib.call("fmri_gan_head_bwd_parts", _P(logit32), 1, B, _P(dlogit16), 8, self.sc.a, _P(self._slot(S_NA)),
                  self._dis_parts())
+        return dlogit16
+
+    def _start_cotangents(self, B):
+        """fp16 starting cotangents of stream A (logits) and stream B (raw conv-3 features)."""
+        feat = self.fw["feat"]
+        dev = feat.device
+        dlogit16 = self._logit_cotangent(B)
         # stream B's cotangent is written straight into the second half of the buffer that stacks both streams for the
         # discriminator's conv backward (DiscriminatorNet fills the first half with stream A: no concatenation copy)
         stack = torch.empty((2 * feat.shape[0],) + tuple(feat.shape[1:]), dtype=feat.dtype, device=dev)
@@ -428,89 +157,20 @@ class _GanStepBase(Monitored):
         lib.call("fmri_feat_mse_bwd", _P(feat), B, feat[0].numel(), _P(dfeat16), self.sc.b, _P(self._slot(S_NB)))
         return dlogit16, dfeat16
 
-    def _renorm(self, x32: torch.Tensor, scale: float, factor_in, rows_global: int):
-        """fp32 cotangent -> unit-RMS fp16 (times ``scale``); S_NE <- (*factor_in) / rms.  The sum of squares is
-        all-reduced so that every data-parallel rank applies the same factor."""
-        n = x32.numel()
-        # the sum of squares in double precision (the KL term's 0.5 * (exp(logvar) - 1), squared, leaves fp32 at
-        # logvar > 44), cleared by the launch itself: a second backward() after one gate() starts from zero as well
-        esq = self.esq64
-        lib.call("fmri_sumsq_f64", _P(x32), n, _P(esq), 1)
-        self.dd.all_reduce(esq)
-        out = torch.empty(x32.shape, dtype=torch.float16, device=x32.device)
-        count = float(rows_global) * (n // x32.shape[0])
-        lib.call("fmri_renorm_f64", _P(x32), _P(out), n, float(scale), _P(esq), count, _P(factor_in),
-                 _P(self._slot(S_NE)))
-        return out
-
-    def capture(self, *static_inputs, warmup: int = 2):
-        """Record one ``step(*static_inputs)`` into a HIP graph and return a zero-argument callable that replays it.
-
-        Every launch of a step is enqueue-only and nothing inside a step synchronises with the host (the equilibrium
-        gate, the stream normalisation and the optimizer gating all live on the device), so the ~370 launches of a
-        step can be replayed as one graph: the step time then no longer depends on how fast the host can issue them.
-        Inputs are read from ``static_inputs`` at every replay -- copy each new batch into those tensors.  Learning
-        rates, lambda, margin, equilibrium and beta are device-resident (``set_lr`` / ``set_hyper``): a replayed step follows
-        their schedules (Adam's step count of the WAE steps lives on the device too, ``wae_steps``).  In a data-parallel run the collectives
-        are kept out of the graphs (see _SegmentRecorder)."""
-        # The weight-gradient side stream (ops.side_run) is switched off while recording: a replayed HIP graph runs
-        # its parallel branches no faster than a chain (measured 8.8 ms chained, 9.0-9.5 ms with the fork/join
-        # branches, 8.4 ms eager with two streams), so the recorded step keeps everything on one stream.
-        side_was = ops._SIDE["on"]
-        ops.join_side()
-        ops._SIDE["on"] = False
-        try:
-            return self._capture(static_inputs, warmup)
-        finally:
-            ops._SIDE["on"] = side_was
-
-    def _capture(self, static_inputs, warmup):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.step(*static_inputs)
-        torch.cuda.current_stream().wait_stream(side)
-        if self.dd.on:
-            # data-parallel: the collectives stay eager, the launches between them become graphs
-            rec = _SegmentRecorder()
-            self.dd.recorder = rec
-            try:
-                with torch.cuda.stream(side):
-                    rec.begin()
-                    self.step(*static_inputs)
-                    rec.end()
-            except BaseException:
-                if rec.cur is not None:          # leave no stream capture open behind a failed recording
-                    try:
-                        rec.cur.capture_end()
-                    except Exception:
-                        pass
-                raise
-            finally:
-                self.dd.recorder = None
-            torch.cuda.current_stream().wait_stream(side)
-            self._graph = rec
-            return self._versioned(rec.replay)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self.step(*static_inputs)
-        self._graph = graph
-        return self._versioned(graph.replay)
-
-    def _versioned(self, replay):
-        """A replay updates the master weights without passing through ``_Optim.step``: bump the groups' version
-        counters so that the first eager step afterwards re-packs its fp16 weights."""
-        groups = [o.g for o in (getattr(self, n, None) for n in ("opt_enc", "opt_dec", "opt_dis", "opt_wd"))
-                  if o is not None]
-
-        def run():
-            for h in getattr(self, "_pre_replay", []):
-                h()
-            replay()
-            for g in groups:
-                g.version += 1
-        return run
+    def _encoder_cotangent(self, dz, norm_slot: int, kl_dev=None, extra_dmu=None):
+        """Decoder-side dz (carried at the device factor of ``norm_slot``: S_NB or S_NP) -> the encoder's fp16 head
+        cotangent: dz and the KL term (device weight ``kl_dev``, default the slot's factor) through the
+        reparameterisation, ``extra_dmu`` (fp32 [B, z], true scale) added on the means at the same factor, then the
+        unit-RMS re-normalisation (S_NE <- factor * nE)."""
+        fw = self.fw
+        B, Z = fw["B"], self.cfg.latent_dim
+        norm = self._slot(norm_slot)
+        dhead32 = torch.empty(B, 2 * Z, dtype=torch.float32, device=dz.device)
+        lib.call("fmri_latent_bwd", _P(fw["head32"]), _P(fw["eps"]), _P(dz), Z, 1.0, 1.0,
+                 _P(norm if kl_dev is None else kl_dev), B, Z, 1.0, None, _P(dhead32), 1)
+        if extra_dmu is not None:
+            dhead32[:, :Z].addcmul_(extra_dmu, norm)
+        return self._renorm(dhead32, self.sc.enc, norm, B * self.dd.world)
 
     def logs(self):
         v = self.scal.tolist()
@@ -547,37 +207,40 @@ class Stage1Step(_GanStepBase):
         self.enc = EncoderNet(cfg, device)
         self.dec = DecoderNet(cfg, device, self.enc.size)
         self.dec.fc_bn.enable_lazy_running()
-        self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self.dis = DiscriminatorNet(cfg, device)
         self._init_common(device, hp, scales, distributed, sync_bn, (self.enc, self.dec, self.dis))
+        self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self._init_rng(rng, feed)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.enc.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dec = _Optim(self.dec.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dis = _Optim(self.dis.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
+        self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         self.enc_updates = 1                 # encoder passes per batch in the script (BN running-stat updates)
         self.extra_mu_decoder_pass = False   # DualStage1Step (wae_steps.py)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
 
     # ---- parameters -----------------------------------------------------------------------------
+    def _subnets(self):
+        """(state-dict prefix, network, slot of the device factor its gradients carry) per sub-network."""
+        return (("encoder.", self.enc, S_NE), ("decoder.", self.dec, S_GDEC), ("discriminator.", self.dis, S_NA))
+
     def load_recipe(self, seed: int, perturb: bool = False):
         rs = np.random.RandomState(seed)
-        for n in (self.enc, self.dec, self.dis):
+        for _, n, _ in self._subnets():
             n.group.load_recipe(rs, perturb)
 
     def state_dict(self):
         sd = {}
-        sd.update(self.enc.group.state_dict("encoder."))
-        sd.update(self.dec.group.state_dict("decoder."))
-        sd.update(self.dis.group.state_dict("discriminator."))
+        for pre, n, _ in self._subnets():
+            sd.update(n.group.state_dict(pre))
         return sd
 
     def load_state_dict(self, sd):
-        self.enc.group.load_state_dict(sd, "encoder.")
-        self.dec.group.load_state_dict(sd, "decoder.")
-        self.dis.group.load_state_dict(sd, "discriminator.")
+        for pre, n, _ in self._subnets():
+            n.group.load_state_dict(sd, pre)
 
     # ---- the step ---------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, z_p: Optional[torch.Tensor] = None):
@@ -627,11 +290,10 @@ class Stage1Step(_GanStepBase):
         # ``early_apply`` also says that nobody reads reference-layout gradients between this pass and the updates: on one
         # GPU the weight gradients then stay in their GEMM layout until the sub-network's one fmri_apply_batch launch
         fuse = early_apply and self.dd.recorder is None
-        gs = self.gate_skip
         ops.begin_grads(self.enc.group, fuse)
-        ops.begin_grads(self.dec.group, fuse, gate=self.flags[1:2] if gs else None)
-        ops.begin_grads(self.dis.group, fuse, gate=self.flags[0:1] if gs else None)
-        dlogit16, dfeat16 = self._start_cotangents(fw["feat"], fw["logit32"], B)
+        ops.begin_grads(self.dec.group, fuse, gate=self._gate_flag(1))
+        ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
+        dlogit16, dfeat16 = self._start_cotangents(B)
         # weight gradients run on the side stream (ops.side_run) and are joined once, at the end of the backward pass, so
         # that a sub-network's last weight gradients overlap the next one's backward
         dp = self.dd.on
@@ -664,18 +326,11 @@ class Stage1Step(_GanStepBase):
             ops.side_run(dev, lambda: self._reduce_apply(self.opt_dec, self.dec, self.flags[1:2], S_GDEC))
         else:
             self._reduce_async(self.dec.group)
-        dhead32 = torch.empty(B, 2 * Z, dtype=torch.float32, device=dev)
         # KL weight: 1, or beta / batch for 'beta-vae' (train_vgan_stage1.py:360-362).  The gate kernel writes it to
         # the device slot S_KLW from the device-resident hyper-parameters, so that a recorded (HIP-graph) step follows
         # set_hyper(beta=...) in the encoder GRADIENT as well as in the logged loss: weight = S_KLW * nB on the device
-        kl_dev = self._slot(S_NB)
-        if self.mode == "beta-vae":
-            kl_dev = torch.mul(self._slot(S_KLW), self._slot(S_NB))
-        lib.call("fmri_latent_bwd", _P(fw["head32"]), _P(fw["eps"]), _P(dz), Z, 1.0, 1.0, _P(kl_dev), B, Z,
-                 1.0, None, _P(dhead32), 1)                              # = nB * dhead_true
-        if extra_dmu is not None:
-            dhead32[:, :Z].addcmul_(extra_dmu, self._slot(S_NB))            # carried at the same device factor nB
-        dhead16 = self._renorm(dhead32, sc.enc, self._slot(S_NB), B * self.dd.world)   # S_NE = nB * nE
+        kl_dev = torch.mul(self._slot(S_KLW), self._slot(S_NB)) if self.mode == "beta-vae" else None
+        dhead16 = self._encoder_cotangent(dz, S_NB, kl_dev, extra_dmu)          # S_NE = nB * nE
         eg = self.enc.group
         tail = eg.offsets["fc.0.weight"]
         if early and dp:
@@ -713,9 +368,7 @@ class Stage1Step(_GanStepBase):
         self._applied_early = False
         for n in (self.enc, self.dec, self.dis):
             n.group.zero_grad()
-        dlogit16 = torch.empty(3 * B, 8, dtype=torch.float16, device=dev)
-        lib.call("fmri_gan_head_bwd_parts", _P(fw["logit32"]), 1, B, _P(dlogit16), 8, sc.a, _P(self._slot(S_NA)),
-                 self._dis_parts())
+        dlogit16 = self._logit_cotangent(B)
         x16, xt16 = d_in[:B], d_in[B:2 * B]
         if self.mode == "dcgan":
             dimg_a, _ = self.dis.backward(fw["sctx"], dlogit16, sc.a, None, sc.b, True, slice(B, 3 * B), join=dp)
@@ -739,12 +392,7 @@ class Stage1Step(_GanStepBase):
         entries = [dict(g=0, scale=sc.p, train=True, need_dz=True)]
         dz = self.dec.backward(fw["dctx"], cot, entries, join=dp)[0]        # = nP * dz_true
         self.dd.all_reduce_async(self.dec.group.grad)
-        dhead32 = torch.empty(B, 2 * Z, dtype=torch.float32, device=dev)
-        lib.call("fmri_latent_bwd", _P(fw["head32"]), _P(fw["eps"]), _P(dz), Z, 1.0, 1.0, _P(self._slot(S_NP)), B, Z,
-                 1.0, None, _P(dhead32), 1)                                  # = nP * dhead_true
-        if extra_dmu is not None:
-            dhead32[:, :Z].addcmul_(extra_dmu, self._slot(S_NP))                # carried at the same device factor nP
-        dhead16 = self._renorm(dhead32, sc.enc, self._slot(S_NP), B * self.dd.world)    # S_NE = nP * nE
+        dhead16 = self._encoder_cotangent(dz, S_NP, extra_dmu=extra_dmu)        # S_NE = nP * nE
         eg = self.enc.group
         tail = eg.offsets["fc.0.weight"]
         self.enc.backward(fw["ectx"], dhead16, sc.enc,
@@ -861,11 +509,10 @@ class Stage1Step(_GanStepBase):
         ``backward()``; ``step()`` does not leave any (FlatGroup.check_grads_readable)."""
         s = self.scal.tolist()
         out = {}
-        for pre, n, f in (("encoder.", self.enc, s[S_NE]), ("decoder.", self.dec, s[S_GDEC]),
-                          ("discriminator.", self.dis, s[S_NA])):
+        for pre, n, slot in self._subnets():
             n.group.check_grads_readable()
             for k, v in n.group.grads.items():
-                out[pre + k] = v / f
+                out[pre + k] = v / s[slot]
         return out
 
 
@@ -899,11 +546,11 @@ class CognitiveStep(_GanStepBase):
         self.cog = CognitiveEncoderNet(cfg, n_voxels, device)
         self.dec = DecoderNet(cfg, device, cfg.encoder_channels[2])
         self.dec.fc_bn.enable_lazy_running()
-        self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self.dis = DiscriminatorNet(cfg, device)
         self.teacher_enc = EncoderNet(cfg, device) if (stage == 2 and mode != "vae") else None
         nets = [self.cog, self.dec, self.dis] + ([self.teacher_enc] if self.teacher_enc is not None else [])
         self._init_common(device, hp, scales, distributed, sync_bn, nets)
+        self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         if feed is not None and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
             raise ValueError("CognitiveStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
         self._init_rng(rng, feed)
@@ -912,6 +559,7 @@ class CognitiveStep(_GanStepBase):
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dec = _Optim(self.dec.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
         self.opt_dis = _Optim(self.dis.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
+        self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.cog), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
 
@@ -923,15 +571,24 @@ class CognitiveStep(_GanStepBase):
             n.group.load_recipe(rs, perturb)
         self.cog.group.load_recipe(np.random.RandomState(seed + 100), perturb)
 
+    def _subnets(self):
+        """(state-dict prefix, network, slot of the device factor its gradients carry or None: not trained in this
+        stage) per sub-network."""
+        st = self.stage
+        nets = [("encoder.", self.cog, S_NE if st == 2 else None), ("decoder.", self.dec, S_GDEC if st == 3 else None),
+                ("discriminator.", self.dis, S_NA)]
+        if self.teacher_enc is not None:
+            nets.append(("teacher_net.encoder.", self.teacher_enc, None))
+        return nets
+
     def state_dict(self):
         sd = {}
-        sd.update(self.cog.group.state_dict("encoder."))
-        sd.update(self.dec.group.state_dict("decoder."))
-        sd.update(self.dis.group.state_dict("discriminator."))
-        if self.teacher_enc is not None:
-            sd.update(self.teacher_enc.group.state_dict("teacher_net.encoder."))
-            sd.update(self.dec.group.state_dict("teacher_net.decoder."))
-            sd.update(self.dis.group.state_dict("teacher_net.discriminator."))
+        nets = self._subnets()
+        for pre, n, _ in nets:
+            sd.update(n.group.state_dict(pre))
+        if self.teacher_enc is not None:         # the teacher's decoder / discriminator are the model's own
+            for pre, n, _ in nets[1:3]:
+                sd.update(n.group.state_dict("teacher_net." + pre))
         return sd
 
     def load_state_dict(self, sd):
@@ -939,11 +596,8 @@ class CognitiveStep(_GanStepBase):
         ``encoder.`` = cognitive encoder, ``decoder.``, ``discriminator.`` and, for stage 2, ``teacher_net.encoder.``
         (train/train_vgan_stage3.py:241 loads the Stage-II file this way; its ``teacher_net.decoder./discriminator.``
         entries alias ``decoder.`` / ``discriminator.`` in Stage II and are not needed in Stage III)."""
-        self.cog.group.load_state_dict(sd, "encoder.")
-        self.dec.group.load_state_dict(sd, "decoder.")
-        self.dis.group.load_state_dict(sd, "discriminator.")
-        if self.teacher_enc is not None:
-            self.teacher_enc.group.load_state_dict(sd, "teacher_net.encoder.")
+        for pre, n, _ in self._subnets():
+            n.group.load_state_dict(sd, pre)
 
     def load_teacher(self, sd):
         """A Stage-I ``VaeGan`` checkpoint as the teacher (train/train_vgan_stage2.py:212-217,230): its decoder and
@@ -1017,26 +671,23 @@ class CognitiveStep(_GanStepBase):
         fuse = fuse and self.dd.recorder is None
         if self.mode == "vae":
             return self._backward_pixel(fuse)
-        dlogit16, dfeat16 = self._start_cotangents(fw["feat"], fw["logit32"], B)
-        gs = self.gate_skip                  # (see Stage1Step: no gradients for a sub-network the gate does not train)
+        dlogit16, dfeat16 = self._start_cotangents(B)
+        # (gate flags: see Stage1Step -- no gradients for a sub-network the gate does not train)
         if self.stage == 2:
             ops.begin_grads(self.cog.group, fuse)
-            ops.begin_grads(self.dis.group, fuse, gate=self.flags[0:1] if gs else None)
+            ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
             _, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 2 * B),
                                           img_streams=(False, True))
             self._reduce_async(self.dis.group)                  # under the decoder / cognitive-encoder backward
             entries = [dict(g=fw["g_tilde"], scale=sc.b, train=False, need_dz=True)]
             dz = self.dec.backward(fw["dctx"], dimg_b, entries)[0]
-            dhead32 = torch.empty(B, 2 * Z, dtype=torch.float32, device=dev)
-            lib.call("fmri_latent_bwd", _P(fw["head32"]), _P(fw["eps"]), _P(dz), Z, 1.0, 1.0, _P(self._slot(S_NB)), B,
-                     Z, 1.0, None, _P(dhead32), 1)
-            dhead16 = self._renorm(dhead32, sc.enc, self._slot(S_NB), B * self.dd.world)
+            dhead16 = self._encoder_cotangent(dz, S_NB)
             self.cog.backward(fw["cctx"], dhead16, sc.enc)
             self._reduce_async(self.cog.group)
             self.dd.wait_all()
         else:
-            ops.begin_grads(self.dec.group, fuse, gate=self.flags[1:2] if gs else None)
-            ops.begin_grads(self.dis.group, fuse, gate=self.flags[0:1] if gs else None)
+            ops.begin_grads(self.dec.group, fuse, gate=self._gate_flag(1))
+            ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
             dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B))
             self._reduce_async(self.dis.group)                  # under the decoder backward
             cot = axpby(dimg_b, dimg_a, sc.dec / sc.b, -sc.dec / sc.a, a_dev=self._slot(S_C1), b_dev=self._slot(S_C2))
@@ -1053,17 +704,14 @@ class CognitiveStep(_GanStepBase):
         B, H, W, Z = fw["B"], fw["H"], fw["W"], cfg.latent_dim
         d_in = fw["disc_in"]
         dev = d_in.device
-        gs = self.gate_skip
-        dlogit16 = torch.empty(3 * B, 8, dtype=torch.float16, device=dev)
-        lib.call("fmri_gan_head_bwd_parts", _P(fw["logit32"]), 1, B, _P(dlogit16), 8, sc.a, _P(self._slot(S_NA)),
-                 self._dis_parts())
+        dlogit16 = self._logit_cotangent(B)
         x16, xt16 = d_in[:B], d_in[B:2 * B]
         if self.stage == 2:
             ops.begin_grads(self.cog.group, fuse)
-            ops.begin_grads(self.dis.group, fuse, gate=self.flags[0:1] if gs else None)
+            ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
         else:
-            ops.begin_grads(self.dec.group, fuse, gate=self.flags[1:2] if gs else None)
-            ops.begin_grads(self.dis.group, fuse, gate=self.flags[0:1] if gs else None)
+            ops.begin_grads(self.dec.group, fuse, gate=self._gate_flag(1))
+            ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
         self.dis.backward(fw["sctx"], dlogit16, sc.a, None, sc.b, True, None)
         self._reduce_async(self.dis.group)
         # stored = p * nP * (x_tilde - x_gt)
@@ -1071,10 +719,7 @@ class CognitiveStep(_GanStepBase):
         if self.stage == 2:
             entries = [dict(g=fw["g_tilde"], scale=sc.p, train=False, need_dz=True)]
             dz = self.dec.backward(fw["dctx"], cot, entries)[0]                  # = nP * dz_true
-            dhead32 = torch.empty(B, 2 * Z, dtype=torch.float32, device=dev)
-            lib.call("fmri_latent_bwd", _P(fw["head32"]), _P(fw["eps"]), _P(dz), Z, 1.0, 1.0, _P(self._slot(S_NP)), B,
-                     Z, 1.0, None, _P(dhead32), 1)
-            dhead16 = self._renorm(dhead32, sc.enc, self._slot(S_NP), B * self.dd.world)   # S_NE = nP * nE
+            dhead16 = self._encoder_cotangent(dz, S_NP)                         # S_NE = nP * nE
             self.cog.backward(fw["cctx"], dhead16, sc.enc)
             self._reduce_async(self.cog.group)
         else:
@@ -1119,11 +764,11 @@ class CognitiveStep(_GanStepBase):
 
     def named_grads(self):
         s = self.scal.tolist()
-        groups = ((("encoder.", self.cog, s[S_NE]), ("discriminator.", self.dis, s[S_NA])) if self.stage == 2 else
-                  (("decoder.", self.dec, s[S_GDEC]), ("discriminator.", self.dis, s[S_NA])))
         out = {}
-        for pre, n, f in groups:
+        for pre, n, slot in self._subnets():
+            if slot is None:
+                continue
             n.group.check_grads_readable()
             for k, v in n.group.grads.items():
-                out[pre + k] = v / f
+                out[pre + k] = v / s[slot]
         return out

@@ -32,10 +32,9 @@ from .nets import CognitiveEncoderNet, DecoderNet, EncoderNet, WaeDiscriminatorN
 from .mmd import mmd_imq
 from .ops import images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
-from .monitor import Monitored
 from .rng import SID_EPS, SID_ZFAKE, SID_ZP, DeviceRng
-from .steps import (LOG_KEYS, S_ESQ, S_NA, S_NB, S_NE, GanHyper, Scales, Stage1Step, _attach_reducers, _Dist,
-                    _GanStepBase, _Optim)
+from .step_base import S_NE, _Dist, _Optim, _StepBase
+from .steps import LOG_KEYS, GanHyper, Scales, Stage1Step
 
 _P = lib.ptr
 
@@ -93,7 +92,7 @@ class _LatentDiscPhase:
         return wd.backward(ctx, dlogit, gscale, False, True)
 
 
-class WaeStep(_LatentDiscPhase, Monitored):
+class WaeStep(_LatentDiscPhase, _StepBase):
     """WAE/GAN Stage I / II / III step.
 
     ``penalty``: "gan" (default) the scripts' latent discriminator; "mmd" the IMQ-kernel MMD_u between the trained
@@ -118,22 +117,19 @@ class WaeStep(_LatentDiscPhase, Monitored):
         self.cfg, self.stage, self.n_voxels = cfg, stage, n_voxels
         self.sc = Scales() if scales is None else scales
         self.hp = hp if hp is not None else (WaeHyper() if stage == 1 else WaeHyper.stage23())
-        self.device = torch.device(device)
         self.img_enc = EncoderNet(cfg, device)                       # Stage I: trained; II/III: Stage-I teacher
         self.cog = CognitiveEncoderNet(cfg, n_voxels, device) if stage > 1 else None
         self.dec = DecoderNet(cfg, device, self.img_enc.size)
         self.dec.fc_bn.enable_lazy_running()
-        self._pre_replay = [self.dec.fc_bn._running_in]
         self.wd = WaeDiscriminatorNet(cfg, device)
-        self.scal = torch.zeros(32, dtype=torch.float32, device=device)
-        self.dd = _Dist(distributed, sync_bn)
-        _attach_reducers([n for n in (self.img_enc, self.cog, self.dec) if n is not None], self.dd)
+        self._init_step(device, [n for n in (self.img_enc, self.cog, self.dec) if n is not None], distributed, sync_bn)
+        self._pre_replay = [self.dec.fc_bn._running_in]
         hp_ = self.hp
         self.enc = self.img_enc if stage == 1 else self.cog          # the network `model.encoder` refers to
         self.opt_enc = _Optim(self.enc.group, "adam", hp_.lr_enc, betas=hp_.betas)
         self.opt_dec = _Optim(self.dec.group, "adam", hp_.lr_dec, betas=hp_.betas)
         self.opt_dis = _Optim(self.wd.group, "adam", hp_.lr_dis, betas=hp_.betas)
-        self.fw = {}
+        self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         if feed is not None and stage > 1 and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
             raise ValueError("WaeStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
         self._init_rng(rng, feed)
@@ -165,7 +161,9 @@ class WaeStep(_LatentDiscPhase, Monitored):
     # ---- the step --------------------------------------------------------------------------------------------
     def step(self, image: Optional[torch.Tensor] = None, z_fake_noise: Optional[torch.Tensor] = None,
              fmri: Optional[torch.Tensor] = None):
-        """Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276); step(x) draws the noise
+        """(``capture()`` records it whole: Adam's step count and the learning rates live on the device, and the ~300
+        launches of a few microseconds each are bound by the host when issued eagerly.)
+        Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276); step(x) draws the noise
         with the step's ``rng``.  Stage II/III: step(image, fmri=fmri).  With a ``feed``: step() / step(None, noise)."""
         st = self.stage
         fed = self._fed(image) if st == 1 else self._fed(image, fmri)
@@ -254,7 +252,7 @@ class WaeStep(_LatentDiscPhase, Monitored):
             dz = dz_rec[0] + dz_pen[:, :Z]
             dhead32 = torch.zeros(B, 2 * Z, dtype=torch.float32, device=dev)        # l_var gets no gradient
             dhead32[:, :Z] = dz
-            dhead16 = self._renorm(dhead32, sc.enc, Bg)
+            dhead16 = self._renorm(dhead32, sc.enc, None, Bg)
             self.enc.group.zero_grad()
             self.enc.backward(ectx, dhead16, sc.enc)
             self.dd.all_reduce_async(self.enc.group.grad)
@@ -290,30 +288,6 @@ class WaeStep(_LatentDiscPhase, Monitored):
         if dq is None:
             return None
         return dq[rank * B:(rank + 1) * B] if dd.on else dq
-
-    # HIP-graph recording of the whole step (Adam's step count and learning rates live on the device): the WAE steps are
-    # ~300 launches of a few microseconds each -- eagerly issued they are bound by the host, replayed by the GPU
-    capture = _GanStepBase.capture
-    _capture = _GanStepBase._capture
-    _versioned = _GanStepBase._versioned
-    _init_rng = _GanStepBase._init_rng
-    _resolve_noise = _GanStepBase._resolve_noise
-    _fed = _GanStepBase._fed
-    _feed_advance = _GanStepBase._feed_advance
-    last_noise = _GanStepBase.last_noise
-
-    def _renorm(self, x32: torch.Tensor, scale: float, rows_global: int):
-        n = x32.numel()
-        ne = self.scal[S_NE:S_NE + 1]
-        esq = self.__dict__.get("esq64")
-        if esq is None:
-            esq = self.esq64 = torch.zeros(1, dtype=torch.float64, device=x32.device)
-        lib.call("fmri_sumsq_f64", _P(x32), n, _P(esq), 1)
-        self.dd.all_reduce(esq)
-        out = torch.empty(x32.shape, dtype=torch.float16, device=x32.device)
-        lib.call("fmri_renorm_f64", _P(x32), _P(out), n, float(scale), _P(esq), float(rows_global) * (n // x32.shape[0]),
-                 None, _P(ne))
-        return out
 
     # ---- views for tests / API -----------------------------------------------------------------------------
     def logs(self):
@@ -361,6 +335,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self.torch14 = torch14_zero_grad
         self.wd = WaeDiscriminatorNet(cfg, device)
         self.opt_wd = _Optim(self.wd.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
+        self.optims.append(self.opt_wd)
         self.wscal = torch.zeros(8, dtype=torch.float32, device=device)
         self.enc_updates = 3
         self.extra_mu_decoder_pass = True
