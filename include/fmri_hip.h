@@ -635,6 +635,79 @@ int fmri_bn_cols_bwd_cnt(const void* x, const void* dy, void* dx, int M, int C, 
                          float* sums, float* dbeta, float* dgamma, float gscale, int param_stream, int* cnt,
                          void* stream);
 
+/* ---- epoch-end schedules and the per-step training log (csrc/schedule.hip; fmri_hip/schedule.py) -----------------------
+ * What the reference's loops do around every step on the host -- the epoch-end block (train/train_vgan_stage1.py:447-458,
+ * the same block in stages 2 / 3 and wae_vgan_stage1.py:456-467, `StepLR.step()` in train_wae_stage*.py) and the per-batch
+ * loss log (train_vgan_stage1.py:391-394, 434-443) -- done on the device, where the epoch of a fed step lives
+ * (fmri_sampler_advance), so that a step recorded into a HIP graph needs no host work at an epoch boundary.
+ *
+ * fmri_schedule: device-resident state, 8-byte aligned.  The values of epoch e are e iterations of
+ *     lr[i] *= lr_gamma  where the NEW epoch index is a multiple of lr_step   (torch's chainable StepLR; ExponentialLR:
+ *                                                                              lr_step = 1 -- a repeated product, not a power)
+ *     margin *= decay_margin;  equilibrium *= decay_equilibrium;  if (margin > equilibrium) equilibrium = margin;
+ *     lambda_mse *= decay_mse;  if (lambda_mse > 1) lambda_mse = 1;
+ * from the base values, in double precision -- IEEE products, no contraction possible: the same doubles on the host and
+ * on the device -- rounded to fp32 once, when handed to the kernels that read them. */
+#define FMRI_SCHED_MAX_LR 4
+typedef struct fmri_schedule {
+    double lr_base[FMRI_SCHED_MAX_LR];           /* epoch-0 values */
+    double margin_base, equilibrium_base, lambda_mse_base;
+    double lr_gamma, decay_margin, decay_equilibrium, decay_mse;
+    double lr[FMRI_SCHED_MAX_LR];                /* the values of epoch `applied_epoch` */
+    double margin, equilibrium, lambda_mse;
+    int64_t lr_step;                             /* >= 1 */
+    int64_t applied_epoch;                       /* >= 0 */
+} fmri_schedule;                                 /* 160 bytes */
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define FMRI_HOST_DEVICE __host__ __device__
+#else
+#define FMRI_HOST_DEVICE
+#endif
+/* The arithmetic itself, shared by the kernel and the host entry point below (upper-case names: inline code of this
+ * header, not symbols of the library).  FMRI_SCHEDULE_SEEK moves the state to `epoch` >= 0: nothing when it is there,
+ * the difference iterated when it is behind, a restart from the base values when it is ahead (a feed set back to an
+ * earlier epoch).  Its cost is linear in the number of epochs iterated. */
+static inline FMRI_HOST_DEVICE void FMRI_SCHEDULE_RESTART(fmri_schedule* s) {
+    for (int i = 0; i < FMRI_SCHED_MAX_LR; ++i) s->lr[i] = s->lr_base[i];
+    s->margin = s->margin_base;
+    s->equilibrium = s->equilibrium_base;
+    s->lambda_mse = s->lambda_mse_base;
+    s->applied_epoch = 0;
+}
+static inline FMRI_HOST_DEVICE void FMRI_SCHEDULE_EPOCH_END(fmri_schedule* s) {
+    const int64_t e = s->applied_epoch + 1;
+    if (e % s->lr_step == 0)
+        for (int i = 0; i < FMRI_SCHED_MAX_LR; ++i) s->lr[i] *= s->lr_gamma;
+    s->margin *= s->decay_margin;
+    s->equilibrium *= s->decay_equilibrium;
+    if (s->margin > s->equilibrium) s->equilibrium = s->margin;
+    s->lambda_mse *= s->decay_mse;
+    if (s->lambda_mse > 1.0) s->lambda_mse = 1.0;
+    s->applied_epoch = e;
+}
+static inline FMRI_HOST_DEVICE void FMRI_SCHEDULE_SEEK(fmri_schedule* s, int64_t epoch) {
+    if (epoch < s->applied_epoch) FMRI_SCHEDULE_RESTART(s);
+    while (s->applied_epoch < epoch) FMRI_SCHEDULE_EPOCH_END(s);
+}
+/* host only: FMRI_SCHEDULE_SEEK on a schedule in HOST memory -- the function the kernel evaluates; out7 (may be NULL)
+ * receives the fp32 roundings [lr[0..3], lambda_mse, equilibrium, margin].  lr_step < 1, epoch < 0: FMRI_E_BADARG. */
+int fmri_schedule_seek_host(fmri_schedule* s, int64_t epoch, float* out7);
+/* The first launch of a fed step, in front of the feed's draws (one thread): e = feed_state[1], the epoch of the batch
+ * about to be drawn (feed_state: the [seed, epoch, cursor] of fmri_sampler_indices); with sched != NULL the schedule is
+ * moved to e and its values are stored as fp32 to *lr_out[i] (each may be NULL: that optimizer is not scheduled) and
+ * hp3_out[0..2] = [lambda_mse, equilibrium, margin] (the head of the hp4_dev of fmri_compose_gate_dev; may be NULL);
+ * *epoch_out = e (may be NULL).  A negative e (never written by the sampler) is taken as 0; a schedule whose lr_step
+ * is < 1 is left alone and nothing is stored.  sched and epoch_out both NULL: FMRI_E_BADARG. */
+int fmri_epoch_begin(const int64_t* feed_state, fmri_schedule* sched, float* lr_out0, float* lr_out1, float* lr_out2,
+                     float* lr_out3, float* hp3_out, int64_t* epoch_out, void* stream);
+/* The last launch of a logged step (one wave): row (*counter mod capacity) of ring [capacity][K] fp32 receives the K
+ * values at src_dev[k] (device array of K device addresses, K <= 64), read as kind_dev[k] = 0: fp32, 1: int32, 2: int64
+ * (integers converted to fp32), then *counter += 1 (int64, 8-byte aligned, >= 0).  Plain stores, stream-ordered behind
+ * the kernels that wrote the sources; no host sync. */
+int fmri_trainlog_append(const void* const* src_dev, const int32_t* kind_dev, int K, float* ring, int64_t capacity,
+                         int64_t* counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

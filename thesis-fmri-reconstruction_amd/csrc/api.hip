@@ -1177,6 +1177,26 @@ int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream) {
     if (N < B_global) return FMRI_E_UNSUPPORTED;
     return sampler_advance_launch(state, N, B_global, S(stream));
 }
+int fmri_schedule_seek_host(fmri_schedule* s, int64_t epoch, float* out7) {
+    if (!s || s->lr_step < 1 || epoch < 0) return FMRI_E_BADARG;
+    return schedule_seek_host(s, epoch, out7);
+}
+int fmri_epoch_begin(const int64_t* feed_state, fmri_schedule* sched, float* lr_out0, float* lr_out1, float* lr_out2,
+                     float* lr_out3, float* hp3_out, int64_t* epoch_out, void* stream) {
+    if (!feed_state || ((uintptr_t)feed_state & 7) || ((uintptr_t)sched & 7) || ((uintptr_t)epoch_out & 7) ||
+        (!sched && !epoch_out))
+        return FMRI_E_BADARG;
+    if ((((uintptr_t)lr_out0 | (uintptr_t)lr_out1 | (uintptr_t)lr_out2 | (uintptr_t)lr_out3 | (uintptr_t)hp3_out) & 3))
+        return FMRI_E_BADARG;
+    return epoch_begin_launch(feed_state, sched, lr_out0, lr_out1, lr_out2, lr_out3, hp3_out, epoch_out, S(stream));
+}
+int fmri_trainlog_append(const void* const* src_dev, const int32_t* kind_dev, int K, float* ring, int64_t capacity,
+                         int64_t* counter, void* stream) {
+    if (!src_dev || ((uintptr_t)src_dev & 7) || !kind_dev || ((uintptr_t)kind_dev & 3) || K < 1 || K > 64 || !ring ||
+        ((uintptr_t)ring & 3) || capacity < 1 || !counter || ((uintptr_t)counter & 7))
+        return FMRI_E_BADARG;
+    return trainlog_append_launch(src_dev, kind_dev, K, ring, capacity, counter, S(stream));
+}
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream) {
     if (!x || !out || (n & 7)) return FMRI_E_BADARG;

@@ -273,6 +273,12 @@ int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int64_t start,
 int rng_advance_launch(int64_t* state, int64_t nblocks, hipStream_t st);
 int sampler_indices_launch(const int64_t* state, int N, int B, int64_t row0, int32_t* idx, hipStream_t st);
 int sampler_advance_launch(int64_t* state, int64_t N, int64_t B_global, hipStream_t st);
+// csrc/schedule.hip (`sched`: an fmri_schedule of include/fmri_hip.h)
+int epoch_begin_launch(const int64_t* feed_state, void* sched, float* lr0, float* lr1, float* lr2, float* lr3, float* hp3,
+                       int64_t* epoch_out, hipStream_t st);
+int schedule_seek_host(void* sched, int64_t epoch, float* out7);
+int trainlog_append_launch(const void* const* src, const int32_t* kind, int K, float* ring, int64_t capacity,
+                           int64_t* counter, hipStream_t st);
 int axpby_f16_launch(const half_t* x, const half_t* y, half_t* out, int64_t n, float a, float b, const float* pa,
                      const float* pb, hipStream_t st);
 int sumsq_launch(const float* x, int64_t n, float* acc, hipStream_t st);

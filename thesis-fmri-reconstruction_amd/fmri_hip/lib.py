@@ -102,6 +102,9 @@ _SIGS = {
     "fmri_rng_advance": [_p, _l, _p],
     "fmri_sampler_indices": [_p, _i, _i, _l, _p, _p],
     "fmri_sampler_advance": [_p, _i, _i, _p],
+    "fmri_schedule_seek_host": [_p, _l, _p],
+    "fmri_epoch_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "fmri_trainlog_append": [_p, _p, _i, _p, _l, _p, _p],
     "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
     "fmri_sumsq": [_p, _l, _p, _p],
@@ -133,6 +136,16 @@ class StatSeg(C.Structure):
                 ("gate", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_float), ("clamp", C.c_float)]
 
 
+class Schedule(C.Structure):
+    """``fmri_schedule`` of include/fmri_hip.h (the device-resident state of an epoch-end schedule)."""
+    _fields_ = [("lr_base", C.c_double * 4), ("margin_base", C.c_double), ("equilibrium_base", C.c_double),
+                ("lambda_mse_base", C.c_double), ("lr_gamma", C.c_double), ("decay_margin", C.c_double),
+                ("decay_equilibrium", C.c_double), ("decay_mse", C.c_double), ("lr", C.c_double * 4),
+                ("margin", C.c_double), ("equilibrium", C.c_double), ("lambda_mse", C.c_double),
+                ("lr_step", C.c_int64), ("applied_epoch", C.c_int64)]
+
+
+SCHED_MAX_LR = 4         # FMRI_SCHED_MAX_LR
 STAT_BYTES = 32          # sizeof(fmri_stat)
 STAT_MAX_SEGS = 8        # FMRI_STAT_MAX_SEGS
 

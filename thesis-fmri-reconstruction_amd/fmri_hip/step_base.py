@@ -11,6 +11,7 @@ import torch
 from . import lib, ops
 from .monitor import Monitored
 from .rng import DeviceRng, StepNoise
+from .schedule import EpochSchedule, TrainLog, lr_columns
 
 _P = lib.ptr
 
@@ -35,12 +36,15 @@ class _Optim:
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=group.device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=group.device) if kind == "adam" else None
         self.stats = None        # (monitor.Monitor, device address of its record pair): set by a monitored step
+        self.scheduled = False   # an attached schedule.EpochSchedule writes lr_dev (set_lr then raises)
 
     @property
     def lr(self) -> float:
         return self._lr
 
     def set_lr(self, lr: float):
+        if self.scheduled:
+            raise RuntimeError("set_lr: this optimizer's learning rate is owned by the step's EpochSchedule")
         self._lr = float(lr)
         self.lr_dev.fill_(float(lr))
 
@@ -223,7 +227,12 @@ def _attach_reducers(nets, d: _Dist):
 
 class _StepBase(Monitored):
     """What every step uses; a subclass sets ``cfg``, builds its networks, calls ``_init_step`` and ``_init_rng``,
-    registers its optimizers in ``optims`` and defines ``step``."""
+    registers its optimizers in ``optims``, calls ``_init_schedule`` / ``_init_log`` and defines ``step`` (which starts
+    with ``_fed`` and ends with ``_log_append``)."""
+
+    schedule: Optional[EpochSchedule] = None
+    log: Optional[TrainLog] = None
+    _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
         self.device = torch.device(device)
@@ -242,13 +251,70 @@ class _StepBase(Monitored):
         self.feed = feed             # fmri_hip.feed.DeviceFeed or None
         self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
 
+    def _init_schedule(self, schedule: Optional[EpochSchedule], default_mask=None, hp=None, hp_dev=None):
+        """``schedule=`` of the step classes (fmri_hip/schedule.py), after ``optims`` is complete.  ``default_mask``: which
+        optimizers follow the lr schedule unless the schedule says otherwise (default: all); ``hp`` / ``hp_dev``: the
+        VAE/GAN hyper-parameters and their device block, None for a step that has none."""
+        self.schedule = schedule
+        if schedule is None:
+            return
+        if self.feed is None:
+            raise ValueError(f"{type(self).__name__}: schedule= needs feed=DeviceFeed(...): the feed is where the epoch "
+                             "lives")
+        mask = [True] * len(self.optims) if default_mask is None else default_mask
+        schedule.attach(self.feed, self.optims, mask, hp, hp_dev)
+
+    def _log_columns(self):
+        """(column name, persistent device tensor, element index) of everything ``logs()`` returns, in its order -- each
+        step class states its layout once, here -- and the names among them that are losses."""
+        raise NotImplementedError
+
+    def _init_log(self, log: Optional[TrainLog]):
+        """``log=`` of the step classes, after ``optims`` is complete: the class's ``_log_columns`` + ``epoch`` (of the
+        batch the step drew; -1 without a feed) + the learning rate of every entry of ``optims``."""
+        self.log = log
+        if log is None:
+            return
+        cols, losses = self._log_columns()
+        self._epoch_dev = torch.full((1,), -1, dtype=torch.int64, device=self.device)
+        log.attach(self.device, list(cols) + [("epoch", self._epoch_dev, 0)] + lr_columns(self.optims), losses)
+
+    def _epoch_begin(self):
+        """The launch in FRONT of the feed's draws: the feed's state still holds the epoch of the batch about to be drawn.
+        Moves the schedule there and / or notes the epoch for the log; nothing for a step with neither."""
+        noted = self._epoch_dev if self.feed is not None else None
+        if self.schedule is not None:
+            self.schedule.launch(noted)
+        elif noted is not None:
+            lib.call("fmri_epoch_begin", _P(self.feed._state), None, None, None, None, None, None, _P(noted))
+
+    def _log_append(self):
+        """The last launch of a step: behind the gate, the loss all-reduce and every kernel that writes a logged value."""
+        if self.log is not None:
+            self.log.append()
+
+    def history(self):
+        """``log=TrainLog(...)``: the logged steps (ONE sync): name -> numpy array, oldest first, the last
+        min(steps, capacity) steps -- per step exactly what ``logs()`` would have returned after it, ``epoch`` (of the
+        batch it drew, -1 without a feed), the learning rates of ``optims`` (``lr_encoder`` ...) and ``step``, the
+        absolute step numbers."""
+        if self.log is None:
+            raise RuntimeError("history(): the step was constructed without log=TrainLog(...)")
+        return self.log.history()
+
+    def epoch_means(self):
+        """Per epoch present in the log's ring: the mean of every loss over the steps held (TrainLog.epoch_means)."""
+        if self.log is None:
+            raise RuntimeError("epoch_means(): the step was constructed without log=TrainLog(...)")
+        return self.log.epoch_means()
+
     def _fed(self, *given):
         """The batch of a step.  Without a feed: ``given`` (the caller's batch tensors) must all be there; returns None.
         With a feed: none may be; the feed enqueues its next batch (fmri_hip/feed.py) -- the first launches of the step,
         so they sit in the one graph of a recording, or in the first segment of a data-parallel one -- and its buffers
         (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
         generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
-        the noise and the augmentation draws."""
+        the noise and the augmentation draws.  A schedule / log puts ONE launch in front of the feed's (``_epoch_begin``)."""
         feed = self.feed
         if feed is None:
             if any(g is None for g in given):
@@ -259,6 +325,7 @@ class _StepBase(Monitored):
             raise ValueError(f"{type(self).__name__}: the step has a feed and draws its own batch: step() takes no "
                              "batch arguments")
         shared = feed.rng is not None and feed.rng is self.rng
+        self._epoch_begin()
         x, fm, _ = feed.next(advance_rng=not shared)
         self._feed_blocks = feed.rng_blocks() if shared else 0
         return x, fm, feed.fmri16
@@ -333,7 +400,8 @@ class _StepBase(Monitored):
         gate, the stream normalisation and the optimizer gating all live on the device), so the ~370 launches of a
         step can be replayed as one graph: the step time then no longer depends on how fast the host can issue them.
         Inputs are read from ``static_inputs`` at every replay -- copy each new batch into those tensors.  Learning
-        rates, lambda, margin, equilibrium and beta are device-resident (``set_lr`` / ``set_hyper``): a replayed step follows
+        rates, lambda, margin, equilibrium and beta are device-resident (``set_lr`` / ``set_hyper``, or a ``schedule=`` that
+        applies the epoch-end block on the device, fmri_hip/schedule.py): a replayed step follows
         their schedules (Adam's step count of the WAE steps lives on the device too, ``wae_steps``).  In a data-parallel run the collectives
         are kept out of the graphs (see _SegmentRecorder)."""
         # The weight-gradient side stream (ops.side_run) is switched off while recording: a replayed HIP graph runs

@@ -96,8 +96,20 @@ class _GanStepBase(_StepBase):
     def set_hyper(self, lr: Optional[float] = None, lambda_mse: Optional[float] = None,
                   equilibrium: Optional[float] = None, margin: Optional[float] = None, beta: Optional[float] = None):
         """The epoch-end updates of the scripts (lr_*.step(), margin *= decay_margin, equilibrium *= decay_equilibrium,
-        lambda_mse *= decay_mse; train_vgan_stage1.py:448-458) -- host copies and the device values the kernels read."""
+        lambda_mse *= decay_mse; train_vgan_stage1.py:448-458) -- host copies and the device values the kernels read.
+        A step built with ``schedule=`` makes those updates itself, on the device: lr / lambda_mse / equilibrium / margin
+        then belong to the schedule (RuntimeError) and ``self.hp`` keeps the BASE values the schedule started from
+        (``schedule.values()`` has the current ones); ``beta`` is not scheduled and is set as ever."""
         hp = self.hp
+        if self.schedule is not None:
+            owned = [n for n, v in (("lr", lr), ("lambda_mse", lambda_mse), ("equilibrium", equilibrium),
+                                    ("margin", margin)) if v is not None]
+            if owned:
+                raise RuntimeError(f"set_hyper({', '.join(owned)}): owned by the step's EpochSchedule")
+            if beta is not None:
+                hp.beta = float(beta)
+                self.hp_dev[3:4].fill_(hp.beta)
+            return
         if lr is not None:
             hp.lr = float(lr)
             # encoder, decoder, discriminator: the Dual step's latent discriminator (registered fourth) keeps its rate
@@ -172,6 +184,15 @@ class _GanStepBase(_StepBase):
             dhead32[:, :Z].addcmul_(extra_dmu, norm)
         return self._renorm(dhead32, self.sc.enc, norm, B * self.dd.world)
 
+    def _log_columns(self):
+        cols = [(k, self.scal, i) for i, k in enumerate(LOG_KEYS)]
+        return cols + [("train_dis", self.flags, 0), ("train_dec", self.flags, 1)], LOG_KEYS
+
+    def _init_extras(self, schedule, log):
+        """``schedule=`` / ``log=`` once ``optims`` is complete.  lr: encoder, decoder, discriminator, as ``set_hyper``."""
+        self._init_schedule(schedule, [i < 3 for i in range(len(self.optims))], self.hp, self.hp_dev)
+        self._init_log(log)
+
     def logs(self):
         v = self.scal.tolist()
         out = {k: v[i] for i, k in enumerate(LOG_KEYS)}
@@ -185,8 +206,13 @@ class Stage1Step(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
-                 monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
+                 monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``); the epoch-end block of the scripts -- lr decay,
+        margin / equilibrium / lambda_mse decays with their clamps -- then happens on the device, as the first launch of
+        the step whose batch opens a new epoch, recorded steps included; ``self.hp`` keeps the base values.
+        ``log``: a fmri_hip.schedule.TrainLog; the last launch of every step then appends what ``logs()`` would return, the
+        batch's epoch and the learning rates to a device ring -- ``history()`` / ``epoch_means()`` read it with one sync.
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps`` and ``z_p`` on the device (``last_noise()``)
         and a step recorded with ``capture(x)`` draws fresh noise at every replay.  Noise passed to ``step`` is used as
         it is, with or without ``rng``.
@@ -221,6 +247,7 @@ class Stage1Step(_GanStepBase):
         self.extra_mu_decoder_pass = False   # DualStage1Step (wae_steps.py)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
+        self._init_extras(schedule, log)
 
     # ---- parameters -----------------------------------------------------------------------------
     def _subnets(self):
@@ -475,6 +502,7 @@ class Stage1Step(_GanStepBase):
                 self.gate(B * self.dd.world)
             self.backward(early_apply=True)
             self.apply()
+            self._log_append()
             return self.scal
         self._fwd_graph = graph
         return run
@@ -489,6 +517,7 @@ class Stage1Step(_GanStepBase):
         self.gate(fw["B"] * self.dd.world)
         self.backward(early_apply=True)
         self.apply()
+        self._log_append()
         return self.scal
 
     # ---- reference-shaped views of the last forward (API / parity tests) -----------------------------
@@ -526,8 +555,9 @@ class CognitiveStep(_GanStepBase):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
-                 rng: Optional[DeviceRng] = None, feed=None):
+                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``schedule`` / ``log``: device-side epoch-end schedule and per-step training log (see Stage1Step).
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(fmri, image)`` then draws ``eps``, ``z_p`` and -- where the teacher
         samples (stage 2, mode 'vae-gan') -- ``eps_teacher`` on the device (see Stage1Step).
         ``feed``: a fmri_hip.feed.DeviceFeed over a dataset with fMRI rows; ``step()`` then draws the image and the fMRI
@@ -562,6 +592,7 @@ class CognitiveStep(_GanStepBase):
         self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.cog), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
+        self._init_extras(schedule, log)
 
     def load_recipe(self, seed: int, perturb: bool = False):
         """Teacher VaeGan weights from seed, cognitive encoder from seed+100 (the golden-fixture recipe)."""
@@ -749,6 +780,7 @@ class CognitiveStep(_GanStepBase):
         self.gate(fw["B"] * self.dd.world)
         self.backward(fuse=True)
         self.apply()
+        self._log_append()
         return self.scal
 
     def outputs(self):

@@ -104,8 +104,13 @@ class WaeStep(_LatentDiscPhase, _StepBase):
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
-                 penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
+                 penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
+                 schedule=None, log=None):
         """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``) -- the scripts' three ``StepLR(step_size, gamma)``
+        (train_wae_stage1.py:226-228, 334-336) on the device; all three optimizers follow it unless ``lr_mask`` says
+        otherwise, and a margin / equilibrium / lambda_mse decay is a ValueError (a WAE step has none of them).
+        ``log``: a fmri_hip.schedule.TrainLog (see steps.Stage1Step).
         ``rng``: a fmri_hip.rng.DeviceRng; Stage I's ``step(x)`` then draws ``z_fake_noise`` on the device (see
         steps.Stage1Step; Stages II / III take no noise).
         ``feed``: a fmri_hip.feed.DeviceFeed (Stages II / III: over a dataset with fMRI rows); ``step()`` then draws its
@@ -135,6 +140,8 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         self._init_rng(rng, feed)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.wd)], 1)
+        self._init_schedule(schedule)
+        self._init_log(log)
 
     # ---- parameters (the golden-fixture recipes of tests/golden/make_golden.py) --------------------------
     def load_recipe(self, seed: int, perturb: Optional[bool] = None):
@@ -264,6 +271,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         self.fw = dict(B=B, y=y, head32=head32, Z=Z)
         if self.mon is not None:
             self.mon.tail(head32, Z, [self.scal[:len(W_LOG_KEYS)]], None)
+        self._log_append()
         return self.scal
 
     def _mmd_penalty(self, head32, p32, w: float, need_dz: bool):
@@ -290,6 +298,9 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         return dq[rank * B:(rank + 1) * B] if dd.on else dq
 
     # ---- views for tests / API -----------------------------------------------------------------------------
+    def _log_columns(self):
+        return [(k, self.scal, i) for i, k in enumerate(W_LOG_KEYS)], W_LOG_KEYS
+
     def logs(self):
         v = self.scal.tolist()
         return {k: v[i] for i, k in enumerate(W_LOG_KEYS)}
@@ -326,9 +337,15 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
-                 mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None):
+                 mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
+                 schedule=None, log=None):
         """``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
-        (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step)."""
+        (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step).
+        ``schedule`` / ``log``: see Stage1Step.  By default the lr schedule covers what ``set_hyper(lr=)`` covers:
+        encoder, decoder and image discriminator; the latent discriminator (registered fourth) keeps its rate.  The
+        script itself rebinds ``lr_discriminator`` to the LATENT discriminator's scheduler (wae_vgan_stage1.py:246-250), so
+        there the image discriminator's rate never decays and the latent discriminator's does:
+        ``EpochSchedule(..., lr_mask=(True, True, False, True))`` reproduces that literally."""
         super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng, feed=feed)
         hp = self.hp
         self.lam = lam
@@ -343,6 +360,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis),
                                      ("wae_discriminator", self.opt_wd, self.wd)], 2)
+        self._init_extras(schedule, log)         # (the base constructor ran with neither: ``optims`` was not complete)
 
     def _monitor_losses(self):
         return [self.scal[:len(LOG_KEYS)], self.wscal[:len(W_LOG_KEYS)]]
@@ -379,7 +397,14 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self._it += 1
         self.backward(extra_dmu=dz_pen)
         self.apply()
+        self._log_append()
         return self.scal
+
+    def _log_columns(self):
+        cols, losses = super()._log_columns()
+        extra = [("loss_penalty", self.wscal, W_PEN), ("loss_discriminator_fake", self.wscal, W_DFAKE),
+                 ("loss_discriminator_real", self.wscal, W_DREAL)]
+        return cols + extra, tuple(losses) + tuple(n for n, _, _ in extra)
 
     def logs(self):
         out = super().logs()
