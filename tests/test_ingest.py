@@ -1,10 +1,12 @@
-"""Batch ingest: oracle against the golden, HIP kernel against the oracle (bit-exact up to the fp16 store)."""
+"""Batch ingest: oracle against the golden, HIP kernel against the oracle (per element, inside the bound the
+number formats give: tests/glue_oracle.py::ingest64)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import glue_oracle as GO
 from oracle import ingest_oracle as IO
 
 
@@ -25,8 +27,13 @@ def test_ingest_hip_matches_oracle(golden_dir):
         o16, o32 = ingest_u8(img, flip=flip, shift=shift, want16=True, want32=True)
         ref = g[f"{tag}/out"]
         np.testing.assert_allclose(o32.cpu().numpy(), ref, rtol=0, atol=2e-7)       # (v/255 - m) * (1/std) vs / std
-        r16 = torch.from_numpy(ref).permute(0, 2, 3, 1).half()
-        assert torch.equal(o16[..., :3].cpu(), r16) or (o16[..., :3].cpu().float() - r16.float()).abs().max() < 1e-3
+        # fp16 output: every element within the fp32 error of (p * fl(1/255) - m) * fl(1/std) plus the fp16 store of the
+        # float64 value of (p / 255 - m) / std at the oracle's pixel; lanes 3..7 exactly zero
+        pix = GO.ingest_pixels(g[f"{tag}/img"], g[f"{tag}/flip"], g[f"{tag}/shift"])
+        res = GO.cmp_ingest(pix, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), o16=o16.cpu().numpy(), o32=o32.cpu().numpy())
+        for ln in GO.lines(f"ingest golden {tag}", res):
+            print(ln)
+        assert GO.passed(res), res
         assert (o16[..., 3:] == 0).all()
     # larger batch without augmentation, ImageNet statistics
     rs = np.random.RandomState(3)
