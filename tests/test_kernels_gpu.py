@@ -589,7 +589,9 @@ def test_dense_second_orientation_is_the_transpose(M, K, N, in_perm, out_perm):
     assert torch.equal(got, ref)
 
 
-@pytest.mark.parametrize("M,C", [(3 * 64 * 64, 32), (600, 128), (2 * 13 * 13, 256), (7, 1024), (5, 16384), (12, 512)])
+# (2049, 8), (4100, 24), (2100, 2056): the streaming path with one chunk column, an idle chunk column, two block columns
+@pytest.mark.parametrize("M,C", [(3 * 64 * 64, 32), (600, 128), (2 * 13 * 13, 256), (7, 1024), (5, 16384), (12, 512),
+                                 (2049, 8), (4100, 24), (2100, 2056)])
 def test_batchnorm_forward_backward(M, C):
     from fmri_hip.ops import BatchNorm
     torch.manual_seed(M + C)
@@ -623,7 +625,7 @@ def test_batchnorm_forward_backward(M, C):
     _close(g.grads["bn.bias"].cpu() * 8.0, br.grad, "bn dbeta", tol=3e-3)
 
 
-@pytest.mark.parametrize("M,C", [(3 * 32 * 32, 128), (600, 256), (37, 64)])
+@pytest.mark.parametrize("M,C", [(3 * 32 * 32, 128), (600, 256), (37, 64), (2049, 8), (4100, 24), (2100, 2056)])
 def test_batchnorm_backward_two_streams(M, C):
     """``BatchNorm.backward2`` (two stacked cotangent streams, the forward tensor read once) against autograd on the two
     cotangents separately; gamma / beta gradients come from stream A only."""
@@ -659,6 +661,30 @@ def test_batchnorm_backward_two_streams(M, C):
     bn.backward2(x16, dy2, sv, relu=True, param_scale=2.0, param_stream=1)
     _close(g.grads["bn.weight"].cpu() * 2.0, ref[1][1], "bn dgamma (B only)", tol=3e-3)
     _close(g.grads["bn.bias"].cpu() * 2.0, ref[1][2], "bn dbeta (B only)", tol=3e-3)
+
+
+@pytest.mark.parametrize("M,C", [(37, 64), (2049, 64)])
+def test_batchnorm_two_streams_equal_one_stream_bitwise(M, C):
+    """``backward2([A | B])`` is ``backward(A)`` and ``backward(B)`` bit for bit, dx and the rows of ``sums``, in the
+    one-launch column path (37 rows) and in the streaming path (2049 rows): the kernels are one template over the stream
+    count, with the same per-thread row order and the same grid for either count.  The streaming kernels spell the ReLU
+    mask differently per count (csrc/norm.hip), and this test is what holds the two spellings to the same values."""
+    from fmri_hip.ops import BatchNorm
+    torch.manual_seed(M * 5 + C)
+    gamma = 1 + 0.2 * torch.randn(C)
+    beta = 0.1 * torch.randn(C)
+    g = _G({"bn.weight": gamma, "bn.bias": beta})
+    g.bufs = {"bn.running_mean": torch.zeros(C, device=DEV), "bn.running_var": torch.ones(C, device=DEV),
+              "bn.num_batches_tracked": torch.zeros((), dtype=torch.int64, device=DEV)}
+    bn = BatchNorm(g, "bn.", C)
+    x16 = (torch.randn(M, C) * 1.2 - 0.2).half().to(DEV)
+    _, sv = bn.forward(x16, relu=True, updates=0)
+    dy2 = torch.cat([torch.randn(M, C), torch.randn(M, C) * 0.5], 0).half().to(DEV)
+    dx2, sums2 = bn.backward2(x16, dy2, sv, relu=True, param_scale=4.0)
+    for s in range(2):
+        dx1, sums1 = bn.backward(x16, dy2[s * M:(s + 1) * M].contiguous(), sv, relu=True, param_scale=4.0)
+        assert torch.equal(dx2[s * M:(s + 1) * M].view(torch.int16), dx1.view(torch.int16)), f"dx of stream {s}"
+        assert torch.equal(sums2[2 * s:2 * s + 2].view(torch.int32), sums1.view(torch.int32)), f"sums of stream {s}"
 
 
 def test_batchnorm_permuted_features():

@@ -868,48 +868,52 @@ int fmri_bn_stats(const void* x, int M, int C, float* sums2C, float* ws, int64_t
     if (!x || !sums2C || (C & 7) || M < 1) return FMRI_E_BADARG;
     return bn_stats_launch((const half_t*)x, M, C, sums2C, ws, ws_floats, S(stream));
 }
+// the finalize arguments of an entry point (in_scale: null = rows stored at true scale)
+static BnFinalize bn_fin(const float* gamma, const float* beta, float eps, float momentum, int updates,
+                         float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
+                         int64_t* num_batches_tracked, const float* in_scale = nullptr) {
+    return {gamma, beta, eps, momentum, updates, running_mean, running_var, mean, rstd, scale, shift,
+            (long long*)num_batches_tracked, in_scale};
+}
+static bool bn_fin_ok(const BnFinalize& f) { return f.gamma && f.beta && f.mean && f.rstd && f.scale && f.shift; }
+
 int fmri_bn_finalize(const float* sums2C, int C, float count, const float* gamma, const float* beta, float eps,
                      float momentum, int updates, float* running_mean, float* running_var, float* mean, float* rstd,
                      float* scale, float* shift, int64_t* num_batches_tracked, void* stream) {
-    if (!sums2C || !gamma || !beta || !mean || !rstd || !scale || !shift) return FMRI_E_BADARG;
-    return bn_finalize_launch(sums2C, C, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean,
-                              rstd, scale, shift, (long long*)num_batches_tracked, nullptr, S(stream));
+    return fmri_bn_finalize_s(sums2C, C, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean,
+                              rstd, scale, shift, num_batches_tracked, nullptr, stream);
 }
 int fmri_bn_finalize_s(const float* sums2C, int C, float count, const float* gamma, const float* beta, float eps,
                        float momentum, int updates, float* running_mean, float* running_var, float* mean, float* rstd,
                        float* scale, float* shift, int64_t* num_batches_tracked, const float* in_scale, void* stream) {
-    if (!sums2C || !gamma || !beta || !mean || !rstd || !scale || !shift) return FMRI_E_BADARG;
-    return bn_finalize_launch(sums2C, C, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean,
-                              rstd, scale, shift, (long long*)num_batches_tracked, in_scale, S(stream));
+    const BnFinalize f = bn_fin(gamma, beta, eps, momentum, updates, running_mean, running_var, mean, rstd, scale,
+                                shift, num_batches_tracked, in_scale);
+    if (!sums2C || !bn_fin_ok(f)) return FMRI_E_BADARG;
+    return bn_finalize_launch(sums2C, C, count, f, S(stream));
 }
 int fmri_bn_stats_finalize(const void* x, int M, int C, float* sums2C, float* ws, int64_t ws_floats, float count,
                            const float* gamma, const float* beta, float eps, float momentum, int updates,
                            float* running_mean, float* running_var, float* mean, float* rstd, float* scale,
                            float* shift, int64_t* num_batches_tracked, void* stream) {
-    if (!x || !sums2C || (C & 7) || M < 1 || !gamma || !beta || !mean || !rstd || !scale || !shift)
-        return FMRI_E_BADARG;
-    return bn_stats_finalize_launch((const half_t*)x, M, C, sums2C, ws, ws_floats, count, gamma, beta, eps, momentum,
-                                    updates, running_mean, running_var, mean, rstd, scale, shift,
-                                    (long long*)num_batches_tracked, S(stream));
+    const BnFinalize f = bn_fin(gamma, beta, eps, momentum, updates, running_mean, running_var, mean, rstd, scale,
+                                shift, num_batches_tracked);
+    if (!x || !sums2C || (C & 7) || M < 1 || !bn_fin_ok(f)) return FMRI_E_BADARG;
+    return bn_stats_finalize_launch((const half_t*)x, M, C, sums2C, ws, ws_floats, count, f, S(stream));
 }
 int fmri_bn_cols_fwd(const void* x, void* y, int M, int C, float count, const float* gamma, const float* beta, float eps,
                      float momentum, int updates, float* running_mean, float* running_var, float* mean, float* rstd,
                      float* scale, float* shift, float* sums2C, int64_t* num_batches_tracked, int relu, void* stream) {
-    if (!x || !y || !sums2C || (C & 7) || C < 8 || M < 1 || !gamma || !beta || !mean || !rstd || !scale || !shift)
-        return FMRI_E_BADARG;
-    return bn_cols_fwd_launch((const half_t*)x, (half_t*)y, M, C, count, gamma, beta, eps, momentum, updates, running_mean,
-                              running_var, mean, rstd, scale, shift, sums2C, (long long*)num_batches_tracked, relu,
-                              nullptr, S(stream));
+    return fmri_bn_cols_fwd_s(x, y, M, C, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean,
+                              rstd, scale, shift, sums2C, num_batches_tracked, relu, nullptr, stream);
 }
 int fmri_bn_cols_fwd_s(const void* x, void* y, int M, int C, float count, const float* gamma, const float* beta, float eps,
                        float momentum, int updates, float* running_mean, float* running_var, float* mean, float* rstd,
                        float* scale, float* shift, float* sums2C, int64_t* num_batches_tracked, int relu,
                        const float* in_scale, void* stream) {
-    if (!x || !y || !sums2C || (C & 7) || C < 8 || M < 1 || !gamma || !beta || !mean || !rstd || !scale || !shift)
-        return FMRI_E_BADARG;
-    return bn_cols_fwd_launch((const half_t*)x, (half_t*)y, M, C, count, gamma, beta, eps, momentum, updates, running_mean,
-                              running_var, mean, rstd, scale, shift, sums2C, (long long*)num_batches_tracked, relu,
-                              in_scale, S(stream));
+    const BnFinalize f = bn_fin(gamma, beta, eps, momentum, updates, running_mean, running_var, mean, rstd, scale,
+                                shift, num_batches_tracked, in_scale);
+    if (!x || !y || !sums2C || (C & 7) || C < 8 || M < 1 || !bn_fin_ok(f)) return FMRI_E_BADARG;
+    return bn_cols_fwd_launch((const half_t*)x, (half_t*)y, M, C, count, f, sums2C, relu, S(stream));
 }
 int fmri_bn_cols_bwd(const void* x, const void* dy, void* dx, int M, int C, int nstreams, float count, const float* mean,
                      const float* rstd, const float* gamma, const float* beta, int relu, float* sums, float* dbeta,
@@ -934,11 +938,10 @@ int fmri_bn_fold_finalize(const float* stat_part, int rows, int C, float* scratc
                           const float* gamma, const float* beta, float eps, float momentum, int updates,
                           float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
                           int64_t* num_batches_tracked, void* stream) {
-    if (!stat_part || rows < 1 || C < 1 || !scratch || !sums2C || !gamma || !beta || !mean || !rstd || !scale || !shift)
-        return FMRI_E_BADARG;
-    return bn_fold_finalize_launch(stat_part, rows, C, scratch, sums2C, count, gamma, beta, eps, momentum, updates,
-                                   running_mean, running_var, mean, rstd, scale, shift, (long long*)num_batches_tracked,
-                                   S(stream));
+    const BnFinalize f = bn_fin(gamma, beta, eps, momentum, updates, running_mean, running_var, mean, rstd, scale,
+                                shift, num_batches_tracked);
+    if (!stat_part || rows < 1 || C < 1 || !scratch || !sums2C || !bn_fin_ok(f)) return FMRI_E_BADARG;
+    return bn_fold_finalize_launch(stat_part, rows, C, scratch, sums2C, count, f, S(stream));
 }
 int fmri_bn_fold(const float* stat_part, int rows, int C, float* scratch, float* sums2C, void* stream) {
     if (!stat_part || rows < 1 || C < 1 || !scratch || !sums2C) return FMRI_E_BADARG;
@@ -961,42 +964,42 @@ int fmri_bn_bwd_reduce(const void* x, const void* dy, int M, int C, const float*
                        const float* gamma, const float* beta, int relu, float* sums2C, float* ws,
                        int64_t ws_floats, float* dbeta, float* dgamma, float gscale, void* stream) {
     if (!x || !dy || !sums2C || (C & 7)) return FMRI_E_BADARG;
-    return bn_bwd_reduce_launch((const half_t*)x, (const half_t*)dy, M, C, mean, rstd, gamma, beta, relu, sums2C, ws,
-                                ws_floats, dbeta, dgamma, gscale, S(stream));
+    return bn_bwd_reduce_launch((const half_t*)x, (const half_t*)dy, M, C, 1, mean, rstd, gamma, beta, relu, sums2C, ws,
+                                ws_floats, dbeta, dgamma, gscale, 0, S(stream));
 }
 int fmri_bn_bwd_reduce2(const void* x, const void* dy2, int M, int C, const float* mean, const float* rstd,
                         const float* gamma, const float* beta, int relu, float* sums4C, float* ws, int64_t ws_floats,
                         float* dbeta, float* dgamma, float gscale, int param_stream, void* stream) {
     if (!x || !dy2 || !sums4C || (C & 7) || M < 1 || (param_stream & ~1)) return FMRI_E_BADARG;
-    return bn_bwd_reduce2_launch((const half_t*)x, (const half_t*)dy2, M, C, mean, rstd, gamma, beta, relu, sums4C, ws,
-                                 ws_floats, dbeta, dgamma, gscale, param_stream, S(stream));
+    return bn_bwd_reduce_launch((const half_t*)x, (const half_t*)dy2, M, C, 2, mean, rstd, gamma, beta, relu, sums4C, ws,
+                                ws_floats, dbeta, dgamma, gscale, param_stream, S(stream));
 }
 int fmri_bn_bwd_apply2(const void* x, const void* dy2, void* dx2, int M, int C, float count, const float* mean,
                        const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
                        void* stream) {
     if (!x || !dy2 || !dx2 || !sums4C || (C & 7) || M < 1) return FMRI_E_BADARG;
-    return bn_bwd_apply2_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, count, mean, rstd, gamma, beta,
-                                relu, sums4C, nullptr, S(stream));
+    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, 2, count, mean, rstd, gamma, beta,
+                               relu, sums4C, nullptr, S(stream));
 }
 int fmri_bn_bwd_apply(const void* x, const void* dy, void* dx, int M, int C, float count, const float* mean,
                       const float* rstd, const float* gamma, const float* beta, int relu, const float* sums2C,
                       void* stream) {
     if (!x || !dy || !dx || (C & 7)) return FMRI_E_BADARG;
-    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, count, mean, rstd, gamma, beta,
+    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, 1, count, mean, rstd, gamma, beta,
                                relu, sums2C, nullptr, S(stream));
 }
 int fmri_bn_bwd_apply2_cnt(const void* x, const void* dy2, void* dx2, int M, int C, float count, const float* mean,
                            const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
                            int* cnt, void* stream) {
     if (!cnt || !x || !dy2 || !dx2 || !sums4C || (C & 7) || M < 1) return FMRI_E_BADARG;
-    return bn_bwd_apply2_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, count, mean, rstd, gamma, beta,
-                                relu, sums4C, cnt, S(stream));
+    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy2, (half_t*)dx2, M, C, 2, count, mean, rstd, gamma, beta,
+                               relu, sums4C, cnt, S(stream));
 }
 int fmri_bn_bwd_apply_cnt(const void* x, const void* dy, void* dx, int M, int C, float count, const float* mean,
                           const float* rstd, const float* gamma, const float* beta, int relu, const float* sums2C,
                           int* cnt, void* stream) {
     if (!cnt || !x || !dy || !dx || (C & 7)) return FMRI_E_BADARG;
-    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, count, mean, rstd, gamma, beta,
+    return bn_bwd_apply_launch((const half_t*)x, (const half_t*)dy, (half_t*)dx, M, C, 1, count, mean, rstd, gamma, beta,
                                relu, sums2C, cnt, S(stream));
 }
 int fmri_act_bwd(const void* y, const void* dy, void* dpre, int M, int C, int act, float* colsum2C, float* ws,

@@ -185,44 +185,42 @@ int reduce_slabs_launch(const float* slabs, int nslabs, int64_t slab_stride, int
 int permute_chw_launch(const float* s, float* d, int C, int HW, int to_engine, float scale, int accumulate,
                        hipStream_t st);
 
+// What a BatchNorm finalize reads and writes besides the batch sums and their count (bn_finalize_channel, norm.hip).
+// api.hip fills one per entry point; it travels by value down to the kernels.
+struct BnFinalize {
+    const float *gamma, *beta;
+    float eps, momentum;
+    int updates;                            // consecutive running-statistics updates of this call (0: none)
+    float *running_mean, *running_var;      // may be null
+    float *mean, *rstd, *scale, *shift;     // outputs, C floats each
+    long long* nbt;                         // num_batches_tracked, += updates (may be null)
+    const float* in_scale;                  // device scalar s of range-scaled rows s * x (null: s = 1)
+};
 int64_t bn_ws_floats(int M, int C);
 int bn_stats_launch(const half_t* x, int M, int C, float* sums, float* ws, int64_t ws_floats, hipStream_t st);
-int bn_bwd_reduce2_launch(const half_t* x, const half_t* dy, int M, int C, const float* mean, const float* rstd,
-                          const float* gamma, const float* beta, int relu, float* sums4C, float* ws, int64_t ws_floats,
-                          float* dbeta, float* dgamma, float gscale, int param_stream, hipStream_t st);
-int bn_bwd_apply2_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
-                         const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
-                         int* cnt, hipStream_t st);
 int bn_stats_finalize_launch(const half_t* x, int M, int C, float* sums, float* ws, int64_t ws_floats, float count,
-                             const float* gamma, const float* beta, float eps, float momentum, int updates, float* rm,
-                             float* rv, float* mean, float* rstd, float* scale, float* shift, long long* nbt,
-                             hipStream_t st);
-int bn_bwd_reduce_launch(const half_t* x, const half_t* dy, int M, int C, const float* mean, const float* rstd,
-                         const float* gamma, const float* beta, int relu, float* sums, float* ws, int64_t ws_floats,
-                         float* dbeta, float* dgamma, float gscale, hipStream_t st);
+                             const BnFinalize& f, hipStream_t st);
 constexpr int FOLD_STAGE_ROWS = 32;     // rows of the intermediate buffer of a two-stage statistics fold
 int bn_fold_finalize_launch(const float* part, int rows, int C, float* scratch, float* sums, float count,
-                            const float* gamma, const float* beta, float eps, float momentum, int updates, float* rm,
-                            float* rv, float* mean, float* rstd, float* scale, float* shift, long long* nbt,
-                            hipStream_t st);
+                            const BnFinalize& f, hipStream_t st);
 int bn_fold_launch(const float* part, int rows, int n, float* scratch, float* sums, hipStream_t st);
 int bn_bwd_fold_launch(const float* part, int rows, int rows_cap, int C, int G, float* scratch, float* sums,
                        float* dbeta, float* dgamma, float gscale, int pgroup, hipStream_t st);
-int bn_finalize_launch(const float* sums, int C, float count, const float* gamma, const float* beta, float eps,
-                       float momentum, int updates, float* rm, float* rv, float* mean, float* rstd, float* scale,
-                       float* shift, long long* nbt, const float* in_scale, hipStream_t st);
-int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, const float* gamma, const float* beta,
-                       float eps, float momentum, int updates, float* rm, float* rv, float* mean, float* rstd,
-                       float* scale, float* shift, float* sums2C, long long* nbt, int relu, const float* in_scale,
-                       hipStream_t st);
+int bn_finalize_launch(const float* sums, int C, float count, const BnFinalize& f, hipStream_t st);
+int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, const BnFinalize& f, float* sums2C,
+                       int relu, hipStream_t st);
 int bn_cols_bwd_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, float* sums,
                        float* dbeta, float* dgamma, float gscale, int pstream, int* cnt, hipStream_t st);
 int bn_apply_launch(const half_t* x, half_t* y, int M, int C, const float* scale, const float* shift, int relu,
                     hipStream_t st);
-int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
-                        const float* rstd, const float* gamma, const float* beta, int relu, const float* sums,
-                        int* cnt, hipStream_t st);
+// backward of nstreams (1 or 2) cotangent streams stacked along the rows of dy / dx; sums [nstreams][2][C]
+int bn_bwd_reduce_launch(const half_t* x, const half_t* dy, int M, int C, int nstreams, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, int relu, float* sums, float* ws,
+                         int64_t ws_floats, float* dbeta, float* dgamma, float gscale, int param_stream, hipStream_t st);
+int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
+                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
+                        const float* sums, int* cnt, hipStream_t st);
 int act_bwd_launch(const half_t* y, const half_t* dy, half_t* dpre, int M, int C, int act, float* colsum, float* ws,
                    int64_t ws_floats, float* dbias, int dbias_n, float gscale, hipStream_t st);
 int colsum_rows_launch(const half_t* x, int M, int C, float* sums2C, float* ws, int64_t ws_floats, float* dbias,

@@ -15,6 +15,12 @@
 // are unrolled x4 to keep 4 independent 16-byte loads in flight per lane.  Reductions write per-block
 // partials to a workspace and a second tiny kernel folds them (no float atomics: 2048 blocks adding
 // into the same 2*C words serialise at the memory side).
+//
+// The backward exists once per direction, templated on the number NS of cotangent streams that share one saved forward
+// (bn_bwd_reduce_kernel<NS>, bn_bwd_apply_kernel<NS, COUNT>, bn_cols_bwd_kernel<NS, COUNT>; COUNT: the numerics
+// monitor), and every fold of partial rows runs through fold_columns.
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace fmri {
@@ -41,8 +47,6 @@ static RowGeom row_geometry(int M, int C, int max_gy) {
     return g;
 }
 
-// MODE 0: sum x, sum x^2.  MODE 1: sum g, sum g*xhat (g = dy masked by the ReLU of the forward).
-// MODE 2: activation backward: dpre = dy*act'(y) written to `dout`, column sums of dpre.
 // fp16 store of a BatchNorm-backward result that SATURATES at +-65504 instead of overflowing to inf.  dx = gamma * rstd *
 // (...) is the one place of the backward pass where a healthy cotangent is multiplied by an unbounded factor: a feature
 // whose batch variance is tiny has rstd up to 1 / sqrt(eps) = 316 -- and 1 / (s sqrt(eps)) behind a range-scaled latent
@@ -54,10 +58,10 @@ __device__ __forceinline__ half_t sat16(float v) {
     return (half_t)(v == v ? __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f) : v);
 }
 
-// Counting variants of the three apply kernels (the numerics monitor, fmri_bn_*_cnt): per lane, the results sat16 clips
-// (|v| > 65504, inf included) and the NaNs it stores; at the end of the kernel one ballot + popcount per bit of the lane
-// counts sums them over the wave and the wave's first lane adds them to cnt[0] / cnt[1] (integer adds: the totals do not
-// depend on the order).  COUNT = false compiles to the uncounted kernels' code.
+// Counting variants of the three backward apply kernels (the numerics monitor, fmri_bn_*_cnt; COUNT = true): per lane,
+// the results sat16 clips (|v| > 65504, inf included) and the NaNs it stores; at the end of the kernel one ballot +
+// popcount per bit of the lane counts sums them over the wave and the wave's first lane adds them to cnt[0] / cnt[1]
+// (integer adds: the totals do not depend on the order).  With COUNT = false nothing is counted and `cnt` is not read.
 struct SatCount {
     int sat = 0, nan = 0;
 };
@@ -83,6 +87,10 @@ __device__ __forceinline__ void sat_count_flush(const SatCount& n, int* cnt) {
     }
 }
 
+// MODE 0: sum x, sum x^2.
+// MODE 2: activation backward: dpre = dy*act'(y) (y passed as `x`) written to `dout`, column sums of dpre.
+// (mean, rstd, gamma and beta are not read: the BatchNorm backward reduction is bn_bwd_reduce_kernel; the argument list
+// keeps the code objects of the two modes unchanged.)
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
                                                         half_t* __restrict__ dout, int M, int C, int cx_log2,
@@ -102,28 +110,12 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const half_t* __restrict
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
     if (chunk < nch) {
-        float mu[8], rs[8], ga[8], be[8];
-        if (MODE == 1) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                mu[j] = mean[chunk * 8 + j]; rs[j] = rstd[chunk * 8 + j];
-                ga[j] = gamma[chunk * 8 + j]; be[j] = beta[chunk * 8 + j];
-            }
-        }
         const int stride = gridDim.y * RY;
         const int64_t coff = (int64_t)chunk * 8;
         auto body = [&](const h8& xv, const h8& gv, int m) {
             if (MODE == 0) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { const float f = (float)xv[j]; s0[j] += f; s1[j] += f * f; }
-            } else if (MODE == 1) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float xh = ((float)xv[j] - mu[j]) * rs[j];
-                    float g = (float)gv[j];
-                    if (relu_or_act && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
-                    s0[j] += g; s1[j] += g * xh;
-                }
             } else {
                 h8 ov;
 #pragma unroll
@@ -170,268 +162,144 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const half_t* __restrict
     }
 }
 
-// sums[i] = sum_p part[p][i], i < n (n = 2*C).  A block folds 32 columns with 8 row groups (4 loads in
-// flight per thread): the partial matrix is small but a single serial chain per column is latency bound.
-// Optionally accumulates the folded sums into parameter gradients (BN backward: g0 += gscale * sums[0..C) = d beta,
-// g1 += gscale * sums[C..2C) = d gamma) -- one writer per element, no atomics.
-__global__ __launch_bounds__(1024) void fold_partials_kernel(const float* __restrict__ part, int nparts, int n,
-                                                             float* __restrict__ sums, float* __restrict__ g0,
-                                                             float* __restrict__ g1, float gscale, int gC, int gOff) {
-    // 32 columns x 32 row lanes per block: the kernel is a chain of memory latencies (few blocks, tiny data), so the
-    // partial rows are spread over as many lanes as a block has and each lane keeps four loads in flight
-    __shared__ float red[32][33];
+// ---- folds of partial rows.  The partial matrices are small, but a single serial chain per column is latency bound
+// (few blocks, tiny data), so a 1024-thread block takes 32 columns x 32 row lanes and every lane keeps DEPTH loads per
+// column in flight.
+//
+// The one fold loop: rows [lo, hi) of the NC columns i, i + cstride, .. of a partial matrix with n columns.  Row lane r
+// (threadIdx.x >> 5) sums rows lo + r, lo + r + 32, .. into DEPTH accumulators by turns, adds them pairwise
+// ((s0 + s1) + (s2 + s3)), and row lane 0 adds the 32 lane sums in lane order: out[] is the block's result THERE and
+// meaningless in the other row lanes.  `live` = this lane's columns exist.  Contains a __syncthreads.
+template <int DEPTH, int NC>
+__device__ __forceinline__ void fold_columns(const float* __restrict__ part, int lo, int hi, int n, int i, int cstride,
+                                             bool live, float (&out)[NC]) {
+    static_assert(DEPTH == 2 || DEPTH == 4, "pairwise sum of the accumulators");
+    __shared__ float red[NC][32][33];
     const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + cx;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (i < n) {
-        int p = gy;
-        for (; p + 96 < nparts; p += 128) {
-            s0 += part[(int64_t)p * n + i];
-            s1 += part[(int64_t)(p + 32) * n + i];
-            s2 += part[(int64_t)(p + 64) * n + i];
-            s3 += part[(int64_t)(p + 96) * n + i];
-        }
-        for (; p < nparts; p += 32) s0 += part[(int64_t)p * n + i];
-    }
-    red[gy][cx] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (gy == 0 && i < n) {
-        float s = 0.f;
+    float s[NC][DEPTH];
 #pragma unroll
-        for (int r = 0; r < 32; ++r) s += red[r][cx];
-        sums[i] = s;
-        // columns [gOff, gOff + C) -> g0, [gOff + C, gOff + 2C) -> g1 (one cotangent stream's sums)
-        const int C = gC > 0 ? gC : (n >> 1);
-        if (g0 && i >= gOff && i < gOff + C) g0[i - gOff] += gscale * s;
-        if (g1 && i >= gOff + C && i < gOff + 2 * C) g1[i - gOff - C] += gscale * s;
+    for (int k = 0; k < NC; ++k)
+#pragma unroll
+        for (int u = 0; u < DEPTH; ++u) s[k][u] = 0.f;
+    if (live) {
+        int p = lo + gy;
+        for (; p + 32 * (DEPTH - 1) < hi; p += 32 * DEPTH)
+#pragma unroll
+            for (int u = 0; u < DEPTH; ++u)
+#pragma unroll
+                for (int k = 0; k < NC; ++k) s[k][u] += part[(int64_t)(p + 32 * u) * n + i + k * cstride];
+        for (; p < hi; p += 32)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) s[k][0] += part[(int64_t)p * n + i + k * cstride];
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        red[k][gy][cx] = DEPTH == 4 ? (s[k][0] + s[k][1]) + (s[k][2] + s[k][3]) : s[k][0] + s[k][1];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NC; ++k) out[k] = 0.f;
+    if (gy == 0)
+#pragma unroll
+        for (int r = 0; r < 32; ++r)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) out[k] += red[k][r][cx];
+}
+
+// sums[g][i] = sum_p part[g][p][i], i < n, for the groups g = blockIdx.y (group stride part_gstride floats; the partials
+// of one reduction are one group, BnBwdEpi's statistics rows are up to four cotangent groups).  Group `pgroup` also
+// accumulates its folded sums into parameter gradients -- one writer per element, no atomics: columns [gOff, gOff + gC)
+// -> g0 += gscale * sum (d beta, or a bias gradient), [gOff + gC, gOff + 2 gC) -> g1 (d gamma); either may be null.
+__global__ __launch_bounds__(1024) void fold_sums_kernel(const float* __restrict__ part, int nparts, int n,
+                                                         int64_t part_gstride, float* __restrict__ sums,
+                                                         float* __restrict__ g0, float* __restrict__ g1, float gscale,
+                                                         int pgroup, int gOff, int gC) {
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31);
+    float s[1];
+    fold_columns<4, 1>(part + blockIdx.y * part_gstride, 0, nparts, n, i, 0, i < n, s);
+    if (threadIdx.x < 32 && i < n) {
+        sums[(int64_t)blockIdx.y * n + i] = s[0];
+        if ((int)blockIdx.y == pgroup) {
+            if (g0 && i >= gOff && i < gOff + gC) g0[i - gOff] += gscale * s[0];
+            if (g1 && i >= gOff + gC && i < gOff + 2 * gC) g1[i - gOff - gC] += gscale * s[0];
+        }
     }
 }
 
-// stage 1 of a long fold (statistics rows written by a contraction's epilogue, StatEpi): block (x, y) sums rows
-// [y*per, (y+1)*per) of columns 32x .. 32x+31 into out[y][n].  Same lane layout as fold_partials_kernel.
+// stage 1 of a long fold (statistics rows written by a contraction's epilogue, StatEpi): block (x, y, g) sums rows
+// [y*per, (y+1)*per) of columns 32x .. 32x+31 of group g into out[g][y][n].
 __global__ __launch_bounds__(1024) void fold_rows_kernel(const float* __restrict__ part, int nparts, int n, int per,
                                                          float* __restrict__ out, int64_t part_gstride,
                                                          int64_t out_gstride) {
-    part += blockIdx.z * part_gstride;      // statistics group
-    out += blockIdx.z * out_gstride;
-    __shared__ float red[32][33];
-    const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + cx;
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31);
     const int lo = blockIdx.y * per;
     const int hi = lo + per < nparts ? lo + per : nparts;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (i < n) {
-        int p = lo + gy;
-        for (; p + 96 < hi; p += 128) {
-            s0 += part[(int64_t)p * n + i];
-            s1 += part[(int64_t)(p + 32) * n + i];
-            s2 += part[(int64_t)(p + 64) * n + i];
-            s3 += part[(int64_t)(p + 96) * n + i];
-        }
-        for (; p < hi; p += 32) s0 += part[(int64_t)p * n + i];
-    }
-    red[gy][cx] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (gy == 0 && i < n) {
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) s += red[r][cx];
-        out[(int64_t)blockIdx.y * n + i] = s;
-    }
+    float s[1];
+    fold_columns<4, 1>(part + blockIdx.z * part_gstride, lo, hi, n, i, 0, i < n, s);
+    if (threadIdx.x < 32 && i < n) out[blockIdx.z * out_gstride + (int64_t)blockIdx.y * n + i] = s[0];
 }
 
-// BatchNorm-backward statistics rows of a contraction's epilogue (BnBwdEpi), G cotangent groups at once: block (x, g)
-// folds columns 32x .. 32x+31 of group g's rows into sums[g][n] (n = 2C: sum g | sum g*xhat); the group `pgroup` also
-// accumulates the parameter gradients d beta += gscale * sum g, d gamma += gscale * sum g*xhat (one writer per element).
-__global__ __launch_bounds__(1024) void fold_groups_kernel(const float* __restrict__ part, int nparts, int n,
-                                                           int64_t part_gstride, float* __restrict__ sums,
-                                                           float* __restrict__ dbeta, float* __restrict__ dgamma,
-                                                           float gscale, int pgroup) {
-    __shared__ float red[32][33];
-    part += blockIdx.y * part_gstride;
-    const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + cx;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (i < n) {
-        int p = gy;
-        for (; p + 96 < nparts; p += 128) {
-            s0 += part[(int64_t)p * n + i];
-            s1 += part[(int64_t)(p + 32) * n + i];
-            s2 += part[(int64_t)(p + 64) * n + i];
-            s3 += part[(int64_t)(p + 96) * n + i];
-        }
-        for (; p < nparts; p += 32) s0 += part[(int64_t)p * n + i];
-    }
-    red[gy][cx] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (gy == 0 && i < n) {
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) s += red[r][cx];
-        sums[(int64_t)blockIdx.y * n + i] = s;
-        const int C = n >> 1;
-        if ((int)blockIdx.y == pgroup) {
-            if (dbeta && i < C) dbeta[i] += gscale * s;
-            if (dgamma && i >= C) dgamma[i - C] += gscale * s;
-        }
-    }
-}
-
-// shared by bn_finalize_kernel and fold_finalize_kernel: channel c from its batch sums.
-// ``in_s``: the rows are s * x for a power of two s (a latent batch stored range-scaled, fmri_latent_fwd_ranged):
+// channel c from its batch sums (every finalizing kernel); returns (scale, shift).
+// ``in_scale``: the rows are s * x for a power of two s (a latent batch stored range-scaled, fmri_latent_fwd_ranged):
 // BN_eps(x) == BN_{eps s^2}(s x), so the normalisation runs on the stored values with eps * s^2 -- mean / rstd / scale /
 // shift are those of the STORED rows (what the apply and backward kernels read) -- and the running statistics receive
 // the true-scale mean / s and var / s^2.
-__device__ __forceinline__ void bn_finalize_channel(int c, float sx, float sxx, float count, const float* gamma,
-                                                    const float* beta, float eps, float momentum, int updates,
-                                                    float* running_mean, float* running_var, float* mean_out,
-                                                    float* rstd_out, float* scale_out, float* shift_out,
-                                                    float in_s = 1.f) {
+__device__ __forceinline__ float2 bn_finalize_channel(int c, float sx, float sxx, float count, const BnFinalize& f) {
+    const float in_s = f.in_scale ? *f.in_scale : 1.f;
+    const float gamma = f.gamma[c], beta = f.beta[c];     // (read before the stores: the struct's pointers may alias)
     const float mean = sx / count;
     float var = sxx / count - mean * mean;
     var = var > 0.f ? var : 0.f;
-    const float rstd = rsqrtf(var + eps * in_s * in_s);
-    mean_out[c] = mean;
-    rstd_out[c] = rstd;
-    const float sc = gamma[c] * rstd;
-    scale_out[c] = sc;
-    shift_out[c] = beta[c] - mean * sc;
-    if (running_mean && updates > 0) {
+    const float rstd = rsqrtf(var + f.eps * in_s * in_s);
+    f.mean[c] = mean;
+    f.rstd[c] = rstd;
+    const float sc = gamma * rstd, sh = beta - mean * sc;
+    f.scale[c] = sc;
+    f.shift[c] = sh;
+    if (f.running_mean && f.updates > 0) {
         const float inv_s = 1.f / in_s;
         const float unb = (count > 1.f ? var * count / (count - 1.f) : var) * inv_s * inv_s;
         const float mean_t = mean * inv_s;
-        float rm = running_mean[c], rv = running_var[c];
-        for (int u = 0; u < updates; ++u) {
-            rm = (1.f - momentum) * rm + momentum * mean_t;
-            rv = (1.f - momentum) * rv + momentum * unb;
+        float rm = f.running_mean[c], rv = f.running_var[c];
+        for (int u = 0; u < f.updates; ++u) {
+            rm = (1.f - f.momentum) * rm + f.momentum * mean_t;
+            rv = (1.f - f.momentum) * rv + f.momentum * unb;
         }
-        running_mean[c] = rm;
-        running_var[c] = rv;
+        f.running_mean[c] = rm;
+        f.running_var[c] = rv;
     }
+    return make_float2(sc, sh);
+}
+// num_batches_tracked: one thread of a finalizing launch
+__device__ __forceinline__ void bn_count_batches(const BnFinalize& f) {
+    if (f.nbt && f.updates > 0) *f.nbt += f.updates;
 }
 
 // fold of the statistics partials [nparts][2][C] + finalize in one launch (forward BatchNorm without a statistics
 // exchange between ranks): block = 32 channels x 32 row lanes, both sums of a channel are folded by the same lanes.
 __global__ __launch_bounds__(1024) void fold_finalize_kernel(const float* __restrict__ part, int nparts, int C,
-                                                             float* __restrict__ sums, float count,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, float eps, float momentum,
-                                                             int updates, float* __restrict__ running_mean,
-                                                             float* __restrict__ running_var,
-                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                             float* __restrict__ scale_out,
-                                                             float* __restrict__ shift_out, long long* __restrict__ nbt) {
-    __shared__ float red[2][32][33];
-    const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cx;
-    const int n = 2 * C;
-    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-    if (c < C) {
-        int p = gy;
-        for (; p + 32 < nparts; p += 64) {
-            a0 += part[(int64_t)p * n + c];
-            b0 += part[(int64_t)p * n + C + c];
-            a1 += part[(int64_t)(p + 32) * n + c];
-            b1 += part[(int64_t)(p + 32) * n + C + c];
-        }
-        for (; p < nparts; p += 32) {
-            a0 += part[(int64_t)p * n + c];
-            b0 += part[(int64_t)p * n + C + c];
-        }
-    }
-    red[0][gy][cx] = a0 + a1;
-    red[1][gy][cx] = b0 + b1;
-    __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x == 0 && nbt && updates > 0) *nbt += updates;      // num_batches_tracked
-    if (gy == 0 && c < C) {
-        float sx = 0.f, sxx = 0.f;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) { sx += red[0][r][cx]; sxx += red[1][r][cx]; }
-        sums[c] = sx;
-        sums[C + c] = sxx;
-        bn_finalize_channel(c, sx, sxx, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean_out,
-                            rstd_out, scale_out, shift_out);
+                                                             float* __restrict__ sums, float count, BnFinalize f) {
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    float s[2];
+    fold_columns<2, 2>(part, 0, nparts, 2 * C, c, C, c < C, s);
+    if (blockIdx.x == 0 && threadIdx.x == 0) bn_count_batches(f);
+    if (threadIdx.x < 32 && c < C) {
+        sums[c] = s[0];
+        sums[C + c] = s[1];
+        bn_finalize_channel(c, s[0], s[1], count, f);
     }
 }
 
 // one thread per channel
-__global__ void bn_finalize_kernel(const float* __restrict__ sums, int C, float count, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float eps, float momentum, int updates,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var,
-                                   float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                   float* __restrict__ scale_out, float* __restrict__ shift_out,
-                                   long long* __restrict__ nbt, const float* __restrict__ in_scale) {
+__global__ void bn_finalize_kernel(const float* __restrict__ sums, int C, float count, BnFinalize f) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0 && nbt && updates > 0) *nbt += updates;      // num_batches_tracked
+    if (c == 0) bn_count_batches(f);
     if (c >= C) return;
-    bn_finalize_channel(c, sums[c], sums[C + c], count, gamma, beta, eps, momentum, updates, running_mean, running_var,
-                        mean_out, rstd_out, scale_out, shift_out, in_scale ? *in_scale : 1.f);
+    bn_finalize_channel(c, sums[c], sums[C + c], count, f);
 }
 
-// MODE 0: y = act(x*scale + shift).   MODE 1: dx = gamma*rstd*(g - sum_g/M - xhat*sum_gx/M), g = dy*mask
-template <int MODE, bool COUNT>
-__device__ __forceinline__ void bn_stream_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                               half_t* __restrict__ out, int M, int C, int cx_log2,
-                                               const float* __restrict__ p0, const float* __restrict__ p1,
-                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                               int relu, float inv_count, const float* __restrict__ sums,
-                                               SatCount& nc) {
-    const int CX = 1 << cx_log2;
-    const int RY = 256 >> cx_log2;
-    const int cx = threadIdx.x & (CX - 1);
-    const int ry = threadIdx.x >> cx_log2;
-    const int chunk = blockIdx.x * CX + cx;
-    if (chunk >= (C >> 3)) return;
-    // MODE 0: a = scale, b = shift.  MODE 1: xhat = (x - b)*a with a = rstd, b = mean;
-    //         dx = k*(g - c0 - xhat*c1), k = gamma*rstd, c0 = sum_g/M, c1 = sum_gx/M
-    float a[8], b[8], k[8], c0[8], c1[8], ga[8], be[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = chunk * 8 + j;
-        if (MODE == 0) {
-            a[j] = p0[c]; b[j] = p1[c];
-        } else {
-            const float mu = p0[c], rs = p1[c];
-            a[j] = rs; b[j] = mu; ga[j] = gamma[c]; be[j] = beta[c];
-            k[j] = ga[j] * rs; c0[j] = sums[c] * inv_count; c1[j] = sums[C + c] * inv_count;
-        }
-    }
-    const int stride = gridDim.y * RY;
-    const int64_t coff = (int64_t)chunk * 8;
-    auto body = [&](const h8& xv, const h8& gv, int m) {
-        h8 ov;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (MODE == 0) {
-                float f = (float)xv[j] * a[j] + b[j];
-                if (relu) f = f > 0.f ? f : 0.f;
-                ov[j] = (half_t)f;
-            } else {
-                const float xh = ((float)xv[j] - b[j]) * a[j];
-                float g = (float)gv[j];
-                if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
-                ov[j] = sat16c<COUNT>(k[j] * (g - c0[j] - xh * c1[j]), nc);
-            }
-        }
-        *(h8*)(out + (int64_t)m * C + coff) = ov;
-    };
-    int m = blockIdx.y * RY + ry;
-    for (; m + 3 * stride < M; m += 4 * stride) {
-        h8 xv[4], gv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            xv[u] = *(const h8*)(x + (int64_t)(m + u * stride) * C + coff);
-            if (MODE == 1) gv[u] = *(const h8*)(dy + (int64_t)(m + u * stride) * C + coff);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) body(xv[u], gv[u], m + u * stride);
-    }
-    for (; m < M; m += stride) {
-        h8 xv = *(const h8*)(x + (int64_t)m * C + coff), gv;
-        if (MODE == 1) gv = *(const h8*)(dy + (int64_t)m * C + coff);
-        body(xv, gv, m);
-    }
-}
+// y = act(x*scale + shift): the forward apply.  Template argument and argument list are those of the one forward /
+// backward streaming kernel this was mode 0 of (dy, gamma, beta, inv_count and sums are not read), which keeps its code
+// object unchanged; the backward modes are bn_bwd_apply_kernel.
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
                                                         half_t* __restrict__ out, int M, int C, int cx_log2,
@@ -439,30 +307,62 @@ __global__ __launch_bounds__(256) void bn_stream_kernel(const half_t* __restrict
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int relu, float inv_count,
                                                         const float* __restrict__ sums) {
-    SatCount nc;
-    bn_stream_body<MODE, false>(x, dy, out, M, C, cx_log2, p0, p1, gamma, beta, relu, inv_count, sums, nc);
-}
-__global__ __launch_bounds__(256) void bn_stream_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                            half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                            const float* __restrict__ p0, const float* __restrict__ p1,
-                                                            const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int relu, float inv_count,
-                                                            const float* __restrict__ sums, int* __restrict__ cnt) {
-    SatCount nc;
-    bn_stream_body<1, true>(x, dy, out, M, C, cx_log2, p0, p1, gamma, beta, relu, inv_count, sums, nc);
-    sat_count_flush(nc, cnt);
+    static_assert(MODE == 0, "forward apply only");
+    const int CX = 1 << cx_log2;
+    const int RY = 256 >> cx_log2;
+    const int cx = threadIdx.x & (CX - 1);
+    const int ry = threadIdx.x >> cx_log2;
+    const int chunk = blockIdx.x * CX + cx;
+    if (chunk >= (C >> 3)) return;
+    float a[8], b[8];       // scale, shift
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = chunk * 8 + j;
+        a[j] = p0[c]; b[j] = p1[c];
+    }
+    const int stride = gridDim.y * RY;
+    const int64_t coff = (int64_t)chunk * 8;
+    auto body = [&](const h8& xv, int m) {
+        h8 ov;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float f = (float)xv[j] * a[j] + b[j];
+            if (relu) f = f > 0.f ? f : 0.f;
+            ov[j] = (half_t)f;
+        }
+        *(h8*)(out + (int64_t)m * C + coff) = ov;
+    };
+    int m = blockIdx.y * RY + ry;
+    for (; m + 3 * stride < M; m += 4 * stride) {
+        h8 xv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) xv[u] = *(const h8*)(x + (int64_t)(m + u * stride) * C + coff);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) body(xv[u], m + u * stride);
+    }
+    for (; m < M; m += stride) {
+        h8 xv = *(const h8*)(x + (int64_t)m * C + coff);
+        body(xv, m);
+    }
 }
 
-// ---- BatchNorm backward of TWO cotangent streams through one saved forward (the discriminator's logit stream A and
-// feature stream B, stacked as dy = [A rows | B rows], M rows each).  The forward tensor x and everything derived from
-// it (xhat, the ReLU mask) are read and computed once for both: 3 + 5 tensor passes instead of 2 x (2 + 3).
-// partials / sums layout: [A: sum g | A: sum g*xhat | B: sum g | B: sum g*xhat], C floats each.
-__global__ __launch_bounds__(256) void bn_reduce2_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                         int M, int C, int cx_log2, const float* __restrict__ mean,
-                                                         const float* __restrict__ rstd,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, int relu,
-                                                         float* __restrict__ part /* [gridDim.y][4][C] */) {
+// ---- BatchNorm backward of NS cotangent streams through one saved forward, stacked along the rows: dy = [stream 0 rows |
+// stream 1 rows], M rows each (NS = 2: the discriminator's logit stream A and feature stream B).  The forward tensor x
+// and everything derived from it (xhat, the ReLU mask) are read and computed once for all streams: 3 + 5 tensor passes
+// instead of 2 x (2 + 3) at NS = 2.  g_s = dy_s masked by the ReLU of the forward;
+// partials / sums layout [NS][2][C]: (sum g_s | sum g_s*xhat) per stream, stream A first.
+// The ReLU mask is spelled per stream count, `if (relu && !(..)) g = 0` for one stream and `on ? g : 0` for two, in the
+// reduction and in the apply kernel alike: the compiler hoists the test on `relu` out of the row loop for the first
+// spelling only, and each count is fastest with the code it always had.  One spelling for both costs one of them an
+// occupancy step or 5-8 % of the two-stream apply (tools/probes/bn_reduce_merged.hip,
+// profiles/bn_refactor_ab.txt).  The values are the same either way.
+template <int NS>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                            int M, int C, int cx_log2, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, int relu,
+                                                            float* __restrict__ part /* [gridDim.y][2 NS][C] */) {
     __shared__ float red[256 * 17];
     const int CX = 1 << cx_log2;
     const int RY = 256 >> cx_log2;
@@ -470,9 +370,11 @@ __global__ __launch_bounds__(256) void bn_reduce2_kernel(const half_t* __restric
     const int ry = threadIdx.x >> cx_log2;
     const int chunk = blockIdx.x * CX + cx;
     const int nch = C >> 3;
-    float sa0[8], sa1[8], sb0[8], sb1[8];
+    float s0[NS][8], s1[NS][8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sa0[j] = 0.f; sa1[j] = 0.f; sb0[j] = 0.f; sb1[j] = 0.f; }
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s0[s][j] = 0.f; s1[s][j] = 0.f; }
     if (chunk < nch) {
         float mu[8], rs[8], ga[8], be[8];
 #pragma unroll
@@ -482,43 +384,48 @@ __global__ __launch_bounds__(256) void bn_reduce2_kernel(const half_t* __restric
         }
         const int stride = gridDim.y * RY;
         const int64_t coff = (int64_t)chunk * 8;
-        const half_t* dyb = dy + (int64_t)M * C;
-        auto body = [&](const h8& xv, const h8& ga_v, const h8& gb_v) {
+        const int64_t sstride = (int64_t)M * C;
+        auto body = [&](const h8& xv, const h8 (&gv)[NS]) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float xh = ((float)xv[j] - mu[j]) * rs[j];
                 const bool on = !relu || (xh * ga[j] + be[j] > 0.f);
-                const float g_a = on ? (float)ga_v[j] : 0.f, g_b = on ? (float)gb_v[j] : 0.f;
-                sa0[j] += g_a; sa1[j] += g_a * xh;
-                sb0[j] += g_b; sb1[j] += g_b * xh;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    float g = (float)gv[s][j];
+                    if (NS == 1) { if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f; }
+                    else g = on ? g : 0.f;
+                    s0[s][j] += g; s1[s][j] += g * xh;
+                }
             }
         };
         int m = blockIdx.y * RY + ry;
         for (; m + 3 * stride < M; m += 4 * stride) {
-            h8 xv[4], av[4], bv[4];
+            h8 xv[4], gv[4][NS];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t o = (int64_t)(m + u * stride) * C + coff;
                 xv[u] = *(const h8*)(x + o);
-                av[u] = *(const h8*)(dy + o);
-                bv[u] = *(const h8*)(dyb + o);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) gv[u][s] = *(const h8*)(dy + s * sstride + o);
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) body(xv[u], av[u], bv[u]);
+            for (int u = 0; u < 4; ++u) body(xv[u], gv[u]);
         }
         for (; m < M; m += stride) {
             const int64_t o = (int64_t)m * C + coff;
-            body(*(const h8*)(x + o), *(const h8*)(dy + o), *(const h8*)(dyb + o));
+            h8 gv[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) gv[s] = *(const h8*)(dy + s * sstride + o);
+            body(*(const h8*)(x + o), gv);
         }
     }
-    // block reduction of the 16 per-thread values of a stream over the RY row lanes, stream A then stream B
+    // block reduction of the 16 per-thread values of a stream over the RY row lanes, stream by stream
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < NS; ++s) {
+        if (s) __syncthreads();              // (the previous stream's fold is done with `red`)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            red[threadIdx.x * 17 + j] = s ? sb0[j] : sa0[j];
-            red[threadIdx.x * 17 + 8 + j] = s ? sb1[j] : sa1[j];
-        }
+        for (int j = 0; j < 8; ++j) { red[threadIdx.x * 17 + j] = s0[s][j]; red[threadIdx.x * 17 + 8 + j] = s1[s][j]; }
         __syncthreads();
         for (int t = threadIdx.x; t < CX * 16; t += 256) {
             const int c = t >> 4, j = t & 15;
@@ -526,89 +433,84 @@ __global__ __launch_bounds__(256) void bn_reduce2_kernel(const half_t* __restric
             if (ch >= nch) continue;
             float v = 0.f;
             for (int r = 0; r < RY; ++r) v += red[((r << cx_log2) + c) * 17 + j];
-            part[((int64_t)blockIdx.y * 4 + 2 * s + (j >> 3)) * C + ch * 8 + (j & 7)] = v;
+            part[((int64_t)blockIdx.y * 2 * NS + 2 * s + (j >> 3)) * C + ch * 8 + (j & 7)] = v;
         }
-        __syncthreads();
     }
 }
 
-// dx_s = gamma*rstd*(g_s - sum_g_s/M - xhat*sum_gx_s/M) for both streams, x read once
-template <bool COUNT>
-__device__ __forceinline__ void bn_stream2_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                int relu, float inv_count, const float* __restrict__ sums /* [4][C] */,
-                                                SatCount& nc) {
+// dx_s = gamma*rstd*(g_s - sum_g_s/M - xhat*sum_gx_s/M) for every stream, x read once.  A lane keeps 4 / NS rows (3, or 2 x
+// 3, 16-byte loads) in flight.
+template <int NS, bool COUNT>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                           half_t* __restrict__ dx, int M, int C, int cx_log2,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int relu, float inv_count,
+                                                           const float* __restrict__ sums /* [NS][2][C] */,
+                                                           int* __restrict__ cnt) {
+    constexpr int U = 4 / NS;
+    SatCount nc;
     const int CX = 1 << cx_log2;
     const int RY = 256 >> cx_log2;
     const int cx = threadIdx.x & (CX - 1);
     const int ry = threadIdx.x >> cx_log2;
     const int chunk = blockIdx.x * CX + cx;
-    if (chunk >= (C >> 3)) return;
-    float a[8], b[8], k[8], ga[8], be[8], a0[8], a1[8], b0[8], b1[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = chunk * 8 + j;
-        a[j] = rstd[c]; b[j] = mean[c]; ga[j] = gamma[c]; be[j] = beta[c];
-        k[j] = ga[j] * a[j];
-        a0[j] = sums[c] * inv_count; a1[j] = sums[C + c] * inv_count;
-        b0[j] = sums[2 * C + c] * inv_count; b1[j] = sums[3 * C + c] * inv_count;
-    }
-    const int stride = gridDim.y * RY;
-    const int64_t coff = (int64_t)chunk * 8;
-    const int64_t sb = (int64_t)M * C;
-    auto body = [&](const h8& xv, const h8& av, const h8& bv, int m) {
-        h8 oa, ob;
+    if (chunk < (C >> 3)) {
+        // xhat = (x - mu)*rs;  dx_s = k*(g_s - c0_s - xhat*c1_s), k = gamma*rstd, c0_s = sum_g_s/M, c1_s = sum_gx_s/M
+        float mu[8], rs[8], ga[8], be[8], k[8], c0[NS][8], c1[NS][8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float xh = ((float)xv[j] - b[j]) * a[j];
-            const bool on = !relu || (xh * ga[j] + be[j] > 0.f);
-            const float g_a = on ? (float)av[j] : 0.f, g_b = on ? (float)bv[j] : 0.f;
-            oa[j] = sat16c<COUNT>(k[j] * (g_a - a0[j] - xh * a1[j]), nc);
-            ob[j] = sat16c<COUNT>(k[j] * (g_b - b0[j] - xh * b1[j]), nc);
-        }
-        const int64_t o = (int64_t)m * C + coff;
-        *(h8*)(out + o) = oa;
-        *(h8*)(out + sb + o) = ob;
-    };
-    int m = blockIdx.y * RY + ry;
-    for (; m + stride < M; m += 2 * stride) {
-        h8 xv[2], av[2], bv[2];
+            const int c = chunk * 8 + j;
+            mu[j] = mean[c]; rs[j] = rstd[c]; ga[j] = gamma[c]; be[j] = beta[c];
+            k[j] = ga[j] * rs[j];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int64_t o = (int64_t)(m + u * stride) * C + coff;
-            xv[u] = *(const h8*)(x + o);
-            av[u] = *(const h8*)(dy + o);
-            bv[u] = *(const h8*)(dy + sb + o);
+            for (int s = 0; s < NS; ++s) {
+                c0[s][j] = sums[(2 * s) * C + c] * inv_count;
+                c1[s][j] = sums[(2 * s + 1) * C + c] * inv_count;
+            }
         }
+        const int stride = gridDim.y * RY;
+        const int64_t coff = (int64_t)chunk * 8;
+        const int64_t sstride = (int64_t)M * C;
+        auto body = [&](const h8& xv, const h8 (&gv)[NS], int m) {
+            h8 ov[NS];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) body(xv[u], av[u], bv[u], m + u * stride);
+            for (int j = 0; j < 8; ++j) {
+                const float xh = ((float)xv[j] - mu[j]) * rs[j];
+                const bool on = !relu || (xh * ga[j] + be[j] > 0.f);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    float g = (float)gv[s][j];
+                    if (NS == 1) { if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f; }      // (the note above)
+                    else g = on ? g : 0.f;
+                    ov[s][j] = sat16c<COUNT>(k[j] * (g - c0[s][j] - xh * c1[s][j]), nc);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s) *(h8*)(dx + s * sstride + (int64_t)m * C + coff) = ov[s];
+        };
+        int m = blockIdx.y * RY + ry;
+        for (; m + (U - 1) * stride < M; m += U * stride) {
+            h8 xv[U], gv[U][NS];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t o = (int64_t)(m + u * stride) * C + coff;
+                xv[u] = *(const h8*)(x + o);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) gv[u][s] = *(const h8*)(dy + s * sstride + o);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) body(xv[u], gv[u], m + u * stride);
+        }
+        for (; m < M; m += stride) {
+            const int64_t o = (int64_t)m * C + coff;
+            h8 gv[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) gv[s] = *(const h8*)(dy + s * sstride + o);
+            body(*(const h8*)(x + o), gv, m);
+        }
     }
-    for (; m < M; m += stride) {
-        const int64_t o = (int64_t)m * C + coff;
-        body(*(const h8*)(x + o), *(const h8*)(dy + o), *(const h8*)(dy + sb + o), m);
-    }
-}
-__global__ __launch_bounds__(256) void bn_stream2_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                         half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, int relu, float inv_count,
-                                                         const float* __restrict__ sums /* [4][C] */) {
-    SatCount nc;
-    bn_stream2_body<false>(x, dy, out, M, C, cx_log2, mean, rstd, gamma, beta, relu, inv_count, sums, nc);
-}
-__global__ __launch_bounds__(256) void bn_stream2_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                             half_t* __restrict__ out, int M, int C, int cx_log2,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ rstd,
-                                                             const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, int relu, float inv_count,
-                                                             const float* __restrict__ sums, int* __restrict__ cnt) {
-    SatCount nc;
-    bn_stream2_body<true>(x, dy, out, M, C, cx_log2, mean, rstd, gamma, beta, relu, inv_count, sums, nc);
-    sat_count_flush(nc, cnt);
+    if (COUNT) sat_count_flush(nc, cnt);
 }
 
 // ---- BatchNorm over FEW rows (the dense layers: BatchNorm1d behind fc.0 / fc1.0, M = batch rows) in ONE launch per
@@ -627,14 +529,8 @@ __device__ __forceinline__ float cols_fold(const float* red, int cx, int j) {
 }
 
 __global__ __launch_bounds__(256) void bn_cols_fwd_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, int M,
-                                                          int C, float count, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float eps, float momentum,
-                                                          int updates, float* __restrict__ running_mean,
-                                                          float* __restrict__ running_var, float* __restrict__ mean_out,
-                                                          float* __restrict__ rstd_out, float* __restrict__ scale_out,
-                                                          float* __restrict__ shift_out, float* __restrict__ sums,
-                                                          long long* __restrict__ nbt, int relu,
-                                                          const float* __restrict__ in_scale) {
+                                                          int C, float count, BnFinalize fin, float* __restrict__ sums,
+                                                          int relu) {
     __shared__ float red[256 * 17];
     __shared__ float par[COLS_CX * 8][2];
     const int cx = threadIdx.x & (COLS_CX - 1), ry = threadIdx.x >> 2;
@@ -653,7 +549,7 @@ __global__ __launch_bounds__(256) void bn_cols_fwd_kernel(const half_t* __restri
 #pragma unroll
     for (int j = 0; j < 8; ++j) { red[threadIdx.x * 17 + j] = s0[j]; red[threadIdx.x * 17 + 8 + j] = s1[j]; }
     __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x == 0 && nbt && updates > 0) *nbt += updates;      // num_batches_tracked
+    if (blockIdx.x == 0 && threadIdx.x == 0) bn_count_batches(fin);
     if (threadIdx.x < COLS_CX * 8) {
         const int c_ = threadIdx.x >> 3, j = threadIdx.x & 7;
         const int c = (blockIdx.x * COLS_CX + c_) * 8 + j;
@@ -661,10 +557,9 @@ __global__ __launch_bounds__(256) void bn_cols_fwd_kernel(const half_t* __restri
             const float sx = cols_fold(red, c_, j), sxx = cols_fold(red, c_, 8 + j);
             sums[c] = sx;
             sums[C + c] = sxx;
-            bn_finalize_channel(c, sx, sxx, count, gamma, beta, eps, momentum, updates, running_mean, running_var, mean_out,
-                                rstd_out, scale_out, shift_out, in_scale ? *in_scale : 1.f);
-            par[threadIdx.x][0] = scale_out[c];
-            par[threadIdx.x][1] = shift_out[c];
+            const float2 ss = bn_finalize_channel(c, sx, sxx, count, fin);
+            par[threadIdx.x][0] = ss.x;
+            par[threadIdx.x][1] = ss.y;
         }
     }
     __syncthreads();
@@ -688,14 +583,17 @@ __global__ __launch_bounds__(256) void bn_cols_fwd_kernel(const half_t* __restri
 // backward through (ReLU o BN) of NS cotangent streams stacked along the rows (dy = [stream 0 rows | stream 1 rows]);
 // sums [NS][2][C] = (sum g | sum g*xhat) per stream; dbeta / dgamma (may be null) += gscale * sums of stream `pstream`
 template <int NS, bool COUNT>
-__device__ __forceinline__ void bn_cols_bwd_body(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                 half_t* __restrict__ dx, int M, int C, float inv_count,
-                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                 int relu, float* __restrict__ sums, float* __restrict__ dbeta,
-                                                 float* __restrict__ dgamma, float gscale, int pstream, SatCount& nc) {
+__global__ __launch_bounds__(256) void bn_cols_bwd_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
+                                                          half_t* __restrict__ dx, int M, int C, float inv_count,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int relu,
+                                                          float* __restrict__ sums, float* __restrict__ dbeta,
+                                                          float* __restrict__ dgamma, float gscale, int pstream,
+                                                          int* __restrict__ cnt) {
     __shared__ float red[256 * 17];
     __shared__ float par[NS][COLS_CX * 8][2];
+    SatCount nc;
     const int cx = threadIdx.x & (COLS_CX - 1), ry = threadIdx.x >> 2;
     const int chunk = blockIdx.x * COLS_CX + cx;
     const int nch = C >> 3;
@@ -745,67 +643,62 @@ __device__ __forceinline__ void bn_cols_bwd_body(const half_t* __restrict__ x, c
         }
     }
     __syncthreads();
-    if (chunk >= nch) return;
-    for (int st = 0; st < NS; ++st) {
-        float c0[8], c1[8];
+    if (chunk < nch)
+        for (int st = 0; st < NS; ++st) {
+            float c0[8], c1[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { c0[j] = par[st][cx * 8 + j][0]; c1[j] = par[st][cx * 8 + j][1]; }
-        for (int m = ry; m < M; m += COLS_RY) {
-            const int64_t o = (int64_t)m * C + coff;
-            const h8 xv = *(const h8*)(x + o);
-            const h8 gv = *(const h8*)(dy + st * sstride + o);
-            h8 ov;
+            for (int j = 0; j < 8; ++j) { c0[j] = par[st][cx * 8 + j][0]; c1[j] = par[st][cx * 8 + j][1]; }
+            for (int m = ry; m < M; m += COLS_RY) {
+                const int64_t o = (int64_t)m * C + coff;
+                const h8 xv = *(const h8*)(x + o);
+                const h8 gv = *(const h8*)(dy + st * sstride + o);
+                h8 ov;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float xh = ((float)xv[j] - mu[j]) * rs[j];
-                float g = (float)gv[j];
-                if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
-                ov[j] = sat16c<COUNT>(ga[j] * rs[j] * (g - c0[j] - xh * c1[j]), nc);
+                for (int j = 0; j < 8; ++j) {
+                    const float xh = ((float)xv[j] - mu[j]) * rs[j];
+                    float g = (float)gv[j];
+                    if (relu && !(xh * ga[j] + be[j] > 0.f)) g = 0.f;
+                    ov[j] = sat16c<COUNT>(ga[j] * rs[j] * (g - c0[j] - xh * c1[j]), nc);
+                }
+                *(h8*)(dx + st * sstride + o) = ov;
             }
-            *(h8*)(dx + st * sstride + o) = ov;
         }
-    }
-}
-template <int NS>
-__global__ __launch_bounds__(256) void bn_cols_bwd_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                          half_t* __restrict__ dx, int M, int C, float inv_count,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, int relu,
-                                                          float* __restrict__ sums, float* __restrict__ dbeta,
-                                                          float* __restrict__ dgamma, float gscale, int pstream) {
-    SatCount nc;
-    bn_cols_bwd_body<NS, false>(x, dy, dx, M, C, inv_count, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma, gscale,
-                                pstream, nc);
-}
-template <int NS>
-__global__ __launch_bounds__(256) void bn_cols_bwd_cnt_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy,
-                                                              half_t* __restrict__ dx, int M, int C, float inv_count,
-                                                              const float* __restrict__ mean,
-                                                              const float* __restrict__ rstd,
-                                                              const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, int relu,
-                                                              float* __restrict__ sums, float* __restrict__ dbeta,
-                                                              float* __restrict__ dgamma, float gscale, int pstream,
-                                                              int* __restrict__ cnt) {
-    SatCount nc;
-    bn_cols_bwd_body<NS, true>(x, dy, dx, M, C, inv_count, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma, gscale,
-                               pstream, nc);
-    sat_count_flush(nc, cnt);
+    if (COUNT) sat_count_flush(nc, cnt);
 }
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? OK : E_LAUNCH)
+
+// launch(NS, COUNT) with the run-time stream count and counter switch as compile-time constants
+template <class F>
+static int bwd_dispatch(int nstreams, bool count, F launch) {
+    using std::integral_constant;
+    if (nstreams == 1)
+        return count ? launch(integral_constant<int, 1>{}, std::true_type{})
+                     : launch(integral_constant<int, 1>{}, std::false_type{});
+    if (nstreams == 2)
+        return count ? launch(integral_constant<int, 2>{}, std::true_type{})
+                     : launch(integral_constant<int, 2>{}, std::false_type{});
+    return E_UNSUPPORTED;
+}
 
 int64_t bn_ws_floats(int M, int C) {
     const RowGeom g = row_geometry(M, C, 1 << 30);
     return (int64_t)g.gy * 2 * C;
 }
 
+// part [G][..][n] (group stride gstride floats, `rows` rows each) -> sums [G][n] (+ parameter gradients, fold_sums_kernel)
+static void fold_sums(const float* part, int rows, int n, int G, int64_t gstride, float* sums, float* g0, float* g1,
+                      float gscale, int pgroup, int gOff, int gC, hipStream_t st) {
+    hipLaunchKernelGGL(fold_sums_kernel, dim3((n + 31) / 32, G), dim3(1024), 0, st, part, rows, n, gstride, sums, g0, g1,
+                       gscale, pgroup, gOff, gC);
+}
+
+// bn_reduce_kernel<MODE> over the rows + the fold of its partials; sums (may be null: then nothing is reduced) gets [2][C];
+// g0 / g1 (may be null): g0[c] += gscale * sums[0][c], g1[c] += gscale * sums[1][c], c < g_count
 template <int MODE>
 static int reduce_launch(const half_t* x, const half_t* dy, half_t* dout, int M, int C, const float* mean,
                          const float* rstd, const float* gamma, const float* beta, int flag, float* sums, float* ws,
-                         int64_t ws_floats, hipStream_t st, float* g0 = nullptr, float* g1 = nullptr,
-                         float gscale = 0.f, int g_count = 0) {
+                         int64_t ws_floats, hipStream_t st, float* g0, float* g1, float gscale, int g_count) {
     int max_gy = 1 << 30;
     if (sums) {
         if (!ws || ws_floats < 2 * (int64_t)C) return E_WORKSPACE;
@@ -814,110 +707,79 @@ static int reduce_launch(const half_t* x, const half_t* dy, half_t* dout, int M,
     const RowGeom g = row_geometry(M, C, max_gy);
     hipLaunchKernelGGL((bn_reduce_kernel<MODE>), dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dout, M, C, g.cx_log2,
                        mean, rstd, gamma, beta, flag, sums ? ws : (float*)nullptr);
-    if (sums) {
-        const int n = 2 * C;
-        hipLaunchKernelGGL(fold_partials_kernel, dim3((n + 31) / 32), dim3(1024), 0, st, ws, g.gy, n, sums, g0, g1,
-                           gscale, g_count, 0);
-    }
+    if (sums) fold_sums(ws, g.gy, 2 * C, 1, 0, sums, g0, g1, gscale, 0, 0, g_count, st);
     return LAUNCH_OK();
 }
 
 int bn_stats_finalize_launch(const half_t* x, int M, int C, float* sums, float* ws, int64_t ws_floats, float count,
-                             const float* gamma, const float* beta, float eps, float momentum, int updates, float* rm,
-                             float* rv, float* mean, float* rstd, float* scale, float* shift, long long* nbt,
-                             hipStream_t st) {
+                             const BnFinalize& f, hipStream_t st) {
     if (!ws || ws_floats < 2 * (int64_t)C) return E_WORKSPACE;
     const RowGeom g = row_geometry(M, C, (int)(ws_floats / (2 * (int64_t)C)));
     hipLaunchKernelGGL((bn_reduce_kernel<0>), dim3(g.gx, g.gy), dim3(256), 0, st, x, (const half_t*)nullptr,
                        (half_t*)nullptr, M, C, g.cx_log2, (const float*)nullptr, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, 0, ws);
-    hipLaunchKernelGGL(fold_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, st, ws, g.gy, C, sums, count, gamma,
-                       beta, eps, momentum, updates, rm, rv, mean, rstd, scale, shift, nbt);
+    hipLaunchKernelGGL(fold_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, st, ws, g.gy, C, sums, count, f);
     return LAUNCH_OK();
 }
-// Statistics rows of a contraction's epilogue (StatEpi): part [rows][2][C] -> sums (+ finalize).  More than 512 rows are
-// folded in two stages through `scratch` (FOLD_STAGE_ROWS x 2C floats).
-static const float* fold_stage1(const float* part, int& rows, int n, float* scratch, hipStream_t st) {
+// Statistics rows of a contraction's epilogue (StatEpi), G groups of them: part [G][..][n], group stride `gstride`.  More
+// than 512 rows are folded in two stages through `scratch` ([G][FOLD_STAGE_ROWS][n] floats): returns the rows to fold
+// next and updates their count and group stride.
+static const float* fold_stage1(const float* part, int& rows, int n, int G, int64_t& gstride, float* scratch,
+                                hipStream_t st) {
     if (rows <= 512) return part;        // one 1024-thread block per 32 channels folds 512 rows in 8 four-deep iterations
     const int per = (rows + FOLD_STAGE_ROWS - 1) / FOLD_STAGE_ROWS;
     const int ny = (rows + per - 1) / per;
-    hipLaunchKernelGGL(fold_rows_kernel, dim3((n + 31) / 32, ny), dim3(1024), 0, st, part, rows, n, per, scratch,
-                       (int64_t)0, (int64_t)0);
+    const int64_t out_gstride = (int64_t)FOLD_STAGE_ROWS * n;
+    hipLaunchKernelGGL(fold_rows_kernel, dim3((n + 31) / 32, ny, G), dim3(1024), 0, st, part, rows, n, per, scratch,
+                       gstride, out_gstride);
     rows = ny;
+    gstride = out_gstride;
     return scratch;
 }
 int bn_fold_finalize_launch(const float* part, int rows, int C, float* scratch, float* sums, float count,
-                            const float* gamma, const float* beta, float eps, float momentum, int updates, float* rm,
-                            float* rv, float* mean, float* rstd, float* scale, float* shift, long long* nbt,
-                            hipStream_t st) {
-    const float* src = fold_stage1(part, rows, 2 * C, scratch, st);
-    hipLaunchKernelGGL(fold_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, st, src, rows, C, sums, count, gamma,
-                       beta, eps, momentum, updates, rm, rv, mean, rstd, scale, shift, nbt);
+                            const BnFinalize& f, hipStream_t st) {
+    int64_t gstride = 0;
+    const float* src = fold_stage1(part, rows, 2 * C, 1, gstride, scratch, st);
+    hipLaunchKernelGGL(fold_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, st, src, rows, C, sums, count, f);
     return LAUNCH_OK();
 }
 int bn_fold_launch(const float* part, int rows, int n, float* scratch, float* sums, hipStream_t st) {
-    const float* src = fold_stage1(part, rows, n, scratch, st);
-    hipLaunchKernelGGL(fold_partials_kernel, dim3((n + 31) / 32), dim3(1024), 0, st, src, rows, n, sums,
-                       (float*)nullptr, (float*)nullptr, 0.f, 0, 0);
+    int64_t gstride = 0;
+    const float* src = fold_stage1(part, rows, n, 1, gstride, scratch, st);
+    fold_sums(src, rows, n, 1, 0, sums, nullptr, nullptr, 0.f, 0, 0, 0, st);
     return LAUNCH_OK();
 }
-// part [G][rows_cap][2][C] (the first `rows` rows of each group are valid) -> sums [G][2][C] (+ parameter gradients)
+// part [G][rows_cap][2][C] (the first `rows` rows of each group are valid) -> sums [G][2][C]; group `pgroup` also gives
+// the parameter gradients d beta += gscale * sum g, d gamma += gscale * sum g*xhat
 int bn_bwd_fold_launch(const float* part, int rows, int rows_cap, int C, int G, float* scratch, float* sums,
                        float* dbeta, float* dgamma, float gscale, int pgroup, hipStream_t st) {
     const int n = 2 * C;
     int64_t gstride = (int64_t)rows_cap * n;
-    const float* src = part;
-    if (rows > 512) {
-        const int per = (rows + FOLD_STAGE_ROWS - 1) / FOLD_STAGE_ROWS;
-        const int ny = (rows + per - 1) / per;
-        hipLaunchKernelGGL(fold_rows_kernel, dim3((n + 31) / 32, ny, G), dim3(1024), 0, st, part, rows, n, per, scratch,
-                           gstride, (int64_t)FOLD_STAGE_ROWS * n);
-        src = scratch;
-        rows = ny;
-        gstride = (int64_t)FOLD_STAGE_ROWS * n;
-    }
-    hipLaunchKernelGGL(fold_groups_kernel, dim3((n + 31) / 32, G), dim3(1024), 0, st, src, rows, n, gstride, sums, dbeta,
-                       dgamma, gscale, pgroup);
+    const float* src = fold_stage1(part, rows, n, G, gstride, scratch, st);
+    fold_sums(src, rows, n, G, gstride, sums, dbeta, dgamma, gscale, pgroup, 0, C, st);
     return LAUNCH_OK();
 }
-int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, const float* gamma, const float* beta,
-                       float eps, float momentum, int updates, float* rm, float* rv, float* mean, float* rstd,
-                       float* scale, float* shift, float* sums2C, long long* nbt, int relu, const float* in_scale,
-                       hipStream_t st) {
+int bn_cols_fwd_launch(const half_t* x, half_t* y, int M, int C, float count, const BnFinalize& f, float* sums2C,
+                       int relu, hipStream_t st) {
     const int nch = C / 8;
-    hipLaunchKernelGGL(bn_cols_fwd_kernel, dim3((nch + COLS_CX - 1) / COLS_CX), dim3(256), 0, st, x, y, M, C, count, gamma,
-                       beta, eps, momentum, updates, rm, rv, mean, rstd, scale, shift, sums2C, nbt, relu, in_scale);
+    hipLaunchKernelGGL(bn_cols_fwd_kernel, dim3((nch + COLS_CX - 1) / COLS_CX), dim3(256), 0, st, x, y, M, C, count, f,
+                       sums2C, relu);
     return LAUNCH_OK();
 }
 int bn_cols_bwd_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, float* sums,
                        float* dbeta, float* dgamma, float gscale, int pstream, int* cnt, hipStream_t st) {
     const int nch = C / 8;
-    const dim3 grid((nch + COLS_CX - 1) / COLS_CX);
-    if (cnt) {
-        if (nstreams == 1)
-            hipLaunchKernelGGL((bn_cols_bwd_cnt_kernel<1>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd,
-                               gamma, beta, relu, sums, dbeta, dgamma, gscale, pstream, cnt);
-        else if (nstreams == 2)
-            hipLaunchKernelGGL((bn_cols_bwd_cnt_kernel<2>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd,
-                               gamma, beta, relu, sums, dbeta, dgamma, gscale, pstream, cnt);
-        else
-            return E_UNSUPPORTED;
+    return bwd_dispatch(nstreams, cnt != nullptr, [&](auto ns, auto count_on) {
+        hipLaunchKernelGGL((bn_cols_bwd_kernel<ns(), count_on()>), dim3((nch + COLS_CX - 1) / COLS_CX), dim3(256), 0, st,
+                           x, dy, dx, M, C, 1.f / count, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma, gscale,
+                           pstream, cnt);
         return LAUNCH_OK();
-    }
-    if (nstreams == 1)
-        hipLaunchKernelGGL((bn_cols_bwd_kernel<1>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd, gamma,
-                           beta, relu, sums, dbeta, dgamma, gscale, pstream);
-    else if (nstreams == 2)
-        hipLaunchKernelGGL((bn_cols_bwd_kernel<2>), grid, dim3(256), 0, st, x, dy, dx, M, C, 1.f / count, mean, rstd, gamma,
-                           beta, relu, sums, dbeta, dgamma, gscale, pstream);
-    else
-        return E_UNSUPPORTED;
-    return LAUNCH_OK();
+    });
 }
 int bn_stats_launch(const half_t* x, int M, int C, float* sums, float* ws, int64_t ws_floats, hipStream_t st) {
-    return reduce_launch<0>(x, nullptr, nullptr, M, C, nullptr, nullptr, nullptr, nullptr, 0, sums, ws, ws_floats,
-                            st);
+    return reduce_launch<0>(x, nullptr, nullptr, M, C, nullptr, nullptr, nullptr, nullptr, 0, sums, ws, ws_floats, st,
+                            nullptr, nullptr, 0.f, 0);
 }
 // column sums of fp16 rows [M][C] (C % 8 == 0) through the statistics reduction: sums2C = [sum x | sum x^2]; dbias (may be
 // null): dbias[c] += gscale * sum x[c], c < dbias_n.  The many-row form of colsum_acc_launch (layout.hip).
@@ -926,12 +788,6 @@ int colsum_rows_launch(const half_t* x, int M, int C, float* sums2C, float* ws, 
     return reduce_launch<0>(x, nullptr, nullptr, M, C, nullptr, nullptr, nullptr, nullptr, 0, sums2C, ws, ws_floats, st, dbias,
                             nullptr, gscale, dbias_n);
 }
-int bn_bwd_reduce_launch(const half_t* x, const half_t* dy, int M, int C, const float* mean, const float* rstd,
-                         const float* gamma, const float* beta, int relu, float* sums, float* ws, int64_t ws_floats,
-                         float* dbeta, float* dgamma, float gscale, hipStream_t st) {
-    return reduce_launch<1>(x, dy, nullptr, M, C, mean, rstd, gamma, beta, relu, sums, ws, ws_floats, st, dbeta, dgamma,
-                            gscale);
-}
 // colsum may be null (then no reduction is performed); colsum gets [2][C] (second half unused).  dbias (may be null):
 // dbias[c] += gscale * colsum[c], c < dbias_n <= C, in the fold of the partial sums (one writer per element).
 int act_bwd_launch(const half_t* y, const half_t* dy, half_t* dpre, int M, int C, int act, float* colsum, float* ws,
@@ -939,23 +795,23 @@ int act_bwd_launch(const half_t* y, const half_t* dy, half_t* dpre, int M, int C
     return reduce_launch<2>(y, dy, dpre, M, C, nullptr, nullptr, nullptr, nullptr, act, colsum, ws, ws_floats, st, dbias,
                             nullptr, gscale, dbias_n);
 }
-int bn_bwd_reduce2_launch(const half_t* x, const half_t* dy, int M, int C, const float* mean, const float* rstd,
-                          const float* gamma, const float* beta, int relu, float* sums4C, float* ws, int64_t ws_floats,
-                          float* dbeta, float* dgamma, float gscale, int param_stream, hipStream_t st) {
-    if (!ws || ws_floats < 4 * (int64_t)C) return E_WORKSPACE;
-    const RowGeom g = row_geometry(M, C, (int)(ws_floats / (4 * (int64_t)C)));
-    hipLaunchKernelGGL(bn_reduce2_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, M, C, g.cx_log2, mean, rstd, gamma,
-                       beta, relu, ws);
-    const int n = 4 * C;
-    hipLaunchKernelGGL(fold_partials_kernel, dim3((n + 31) / 32), dim3(1024), 0, st, ws, g.gy, n, sums4C, dbeta, dgamma,
-                       gscale, C, param_stream ? 2 * C : 0);
-    return LAUNCH_OK();
+// sums [nstreams][2][C]; dbeta / dgamma (may be null) += gscale * the sums of stream `param_stream`
+int bn_bwd_reduce_launch(const half_t* x, const half_t* dy, int M, int C, int nstreams, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, int relu, float* sums, float* ws,
+                         int64_t ws_floats, float* dbeta, float* dgamma, float gscale, int param_stream,
+                         hipStream_t st) {
+    const int64_t n = 2 * (int64_t)nstreams * C;
+    if (!ws || ws_floats < n) return E_WORKSPACE;
+    const RowGeom g = row_geometry(M, C, (int)(ws_floats / n));
+    return bwd_dispatch(nstreams, false, [&](auto ns, auto) {
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<ns()>), dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, M, C, g.cx_log2, mean,
+                           rstd, gamma, beta, relu, ws);
+        fold_sums(ws, g.gy, (int)n, 1, 0, sums, dbeta, dgamma, gscale, 0, param_stream * 2 * C, C, st);
+        return LAUNCH_OK();
+    });
 }
-int bn_finalize_launch(const float* sums, int C, float count, const float* gamma, const float* beta, float eps,
-                       float momentum, int updates, float* rm, float* rv, float* mean, float* rstd, float* scale,
-                       float* shift, long long* nbt, const float* in_scale, hipStream_t st) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, C, count, gamma, beta, eps,
-                       momentum, updates, rm, rv, mean, rstd, scale, shift, nbt, in_scale);
+int bn_finalize_launch(const float* sums, int C, float count, const BnFinalize& f, hipStream_t st) {
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, C, count, f);
     return LAUNCH_OK();
 }
 static RowGeom stream_geometry(int M, int C) {
@@ -976,31 +832,15 @@ int bn_apply_launch(const half_t* x, half_t* y, int M, int C, const float* scale
                        (const float*)nullptr);
     return LAUNCH_OK();
 }
-int bn_bwd_apply2_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
-                         const float* rstd, const float* gamma, const float* beta, int relu, const float* sums4C,
-                         int* cnt, hipStream_t st) {
+int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, int nstreams, float count,
+                        const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
+                        const float* sums, int* cnt, hipStream_t st) {
     const RowGeom g = stream_geometry(M, C);
-    if (cnt) {
-        hipLaunchKernelGGL(bn_stream2_cnt_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
-                           gamma, beta, relu, 1.f / count, sums4C, cnt);
+    return bwd_dispatch(nstreams, cnt != nullptr, [&](auto ns, auto count_on) {
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<ns(), count_on()>), dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C,
+                           g.cx_log2, mean, rstd, gamma, beta, relu, 1.f / count, sums, cnt);
         return LAUNCH_OK();
-    }
-    hipLaunchKernelGGL(bn_stream2_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
-                       gamma, beta, relu, 1.f / count, sums4C);
-    return LAUNCH_OK();
-}
-int bn_bwd_apply_launch(const half_t* x, const half_t* dy, half_t* dx, int M, int C, float count, const float* mean,
-                        const float* rstd, const float* gamma, const float* beta, int relu, const float* sums,
-                        int* cnt, hipStream_t st) {
-    const RowGeom g = stream_geometry(M, C);
-    if (cnt) {
-        hipLaunchKernelGGL(bn_stream_cnt_kernel, dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean, rstd,
-                           gamma, beta, relu, 1.f / count, sums, cnt);
-        return LAUNCH_OK();
-    }
-    hipLaunchKernelGGL((bn_stream_kernel<1>), dim3(g.gx, g.gy), dim3(256), 0, st, x, dy, dx, M, C, g.cx_log2, mean,
-                       rstd, gamma, beta, relu, 1.f / count, sums);
-    return LAUNCH_OK();
+    });
 }
 
 }  // namespace fmri
