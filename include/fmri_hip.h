@@ -241,6 +241,28 @@ int64_t fmri_ssim_pairs_ws_bytes(int N, int M, int C, int H, int W);
 int fmri_ssim_pairs(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
                     float* out, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- validation metrics of a batch in the engine's image layout (evaluation pass of the fused steps) ----------
+ * fmri_image_metrics: out7[0..2] = PCC (PearsonCorrelation.forward over the whole batch, :276-292), mean SSIM
+ *   (StructuralSimilarity.forward, size_average, :343-420: 11x11 Gaussian sigma 1.5, padding 5, C1 = 1e-4, C2 = 9e-4)
+ *   and MSE (nn.MSELoss over the N C H W real elements) of pred16 against truth16, both fp16 [N][H][W][Cp] with
+ *   channels 0..C-1 real (lanes C..Cp-1 may hold anything: they reach no sum), 16-byte aligned.  scale / shift: HOST
+ *   float[C] each, or both NULL -- the metrics are then those of v * scale[c] + shift[c] (denormalize_image, :234-240),
+ *   applied in fp32 to in-image pixels only (the padding stays 0).  Launch 1: one block per 16 x 16 tile of one pair,
+ *   all channels, one 16-byte load per pixel of the 26 x 26 halo; window, filtered statistics and SSIM map in fp64
+ *   (as fmri_ssim_pairs), plus the tile's fp64 sums of x, y, x^2, y^2, xy and (x - y)^2; 7 doubles per block into ws
+ *   (fmri_image_metrics_ws_bytes(N, H, W) bytes; < 0: bad geometry).  Launch 2: one block folds them in a fixed order.
+ *   acc4 (device double[4]: sums of pcc, ssim, mse over batches, and the batch count; may be NULL): launch 2 also adds
+ *   this batch -- after clearing acc4 when acc_mode = 0, on top of it when acc_mode = 1 -- and writes the running means
+ *   and the count to out7[3..6]; with acc4 NULL out7[3..6] are left alone.
+ *   No atomics, no allocation, no host sync; two launches per call.  out7[0..2] is a bitwise function of the two
+ *   tensors and (N, H, W, C, scale, shift) only: two calls are bit-identical with fmri_set_deterministic on or off.
+ *   H or W < 11: FMRI_E_UNSUPPORTED, as fmri_ssim; Cp != 8: FMRI_E_UNSUPPORTED; ws_bytes too small: FMRI_E_WORKSPACE;
+ *   nothing is launched then. */
+int64_t fmri_image_metrics_ws_bytes(int N, int H, int W);
+int fmri_image_metrics(const void* pred16, const void* truth16, int N, int H, int W, int C, int Cp,
+                       const float* scale, const float* shift,      /* host float[C] each, or both NULL */
+                       void* ws, int64_t ws_bytes, float* out7, double* acc4, int acc_mode, void* stream);
+
 /* ---- layout casts ------------------------------------------------------------------------------- */
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream);
 int fmri_nhwc_to_nchw(const void* src, float* dst, int N, int C, int HW, int Cp, float scale, void* stream);

@@ -133,6 +133,21 @@ int fmri_ssim_pairs(const float* pred, const float* truth, int N, int M, int C, 
     if (((int64_t)N + M) * C > INT32_MAX || H > 65535 * 16 || W > 65535 * 16) return FMRI_E_UNSUPPORTED;
     return ssim_pairs_launch(pred, truth, N, M, C, H, W, pairs, P, out, ws, ws_bytes, S(stream));
 }
+/* ---- PCC / SSIM / MSE of a batch in the engine's image layout (the evaluation pass, fmri_hip/evaluate.py) ---- */
+int64_t fmri_image_metrics_ws_bytes(int N, int H, int W) { return image_metrics_ws_bytes(N, H, W); }
+int fmri_image_metrics(const void* pred16, const void* truth16, int N, int H, int W, int C, int Cp, const float* scale,
+                       const float* shift, void* ws, int64_t ws_bytes, float* out7, double* acc4, int acc_mode,
+                       void* stream) {
+    if (!pred16 || !truth16 || !ws || !out7 || N < 1 || H < 1 || W < 1 || C < 1 || C > 8 || (!scale) != (!shift) ||
+        ((uintptr_t)pred16 & 15) || ((uintptr_t)truth16 & 15) || ((uintptr_t)ws & 7) || ((uintptr_t)out7 & 3) ||
+        ((uintptr_t)acc4 & 7) || (acc4 && acc_mode != 0 && acc_mode != 1))
+        return FMRI_E_BADARG;
+    if (Cp != 8) return FMRI_E_UNSUPPORTED;            // one 16-byte load per pixel
+    if (H < 11 || W < 11) return FMRI_E_UNSUPPORTED;   // as fmri_ssim: the reference's window shrinks, its padding not
+    if (N > 65535 || H > 65535 * 16) return FMRI_E_UNSUPPORTED;     // y / z grid dimensions
+    return image_metrics_launch((const half_t*)pred16, (const half_t*)truth16, N, H, W, C, scale, shift, ws, ws_bytes,
+                                out7, acc4, acc_mode, S(stream));
+}
 
 int fmri_version(void) { return 100; }
 

@@ -20,23 +20,13 @@
 // (C, H, W) only, and there are no atomics.  Two calls are bit-identical, a pair's value does not depend on its
 // position in the list, on N, M or P, and truth_j == truth_i bitwise gives S_ij == S_ii bitwise.
 #include "kernels.h"
+#include "ssim_window.h"
 
 namespace fmri {
 
 namespace {
 
 constexpr int PCC_KC = 1024;      // K chunk of the Gram: fixed, so a pair's partial sums depend on D only
-constexpr int SS_TS = 16, SS_WIN = 11, SS_PAD = 5, SS_R = SS_TS + SS_WIN - 1;   // 26
-
-// fixed-order sum over a 256-thread block (wave tree, then the four waves in order); every thread gets the total
-__device__ inline double block_sum_fixed(double v, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 __global__ __launch_bounds__(256) void ident_rowstats_kernel(const float* __restrict__ pred, int N,
                                                              const float* __restrict__ truth, int M, int64_t D,
@@ -108,16 +98,6 @@ __global__ __launch_bounds__(256) void ident_pcc_final_kernel(const float* __res
         double g = 0.0;
         for (int c = 0; c < chunks; ++c) g += (double)part[(int64_t)c * nm + e];
         S[(int64_t)i * ldS + j] = (float)(g / (norm[i] * norm[N + j]));
-    }
-}
-
-// gaussian(11, 1.5) normalised to sum 1, in fp64 (the reference's window is the fp32 rounding of the same numbers)
-__device__ inline void gauss11(double* g) {
-    if (threadIdx.x < SS_WIN) {
-        double s = 0.0;
-        for (int i = 0; i < SS_WIN; ++i) s += exp(-(double)((i - 5) * (i - 5)) / 4.5);
-        const int i = threadIdx.x;
-        g[i] = exp(-(double)((i - 5) * (i - 5)) / 4.5) / s;
     }
 }
 

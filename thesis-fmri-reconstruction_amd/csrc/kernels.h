@@ -311,5 +311,9 @@ int pcc_matrix_launch(const float* pred, const float* truth, int N, int M, int64
 int64_t ssim_pairs_ws_bytes(int N, int M, int C, int H, int W);
 int ssim_pairs_launch(const float* pred, const float* truth, int N, int M, int C, int H, int W, const int* pairs, int P,
                       float* out, void* ws, int64_t ws_bytes, hipStream_t st);
+int64_t image_metrics_ws_bytes(int N, int H, int W);
+int image_metrics_launch(const half_t* pred, const half_t* truth, int N, int H, int W, int C, const float* scale,
+                         const float* shift, void* ws, int64_t ws_bytes, float* out7, double* acc4, int acc_mode,
+                         hipStream_t st);
 
 }  // namespace fmri

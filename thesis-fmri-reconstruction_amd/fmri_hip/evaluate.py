@@ -1,0 +1,234 @@
+"""On-device validation pass of the fused steps (csrc/evalmetrics.hip; include/fmri_hip.h fmri_image_metrics).
+
+The block of the scripts' epoch that a fused step could not run: the epoch-end metrics (train/train_vgan_stage1.py:487-520
+and its copies) and ``evaluate()`` over a whole validation set (train/train_utils.py:678-749, without the Inception score
+and the image dumps).  The eval-mode forward of the step's OWN networks -- BatchNorm from running statistics, applied in
+the conv epilogues -- goes straight into one metrics kernel pair per batch, and a pass leaves one row in a device ring:
+
+    ev = Evaluator(step, DeviceDataset(val_images_u8, val_fmri), batch=64, rng=DeviceRng(seed_eval, dev))
+    for epoch in range(epochs):
+        for _ in range(steps_per_epoch):
+            replay()
+        ev.train_batch()                # PCC / SSIM / MSE of the last training batch (train-mode x_tilde)
+        ev.run()                        # the whole validation set in eval mode, one row
+    h = ev.history()                    # ONE sync
+
+The forward per step class follows models/vae_gan.py: ``Stage1Step`` / ``DualStage1Step`` decoder(mu + eps * exp(logvar / 2))
+of encoder(x) (``VaeGan.forward`` reparameterises in eval mode too); ``CognitiveStep`` the same from
+cognitive_encoder(fmri), against the dataset image; ``WaeStep`` decoder(encoder(x).mu) in Stage I and
+decoder(cognitive_encoder(fmri).mu) in Stages II / III (no noise).
+
+Columns of a row: ``epoch`` (of the step's training feed, read on the device; only with a feed), ``batches``,
+``valid_PCC / valid_SSIM / valid_MSE`` (the LAST batch: what the scripts' epoch-end block leaves in
+``result_metrics_valid``, overwritten per batch), ``mean_PCC / mean_SSIM / mean_MSE`` (the mean over the batches, every
+batch weighted equally: what ``evaluate()`` returns) and ``train_PCC / train_SSIM / train_MSE`` (the last
+``train_batch()`` since the previous row, NaN without one).
+
+A pass leaves training where it was: ``bn.eval_mode`` is set for the pass and restored, no running statistic and no
+``num_batches_tracked`` moves, nothing the step owns is written or re-bound (latent range scratch, noise, batch buffers and
+the generator are the evaluator's own), and a step recorded with ``capture()`` before or after replays unchanged.  The pass
+sees the weights and statistics of the last step, replayed ones included: the fp16 GEMM copies follow the groups' version
+counters, and ``dec.fc_bn`` keeps its LIVE running statistics in engine order (ops.BatchNorm.enable_lazy_running), which is
+what its eval-mode forward reads -- nothing has to be flushed.
+
+Nothing here synchronises with the host except ``history()``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import lib, ops
+from .feed import DeviceDataset
+from .ops import nhwc_to_images, pad8
+from .rng import SID_EPS, DeviceRng, blocks
+from .schedule import TrainLog
+
+_P = lib.ptr
+
+METRICS = ("PCC", "SSIM", "MSE")
+
+
+def batch_ranges(n: int, batch: int) -> List[Tuple[int, int]]:
+    """(first row, rows) of the batches of a pass over ``n`` dataset rows: in order, no drop-last -- the scripts'
+    validation loaders have ``shuffle=False`` and the default ``drop_last``."""
+    if n < 1 or batch < 1:
+        raise ValueError("batch_ranges: n >= 1 and batch >= 1")
+    return [(r, min(batch, n - r)) for r in range(0, n, batch)]
+
+
+class Evaluator:
+    """``step``: a Stage1Step / DualStage1Step / CognitiveStep / WaeStep.  ``dataset``: the validation set (with fMRI rows
+    where the step takes fMRI).  ``rng``: the evaluator's OWN generator for ``eps`` (stream SID_EPS, advanced by the
+    evaluator after every batch); needed only where the eval forward samples.  ``mean`` / ``std``: the ingest
+    normalisation, as DeviceFeed.  ``denorm``: metrics on v * std + mean (``evaluate(norm=True)``, denormalize_image)
+    instead of the normalised images.  ``capacity``: rows of the ring.
+
+    With ``distributed=True`` steps every rank evaluates the whole set by itself: there is no collective in a pass."""
+
+    def __init__(self, step, dataset: DeviceDataset, batch: int, rng: Optional[DeviceRng] = None,
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), denorm: bool = False, capacity: int = 1024):
+        from .steps import CognitiveStep, Stage1Step
+        from .wae_steps import WaeStep
+        if isinstance(step, WaeStep):
+            self.enc, self.uses_fmri, self.samples = (step.img_enc if step.stage == 1 else step.cog), step.stage > 1, False
+        elif isinstance(step, CognitiveStep):
+            self.enc, self.uses_fmri, self.samples = step.cog, True, True
+        elif isinstance(step, Stage1Step):
+            self.enc, self.uses_fmri, self.samples = step.enc, False, True
+        else:
+            raise TypeError("Evaluator: step must be a Stage1Step, DualStage1Step, CognitiveStep or WaeStep")
+        self.step, self.ds, self.dec = step, dataset, step.dec
+        cfg = step.cfg
+        N, H, W, _ = dataset.images.shape
+        if (H, W) != (cfg.image_size, cfg.image_size):
+            raise ValueError(f"Evaluator: validation images are {H} x {W}, the step's are {cfg.image_size} x "
+                             f"{cfg.image_size}")
+        if dataset.images.device != step.device:
+            raise ValueError("Evaluator: the dataset lives on another device than the step")
+        if self.uses_fmri and (dataset.fmri is None or dataset.fmri.shape[1] != step.n_voxels):
+            raise ValueError("Evaluator: this step takes fMRI -- the dataset needs fp32 fMRI rows of n_voxels columns")
+        if self.samples and rng is None:
+            raise ValueError("Evaluator: the eval-mode forward of this step samples z = mu + eps * sigma -- pass "
+                             "rng=DeviceRng(seed, device)")
+        if rng is not None and rng.device != step.device:
+            raise ValueError("Evaluator: rng lives on another device than the step")
+        if int(batch) != batch or batch < 1:
+            raise ValueError("Evaluator: batch must be an integer >= 1")
+        self.rng = rng if self.samples else None
+        self.B = B = min(int(batch), N)
+        self.ranges = batch_ranges(N, B)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        if denorm:
+            self._scale, self._shift = (C.c_float * 3)(*self.std), (C.c_float * 3)(*self.mean)
+        else:
+            self._scale = self._shift = None
+        dev = step.device
+        Z = cfg.latent_dim
+        self.H, self.W, self.Z = H, W, Z
+        # persistent buffers (a short last batch uses their first rows)
+        self._idx = torch.arange(N, dtype=torch.int32, device=dev)
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._x16 = torch.empty(B, H, W, 8, dtype=torch.float16, device=dev)
+        self._pred16 = torch.empty(B, H, W, 8, dtype=torch.float16, device=dev)
+        self._fmri16 = (torch.empty(B, pad8(dataset.fmri.shape[1]), dtype=torch.float16, device=dev)
+                        if self.uses_fmri else None)
+        self._eps = torch.empty(B, Z, dtype=torch.float32, device=dev) if self.samples else None
+        self._z16 = torch.empty(B, pad8(Z), dtype=torch.float16, device=dev)
+        self._zst = torch.zeros(2, dtype=torch.float32, device=dev)          # [max |z|, range scale] of the batch
+        self._last_rows = 0
+        # metrics: one row [pcc, ssim, mse, running means, batches] per batch of the pass, written by the fold launch
+        self._ws_bytes = lib.load().fmri_image_metrics_ws_bytes(B, H, W)
+        self._ws = torch.empty(self._ws_bytes // 8, dtype=torch.float64, device=dev)
+        self._acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        self._bm = torch.zeros(len(self.ranges), 7, dtype=torch.float32, device=dev)
+        self._train = torch.full((7,), float("nan"), dtype=torch.float32, device=dev)
+        last = (len(self.ranges) - 1) * 7
+        flat = self._bm.view(-1)
+        cols = [("epoch", step.feed._state, 1)] if step.feed is not None else []
+        cols.append(("batches", flat, last + 6))
+        cols += [(f"valid_{m}", flat, last + k) for k, m in enumerate(METRICS)]
+        cols += [(f"mean_{m}", flat, last + 3 + k) for k, m in enumerate(METRICS)]
+        cols += [(f"train_{m}", self._train, k) for k, m in enumerate(METRICS)]
+        self.log = TrainLog(capacity)
+        self.log.attach(dev, cols, ())
+
+    # ---- the metrics of one batch: two launches ----------------------------------------------------------------------
+    def _metrics(self, pred16: torch.Tensor, truth16: torch.Tensor, out7: torch.Tensor, acc, acc_mode: int):
+        n, H, W, cp = pred16.shape
+        nbytes = lib.load().fmri_image_metrics_ws_bytes(n, H, W)
+        if nbytes > self._ws_bytes:          # (a training batch larger than the validation batch)
+            self._ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred16.device)
+            self._ws_bytes = nbytes
+        sc = None if self._scale is None else C.cast(self._scale, C.c_void_p)
+        sf = None if self._shift is None else C.cast(self._shift, C.c_void_p)
+        lib.call("fmri_image_metrics", _P(pred16), _P(truth16), n, H, W, 3, cp, sc, sf, _P(self._ws), self._ws_bytes,
+                 _P(out7), _P(acc), acc_mode)
+
+    # ---- the eval-mode forward of one batch --------------------------------------------------------------------------
+    def _forward(self, r0: int, b: int):
+        ds, Z = self.ds, self.Z
+        N, H, W, Cimg = ds.images.shape
+        idx = self._idx[r0:r0 + b]
+        x16, pred16, z16 = self._x16[:b], self._pred16[:b], self._z16[:b]
+        m, s = self.mean, self.std
+        lib.call("fmri_ingest_u8_gather", _P(ds.images), _P(idx), N, b, H, W, Cimg, None, None, m[0], m[1], m[2], s[0],
+                 s[1], s[2], _P(x16), None, _P(self._err))
+        if self.uses_fmri:
+            lib.call("fmri_gather_rows_f32", _P(ds.fmri), N, ds.fmri.shape[1], _P(idx), b, None, _P(self._fmri16[:b]),
+                     _P(self._err))
+            head32, _ = self.enc.forward(self._fmri16[:b])
+        else:
+            head32, _ = self.enc.forward(x16)
+        if self.samples:
+            eps = self._eps[:b]
+            self.rng.normal(b, Z, SID_EPS, out=eps)
+            self.rng.advance(blocks(b * Z))
+            self._zst.zero_()
+            ops.latent_ranged(head32, eps, b, Z, z16, self._zst[0:1], self._zst[1:2], sample=True)
+            self.dec.forward(z16, 1, out=pred16, zscale=self._zst[1:2])
+        else:
+            lib.call("fmri_latent_fwd", _P(head32), None, b, Z, z16.shape[1], _P(z16), None, None, 0)      # z = mu
+            self.dec.forward(z16, 1, out=pred16)
+        self._last_rows = b
+        return pred16, x16
+
+    def run(self):
+        """One pass over the validation set in eval mode and one row in the ring; enqueues only."""
+        ops.require_gpu(self.ds.images)
+        bns = [bn for net in (self.enc, self.dec) for bn in net.all_bns()]
+        was = [bn.eval_mode for bn in bns]
+        for bn in bns:
+            bn.eval_mode = True
+        try:
+            for k, (r0, b) in enumerate(self.ranges):
+                pred16, x16 = self._forward(r0, b)
+                self._metrics(pred16, x16, self._bm[k], self._acc, 0 if k == 0 else 1)
+        finally:
+            for bn, w in zip(bns, was):
+                bn.eval_mode = w
+        self.log.append()
+        self._train.fill_(float("nan"))          # a train_batch() counts for the next row only
+
+    def train_batch(self):
+        """PCC / SSIM / MSE of the step's last TRAINING batch -- its train-mode ``x_tilde`` against the block the script
+        compares it with (``x`` in Stage I, the ``x_gt`` the model returned in Stages II / III) -- into the ``train_*``
+        columns of the next row; enqueues only."""
+        from .wae_steps import WaeStep
+        fw = self.step.fw
+        if not fw:
+            raise RuntimeError("Evaluator.train_batch(): the step has not run yet")
+        if isinstance(self.step, WaeStep):
+            pred16, truth16 = fw["y"], fw["x16"]
+        else:
+            B, d = fw["B"], fw["disc_in"]
+            pred16, truth16 = d[B:2 * B], d[:B]
+        self._metrics(pred16, truth16, self._train, None, 0)
+
+    # ---- reading back ---------------------------------------------------------------------------------------------------
+    def history(self) -> Dict[str, np.ndarray]:
+        """ONE sync: column name -> numpy array over the last min(passes, capacity) passes, oldest first, and ``"pass"``,
+        their absolute numbers."""
+        h = self.log.history()
+        h["pass"] = h.pop("step")
+        h["batches"] = np.rint(h["batches"]).astype(np.int64)
+        return h
+
+    def batch_metrics(self) -> torch.Tensor:
+        """Device fp32 [n_batches, 3]: PCC, SSIM, MSE of every batch of the last pass (a view: the next pass rewrites it)."""
+        return self._bm[:, :3]
+
+    def last_output(self) -> torch.Tensor:
+        """fp32 NCHW reconstructions of the last batch of the last pass."""
+        return nhwc_to_images(self._pred16[:self._last_rows], 3)
+
+    def last_truth(self) -> torch.Tensor:
+        """fp32 NCHW ingested (normalised) images of the last batch of the last pass."""
+        return nhwc_to_images(self._x16[:self._last_rows], 3)
+
+    def last_noise(self) -> Optional[torch.Tensor]:
+        """fp32 [rows, latent_dim] ``eps`` of the last batch of the last pass (a copy); None where nothing is sampled."""
+        return self._eps[:self._last_rows].clone() if self.samples else None

@@ -268,7 +268,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
             self.opt_enc.step(gdev=self.scal[S_NE:S_NE + 1])
         if train_dec:
             self.opt_dec.step()
-        self.fw = dict(B=B, y=y, head32=head32, Z=Z)
+        self.fw = dict(B=B, y=y, x16=x16, head32=head32, Z=Z)      # (x16: what Evaluator.train_batch compares y with)
         if self.mon is not None:
             self.mon.tail(head32, Z, [self.scal[:len(W_LOG_KEYS)]], None)
         self._log_append()
