@@ -263,6 +263,37 @@ int fmri_image_metrics(const void* pred16, const void* truth16, int N, int H, in
                        const float* scale, const float* shift,      /* host float[C] each, or both NULL */
                        void* ws, int64_t ws_bytes, float* out7, double* acc4, int acc_mode, void* stream);
 
+/* ---- n-way identification of a batch in the engine's image layout (objective_assessment, :752-816, on the device) ----
+ * fmri_nway_scores: pred16 / truth16 fp16 [n][H][W][Cp], 16-byte aligned, channels 0..C-1 real (lanes C..Cp-1 may hold
+ *   anything: they reach no sum), n >= 2, C <= 4.
+ *   s_pcc[i * n + j] = PearsonCorrelation.forward(pred_i, truth_j) over one image, s_ssim[i * n + j] = the pair's mean
+ *   SSIM: the definitions of fmri_pcc_matrix / fmri_ssim_pairs on the fp32 values of the fp16 elements (window, filtered
+ *   statistics and SSIM map fp64; centring and norm fp64, the Gram fp32 MFMA chains of 16 k summed in fp64).  A pair's
+ *   value is a bitwise function of its two images and (C, H, W) only -- not of i, j, n, the tile it falls into or
+ *   fmri_set_deterministic -- so truth_j == truth_i bitwise gives S[i][j] == S[i][i] bitwise.  No atomics.
+ *   cnt_m[i] = #{j != i : S_m[i][j] < S_m[i][i]} (NaN compares false); E_m = sum_i (cnt_m[i] / (n - 1))^(top - 1), the
+ *   power by repeated multiplication and the sum in index order, both fp64 (top = 1: n).
+ *   rng_state (device int64[2] of fmri_rng_normal, or NULL): distractor d[i][k], k < top - 1, is element
+ *   e = i (top - 1) + k of stream sid at the state's offset under the mapping of fmri_rng_u32 on [0, n - 2],
+ *   u = (w_e (n - 1)) >> 32, then d = u + (u >= i): uniform over the other images, with replacement, as random.choice
+ *   in the reference (the same distribution, not the host's draws).  hit_m[i] = for all k: S_m[i][i] > S_m[i][d[i][k]]
+ *   (top = 1: every image).  The offset is not moved.  distractors (int32 [n][top - 1], or NULL) receives d.
+ *   acc6 (device double[6]): hits_pcc, hits_ssim, E_pcc, E_ssim, images, batches -- cleared first (acc_mode 0) or added
+ *   to (1).  out8[0..3] = this batch's hits / n and E / n; out8[4..7] = acc6[0..3] / acc6[4], the score over the images
+ *   so far (tp / dataset_size).  With rng_state NULL the two hit entries of out8 and acc6 are NaN.
+ *   Five launches whatever n is (per-image statistics, Gram, pair SSIM blocked 16 pred x 8 truth per tile and channel,
+ *   rows, fold); no allocation, no memset, no host sync.  ws: fmri_nway_ws_bytes(n, H, W) bytes (< 0: bad geometry),
+ *   16-byte aligned.  Errors, before anything is launched: n < 2, top < 1, a NULL or misaligned required pointer or
+ *   acc_mode outside {0, 1}: FMRI_E_BADARG; H or W < 11, Cp != 8 or C > 4: FMRI_E_UNSUPPORTED; ws_bytes too small:
+ *   FMRI_E_WORKSPACE. */
+int64_t fmri_nway_ws_bytes(int n, int H, int W);
+int fmri_nway_scores(const void* pred16, const void* truth16, int n, int H, int W, int C, int Cp, int top,
+                     const int64_t* rng_state /* device int64[2] or NULL */, int sid,
+                     void* ws, int64_t ws_bytes,
+                     float* s_pcc, float* s_ssim,        /* device fp32 [n][n], written */
+                     int32_t* distractors,               /* device int32 [n][top-1] or NULL, written when given */
+                     float* out8, double* acc6, int acc_mode, void* stream);
+
 /* ---- layout casts ------------------------------------------------------------------------------- */
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream);
 int fmri_nhwc_to_nchw(const void* src, float* dst, int N, int C, int HW, int Cp, float scale, void* stream);

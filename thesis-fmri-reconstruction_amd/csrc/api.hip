@@ -148,6 +148,23 @@ int fmri_image_metrics(const void* pred16, const void* truth16, int N, int H, in
     return image_metrics_launch((const half_t*)pred16, (const half_t*)truth16, N, H, W, C, scale, shift, ws, ws_bytes,
                                 out7, acc4, acc_mode, S(stream));
 }
+/* ---- n-way identification of a batch in the engine's image layout (the evaluation pass, fmri_hip/evaluate.py) ---- */
+int64_t fmri_nway_ws_bytes(int n, int H, int W) { return nway_ws_bytes(n, H, W); }
+int fmri_nway_scores(const void* pred16, const void* truth16, int n, int H, int W, int C, int Cp, int top,
+                     const int64_t* rng_state, int sid, void* ws, int64_t ws_bytes, float* s_pcc, float* s_ssim,
+                     int32_t* distractors, float* out8, double* acc6, int acc_mode, void* stream) {
+    if (!pred16 || !truth16 || !ws || !s_pcc || !s_ssim || !out8 || !acc6 || n < 2 || top < 1 || H < 1 || W < 1 ||
+        C < 1 || C > 8 || sid < 0 || (acc_mode != 0 && acc_mode != 1) || ((uintptr_t)pred16 & 15) ||
+        ((uintptr_t)truth16 & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)rng_state & 7) || ((uintptr_t)s_pcc & 3) ||
+        ((uintptr_t)s_ssim & 3) || ((uintptr_t)distractors & 3) || ((uintptr_t)out8 & 3) || ((uintptr_t)acc6 & 7))
+        return FMRI_E_BADARG;
+    if (Cp != 8) return FMRI_E_UNSUPPORTED;            // one 16-byte load per pixel
+    if (H < 11 || W < 11) return FMRI_E_UNSUPPORTED;   // as fmri_ssim: the reference's window shrinks, its padding not
+    if (C > nway_cmax()) return FMRI_E_UNSUPPORTED;    // the workspace is sized without knowing C
+    if (n > 65535 * 8) return FMRI_E_UNSUPPORTED;      // y / z grid dimensions of the pair launches
+    return nway_scores_launch((const half_t*)pred16, (const half_t*)truth16, n, H, W, C, top, rng_state, sid, ws, ws_bytes,
+                              s_pcc, s_ssim, distractors, out8, acc6, acc_mode, S(stream));
+}
 
 int fmri_version(void) { return 100; }
 

@@ -315,5 +315,11 @@ int64_t image_metrics_ws_bytes(int N, int H, int W);
 int image_metrics_launch(const half_t* pred, const half_t* truth, int N, int H, int W, int C, const float* scale,
                          const float* shift, void* ws, int64_t ws_bytes, float* out7, double* acc4, int acc_mode,
                          hipStream_t st);
+// csrc/nway.hip
+int nway_cmax();
+int64_t nway_ws_bytes(int n, int H, int W);
+int nway_scores_launch(const half_t* pred, const half_t* truth, int n, int H, int W, int C, int top,
+                       const int64_t* rng_state, int sid, void* ws, int64_t ws_bytes, float* s_pcc, float* s_ssim,
+                       int32_t* distractors, float* out8, double* acc6, int acc_mode, hipStream_t st);
 
 }  // namespace fmri

@@ -16,40 +16,11 @@
 // offset, so a step recorded into a HIP graph draws fresh numbers at every replay.  A number depends on (seed, offset,
 // global row, column, stream id) only -- not on the launch shape, the rank or the vector / scalar store path.
 #include "kernels.h"
+#include "philox.h"
 
 namespace fmri {
 
 namespace {
-
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-struct u32x4 {
-    uint32_t w[4];
-};
-
-__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                               uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += PHILOX_W0;
-        k1 += PHILOX_W1;
-    }
-    return u32x4{{c0, c1, c2, c3}};
-}
-
-// Philox block `blk` of stream `sid` at the state's seed and offset
-__device__ __forceinline__ u32x4 rng_block(const int64_t* __restrict__ state, uint64_t blk, uint32_t sid) {
-    const uint64_t seed = (uint64_t)state[0];
-    const uint64_t ctr = (uint64_t)state[1] + blk;
-    return philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), sid, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
 
 // u = (k + 0.5) * 2^-24 with k = w >> 8 is no fp32 number for k >= 2^23 (25 significant bits), and near u = 1 the half
 // step it would be rounded by moves sqrt(-2 ln u) by far more than an ulp.  1 - u = ((2^24 - 1 - k) + 0.5) * 2^-24 IS one

@@ -24,6 +24,17 @@ Columns of a row: ``epoch`` (of the step's training feed, read on the device; on
 batch weighted equally: what ``evaluate()`` returns) and ``train_PCC / train_SSIM / train_MSE`` (the last
 ``train_batch()`` since the previous row, NaN without one).
 
+``identify=top`` adds n-way identification (the ``objective_assessment`` the scripts call beside ``evaluate()``,
+train/train_utils.py:752-816; csrc/nway.hip, include/fmri_hip.h fmri_nway_scores): every batch's reconstructions against
+the batch's ingested images -- always the normalised tensors, whatever ``denorm`` is -- with the ``top - 1`` distractors
+of every image drawn on the device.  Columns ``nway_PCC / nway_SSIM`` (hits over images: ``tp / dataset_size``, weighted
+by images, unlike ``mean_*``) and ``nway_exp_PCC / nway_exp_SSIM`` (the same score's expectation over the draws: no
+sampling noise).  The draws are uniform over the batch's other images with replacement, as the reference's
+``random.choice``, but not the host's draws.  They are made at the evaluator's generator offset on stream SID_DISTRACT
+before the batch's advance, which stays ``blocks(b * latent_dim)`` where the forward samples -- ``eps``, and with it every
+other column, has the same bits with and without ``identify`` -- and is ``blocks(b * (top - 1))`` where it does not and an
+``rng`` was given.  Without an ``rng`` the two sampled columns are NaN.
+
 A pass leaves training where it was: ``bn.eval_mode`` is set for the pass and restored, no running statistic and no
 ``num_batches_tracked`` moves, nothing the step owns is written or re-bound (latent range scratch, noise, batch buffers and
 the generator are the evaluator's own), and a step recorded with ``capture()`` before or after replays unchanged.  The pass
@@ -44,12 +55,13 @@ import torch
 from . import lib, ops
 from .feed import DeviceDataset
 from .ops import nhwc_to_images, pad8
-from .rng import SID_EPS, DeviceRng, blocks
+from .rng import SID_DISTRACT, SID_EPS, DeviceRng, blocks
 from .schedule import TrainLog
 
 _P = lib.ptr
 
 METRICS = ("PCC", "SSIM", "MSE")
+NWAY = ("nway_PCC", "nway_SSIM", "nway_exp_PCC", "nway_exp_SSIM")
 
 
 def batch_ranges(n: int, batch: int) -> List[Tuple[int, int]]:
@@ -65,12 +77,14 @@ class Evaluator:
     where the step takes fMRI).  ``rng``: the evaluator's OWN generator for ``eps`` (stream SID_EPS, advanced by the
     evaluator after every batch); needed only where the eval forward samples.  ``mean`` / ``std``: the ingest
     normalisation, as DeviceFeed.  ``denorm``: metrics on v * std + mean (``evaluate(norm=True)``, denormalize_image)
-    instead of the normalised images.  ``capacity``: rows of the ring.
+    instead of the normalised images.  ``capacity``: rows of the ring.  ``identify``: None, or the ``top`` of n-way
+    identification (above); every batch of a pass, the last included, then needs at least two images.
 
     With ``distributed=True`` steps every rank evaluates the whole set by itself: there is no collective in a pass."""
 
     def __init__(self, step, dataset: DeviceDataset, batch: int, rng: Optional[DeviceRng] = None,
-                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), denorm: bool = False, capacity: int = 1024):
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), denorm: bool = False, capacity: int = 1024,
+                 identify: Optional[int] = None):
         from .steps import CognitiveStep, Stage1Step
         from .wae_steps import WaeStep
         if isinstance(step, WaeStep):
@@ -101,6 +115,17 @@ class Evaluator:
         self.rng = rng if self.samples else None
         self.B = B = min(int(batch), N)
         self.ranges = batch_ranges(N, B)
+        if identify is not None:
+            if int(identify) != identify or identify < 1:
+                raise ValueError("Evaluator: identify must be an integer >= 1 (the `top` of objective_assessment)")
+            if self.ranges[-1][1] < 2:
+                raise ValueError(f"Evaluator: identify needs two images in every batch, the last batch of {N} images in "
+                                 f"batches of {B} holds one (the reference's random.choice([]) raises there too)")
+            if self.samples and identify - 1 > cfg.latent_dim:
+                raise ValueError(f"Evaluator: identify - 1 = {identify - 1} distractors per image exceed latent_dim = "
+                                 f"{cfg.latent_dim}, the generator's advance per image")
+        self.identify = None if identify is None else int(identify)
+        self._id_rng = rng if identify is not None else None
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         if denorm:
             self._scale, self._shift = (C.c_float * 3)(*self.std), (C.c_float * 3)(*self.mean)
@@ -133,6 +158,16 @@ class Evaluator:
         cols += [(f"valid_{m}", flat, last + k) for k, m in enumerate(METRICS)]
         cols += [(f"mean_{m}", flat, last + 3 + k) for k, m in enumerate(METRICS)]
         cols += [(f"train_{m}", self._train, k) for k, m in enumerate(METRICS)]
+        if self.identify is not None:
+            # persistent, as the metrics buffers; one out8 row per batch, the running scores of the last row are the pass's
+            self._id_bytes = lib.load().fmri_nway_ws_bytes(B, H, W)
+            self._id_ws = torch.empty(self._id_bytes, dtype=torch.uint8, device=dev)
+            self._id_sim = torch.zeros(2, B * B, dtype=torch.float32, device=dev)
+            self._id_draws = (torch.zeros(B * (self.identify - 1), dtype=torch.int32, device=dev)
+                              if self._id_rng is not None else None)
+            self._id_acc = torch.zeros(6, dtype=torch.float64, device=dev)
+            self._id_out = torch.zeros(len(self.ranges), 8, dtype=torch.float32, device=dev)
+            cols += [(name, self._id_out.view(-1), (len(self.ranges) - 1) * 8 + 4 + k) for k, name in enumerate(NWAY)]
         self.log = TrainLog(capacity)
         self.log.attach(dev, cols, ())
 
@@ -148,8 +183,18 @@ class Evaluator:
         lib.call("fmri_image_metrics", _P(pred16), _P(truth16), n, H, W, 3, cp, sc, sf, _P(self._ws), self._ws_bytes,
                  _P(out7), _P(acc), acc_mode)
 
+    # ---- n-way identification of one batch: five launches ----------------------------------------------------------------
+    def _identify(self, pred16: torch.Tensor, truth16: torch.Tensor, k: int):
+        """n-way identification of batch ``k`` of the pass: one fmri_nway_scores (five launches) into row k of the out8
+        rows, on top of the accumulator from the second batch on."""
+        b, H, W, cp = pred16.shape
+        g = self._id_rng
+        lib.call("fmri_nway_scores", _P(pred16), _P(truth16), b, H, W, 3, cp, self.identify,
+                 None if g is None else _P(g._state), SID_DISTRACT, _P(self._id_ws), self._id_bytes, _P(self._id_sim[0]),
+                 _P(self._id_sim[1]), _P(self._id_draws), _P(self._id_out[k]), _P(self._id_acc), 0 if k == 0 else 1)
+
     # ---- the eval-mode forward of one batch --------------------------------------------------------------------------
-    def _forward(self, r0: int, b: int):
+    def _forward(self, r0: int, b: int, advance: bool = True):
         ds, Z = self.ds, self.Z
         N, H, W, Cimg = ds.images.shape
         idx = self._idx[r0:r0 + b]
@@ -166,7 +211,8 @@ class Evaluator:
         if self.samples:
             eps = self._eps[:b]
             self.rng.normal(b, Z, SID_EPS, out=eps)
-            self.rng.advance(blocks(b * Z))
+            if advance:
+                self.rng.advance(blocks(b * Z))
             self._zst.zero_()
             ops.latent_ranged(head32, eps, b, Z, z16, self._zst[0:1], self._zst[1:2], sample=True)
             self.dec.forward(z16, 1, out=pred16, zscale=self._zst[1:2])
@@ -185,8 +231,13 @@ class Evaluator:
             bn.eval_mode = True
         try:
             for k, (r0, b) in enumerate(self.ranges):
-                pred16, x16 = self._forward(r0, b)
+                # with identify, the batch's advance waits for the distractor draws made at the same offset
+                pred16, x16 = self._forward(r0, b, advance=self.identify is None)
                 self._metrics(pred16, x16, self._bm[k], self._acc, 0 if k == 0 else 1)
+                if self.identify is not None:
+                    self._identify(pred16, x16, k)
+                    if self._id_rng is not None:
+                        self._id_rng.advance(blocks(b * (self.Z if self.samples else self.identify - 1)))
         finally:
             for bn, w in zip(bns, was):
                 bn.eval_mode = w
@@ -220,6 +271,35 @@ class Evaluator:
     def batch_metrics(self) -> torch.Tensor:
         """Device fp32 [n_batches, 3]: PCC, SSIM, MSE of every batch of the last pass (a view: the next pass rewrites it)."""
         return self._bm[:, :3]
+
+    def _identifying(self, what: str):
+        if self.identify is None:
+            raise RuntimeError(f"Evaluator.{what}(): built without identify")
+
+    def identification(self) -> torch.Tensor:
+        """Device float64 [6] of the last pass: hits (PCC, SSIM), expected hits (PCC, SSIM), images, batches (a view)."""
+        self._identifying("identification")
+        return self._id_acc
+
+    def batch_identification(self) -> torch.Tensor:
+        """Device fp32 [n_batches, 8] of the last pass: per batch hits / n and expectation / n (PCC, SSIM each), then the
+        same four over the images up to and including that batch (a view)."""
+        self._identifying("batch_identification")
+        return self._id_out
+
+    def last_similarity(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(S_pcc, S_ssim), fp32 [rows, rows] views: reconstruction i against image j of the last batch of the last pass."""
+        self._identifying("last_similarity")
+        b = self._last_rows
+        return self._id_sim[0, :b * b].view(b, b), self._id_sim[1, :b * b].view(b, b)
+
+    def last_distractors(self) -> Optional[torch.Tensor]:
+        """int32 [rows, identify - 1] view of the last batch's draws; None without an rng."""
+        self._identifying("last_distractors")
+        if self._id_draws is None:
+            return None
+        k = self.identify - 1
+        return self._id_draws[:self._last_rows * k].view(self._last_rows, k)
 
     def last_output(self) -> torch.Tensor:
         """fp32 NCHW reconstructions of the last batch of the last pass."""

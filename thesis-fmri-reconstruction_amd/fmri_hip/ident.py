@@ -8,6 +8,10 @@ pairwise similarities computed by csrc/ident.hip through the C ABI (include/fmri
     n_way_expected(pred, truth, top)   float64 [2]: the score's exact expectation over the distractor draws
     objective_assessment(model, dataloader, dataset=None, mode=None, top=5)
                                        the reference's function: same signature, same draws, same CPU result
+    nway_scores16(pred16, truth16, top, rng=None, ...)
+                                       one batch in the engine's fp16 [n, H, W, 8] layout, everything on the device
+                                       (fmri_nway_scores, csrc/nway.hip): both matrices, the distractors drawn from a
+                                       DeviceRng, the hits, the expectation and a running accumulator
 
 Images are GPU tensors [N, C, H, W]: a CPU tensor is a RuntimeError, there is no eager fallback.  A pair's value is a
 bitwise function of the two images (include/fmri_hip.h), so the strict ``>`` of the reference counts as on the host,
@@ -29,6 +33,7 @@ import torch
 
 from . import lib
 from .ops import require_gpu
+from .rng import SID_DISTRACT
 
 _P = lib.ptr
 _PAIR_CHUNK = 1 << 16           # pairs per fmri_ssim_pairs launch of ssim_matrix
@@ -173,6 +178,38 @@ def n_way_expected(pred: torch.Tensor, truth: torch.Tensor, top: int) -> torch.T
     k = int(top) - 1
     res = [float(sum(Fraction(c, N - 1) ** k for c in col) / N) for col in counts]
     return torch.tensor(res, dtype=torch.float64, device=a.device)
+
+
+def nway_scores16(pred16: torch.Tensor, truth16: torch.Tensor, top: int, rng=None, sid: int = SID_DISTRACT, acc=None,
+                  acc_mode: int = 0, C: int = 3):
+    """One fmri_nway_scores on a batch in the engine's image layout (fp16 [n, H, W, 8], channels 0..C-1 real); enqueues
+    only.  ``rng``: a DeviceRng -- the n (top - 1) distractors are drawn at its current offset on stream ``sid`` (the
+    offset is not moved); None: no draws, the sampled scores are NaN.  ``acc``: a device float64 [6] to clear and fill
+    (``acc_mode`` 0) or add to (1); None: a fresh one.
+
+    Returns ``(S_pcc, S_ssim, distractors, out8, acc6)``: fp32 [n, n] twice, int32 [n, top - 1] (None without ``rng``),
+    fp32 [8] = this batch's hits / n (PCC, SSIM) and expectation / n (PCC, SSIM), then the same four over all images
+    accumulated so far, and float64 [6] = hits (PCC, SSIM), expectation (PCC, SSIM), images, batches."""
+    require_gpu(pred16)
+    if (pred16.dim() != 4 or pred16.shape != truth16.shape or pred16.dtype != torch.float16
+            or truth16.dtype != torch.float16 or truth16.device != pred16.device
+            or not (pred16.is_contiguous() and truth16.is_contiguous())):
+        raise ValueError("nway_scores16: pred16 and truth16 must be contiguous fp16 [n, H, W, Cp] of one shape on one "
+                         "device")
+    n, H, W, cp = pred16.shape
+    dev = pred16.device
+    nb = lib.load().fmri_nway_ws_bytes(n, H, W)
+    ws = _workspace(nb, "nway_scores16", dev)
+    S_pcc = torch.empty(n, n, dtype=torch.float32, device=dev)
+    S_ssim = torch.empty(n, n, dtype=torch.float32, device=dev)
+    d = torch.empty(n, max(int(top) - 1, 0), dtype=torch.int32, device=dev) if rng is not None else None
+    out8 = torch.empty(8, dtype=torch.float32, device=dev)
+    if acc is None:
+        acc = torch.zeros(6, dtype=torch.float64, device=dev)
+    lib.call("fmri_nway_scores", _P(pred16), _P(truth16), n, H, W, C, cp, int(top),
+             None if rng is None else _P(rng._state), int(sid), _P(ws), nb, _P(S_pcc), _P(S_ssim), _P(d), _P(out8),
+             _P(acc), int(acc_mode))
+    return S_pcc, S_ssim, d, out8, acc
 
 
 def objective_assessment(model, dataloader, dataset=None, mode=None, top=5):

@@ -24,6 +24,7 @@ SID_EPS_TEACHER = 2    # reparameterisation noise of the Stage-II teacher
 SID_ZFAKE = 3          # WAE prior sample (before the factor 0.5)
 SID_FLIP = 8           # per-image horizontal flip
 SID_SHIFT = 9          # per-image (rows, cols) shift
+SID_DISTRACT = 10      # distractors of n-way identification (fmri_nway_scores)
 SID_PERM = 16          # the epoch sampler's round function (fmri_sampler_indices; a counter layout of its own)
 
 _I64 = (1 << 64) - 1
