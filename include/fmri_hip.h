@@ -294,6 +294,51 @@ int fmri_nway_scores(const void* pred16, const void* truth16, int n, int H, int 
                      int32_t* distractors,               /* device int32 [n][top-1] or NULL, written when given */
                      float* out8, double* acc6, int acc_mode, void* stream);
 
+/* ---- uint8 image egress of a batch in the engine's image layout (the pictures the scripts write) --------------
+ * fmri_images_u8: src16 fp16 [n][H][W][Cp], 16-byte aligned, channels 0..C-1 real (lanes C..Cp-1 may hold anything:
+ *   they reach neither the range nor the output) -> normalised uint8 pixels, HWC.
+ *   Arithmetic: torchvision 0.5.0's norm_ip / save_image as torch runs them on the CPU, every operation a separately
+ *   rounded fp32 operation: lo, hi = min, max of the real elements; d = (float)((double)hi - (double)lo + 1e-5);
+ *   y = (x + (-lo)) / d, a correctly rounded division; b = (uint8)clamp(y * 255 + 0.5, 0, 255), truncating.
+ *   mode 0: save_image(F.interpolate(im, size=R), normalize=True) per image (evaluate(save=True),
+ *     train/train_utils.py:728-735): one range per image; out [n][R][R][3] ([n][H][W][3] with R = 0), source index
+ *     min((int)floorf(dst * ((float)H / R)), H - 1) (F.interpolate's default nearest mode).  0 < R < max(H, W):
+ *     FMRI_E_UNSUPPORTED -- a smaller output drops pixels, and the scripts' range is that of the resized image.
+ *   mode 1: make_grid(x, nrow, padding, normalize=True): one range over all n images; xmaps = min(nrow, n),
+ *     ymaps = ceil(n / xmaps), out [ymaps (H + padding) + padding][xmaps (W + padding) + padding][3], image k at row
+ *     (k / xmaps)(H + padding) + padding, column (k % xmaps)(W + padding) + padding, padding and empty cells 0;
+ *     n == 1: the image alone, H x W.
+ *   out: 4-byte aligned, with room for its byte count (fmri_images_u8_out_bytes; < 0: bad geometry) rounded up to a
+ *   multiple of 4: the output is written as dwords, the up to three bytes behind its end as 0.
+ *   slot_dev (device int64, or NULL: out as is): the output goes to out + (slot_dev[0] mod slot_mod) * slot_stride,
+ *   the counter read ON THE DEVICE by the launch (slot_stride a multiple of 4) -- a ring whose slot follows a device
+ *   counter such as fmri_trainlog_append's, in enqueue order.  present_dev (may be NULL): present_dev[slot] = 1
+ *   (slot 0 without slot_dev).
+ *   Two launches: one block per image writes its [lo, hi] to ws (fmri_images_u8_ws_bytes(n) bytes, 4-byte aligned;
+ *   < 0: n < 1), one 16-byte load per pixel; the second is output-stationary, every lane decodes four consecutive
+ *   bytes and issues one dword store, and in mode 1 every block folds the n ranges itself.  No atomics, no memset, no
+ *   allocation, no host sync; the bytes are a function of the input and the geometry only (fmri_set_deterministic on
+ *   or off).  A non-finite pixel gives unspecified bytes and moves no address.
+ *   Errors, before anything is launched: Cp != 8 or C != 3: FMRI_E_UNSUPPORTED; a NULL or misaligned pointer, bad
+ *   geometry, mode outside {0, 1}, slot_mod < 1 or a slot_stride that is no multiple of 4 with slot_dev:
+ *   FMRI_E_BADARG; ws_bytes too small: FMRI_E_WORKSPACE; an output of 2^31 bytes or more: FMRI_E_UNSUPPORTED.
+ * fmri_images_u8_open: one thread.  Unless opened_dev[0] == slot_dev[0] + 1 already: clears
+ *   present_dev[k * present_stride + slot] for k < kinds, slot = slot_dev[0] mod slot_mod, and sets opened_dev[0] =
+ *   slot_dev[0] + 1 -- the first call of a pass opens the slot, later calls of the same pass do nothing.  A ring's
+ *   flags are cleared by this launch, not by a host memset that a replay would not repeat. */
+int64_t fmri_images_u8_ws_bytes(int n);
+int64_t fmri_images_u8_out_bytes(int n, int H, int W, int mode, int R, int nrow, int padding);
+int fmri_images_u8(const void* src16, int n, int H, int W, int C, int Cp,
+                   int mode,              /* 0: one range per image (save_image of one image); 1: one range over all n, grid */
+                   int R,                 /* mode 0: output side, nearest-neighbour resize H x W -> R x R; 0 = no resize */
+                   int nrow, int padding, /* mode 1 */
+                   void* ws, int64_t ws_bytes, uint8_t* out,
+                   const int64_t* slot_dev, int64_t slot_stride, int slot_mod,   /* ring addressing; NULL: out as is */
+                   uint8_t* present_dev,  /* may be NULL: set to 1 at the addressed slot */
+                   void* stream);
+int fmri_images_u8_open(const int64_t* slot_dev, int slot_mod, int64_t* opened_dev /* device int64 */,
+                        uint8_t* present_dev, int64_t present_stride, int kinds, void* stream);
+
 /* ---- layout casts ------------------------------------------------------------------------------- */
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream);
 int fmri_nhwc_to_nchw(const void* src, float* dst, int N, int C, int HW, int Cp, float scale, void* stream);

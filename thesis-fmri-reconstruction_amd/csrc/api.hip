@@ -165,6 +165,34 @@ int fmri_nway_scores(const void* pred16, const void* truth16, int n, int H, int 
     return nway_scores_launch((const half_t*)pred16, (const half_t*)truth16, n, H, W, C, top, rng_state, sid, ws, ws_bytes,
                               s_pcc, s_ssim, distractors, out8, acc6, acc_mode, S(stream));
 }
+/* ---- uint8 image egress of a batch in the engine's image layout (fmri_hip/egress.py) ---- */
+int64_t fmri_images_u8_ws_bytes(int n) { return images_u8_ws_bytes(n); }
+int64_t fmri_images_u8_out_bytes(int n, int H, int W, int mode, int R, int nrow, int padding) {
+    if (n < 1 || H < 1 || W < 1 || H > 32768 || W > 32768 || (mode != 0 && mode != 1) || R > 32768 ||
+        (mode == 0 && R < 0) || (mode == 1 && (nrow < 1 || padding < 0 || padding > 32768)))
+        return -1;
+    return images_u8_out_bytes(n, H, W, mode, R, nrow, padding);
+}
+int fmri_images_u8(const void* src16, int n, int H, int W, int C, int Cp, int mode, int R, int nrow, int padding,
+                   void* ws, int64_t ws_bytes, uint8_t* out, const int64_t* slot_dev, int64_t slot_stride, int slot_mod,
+                   uint8_t* present_dev, void* stream) {
+    if (Cp != 8 || C != 3) return FMRI_E_UNSUPPORTED;  // one 16-byte load per pixel, three bytes per output pixel
+    if (!src16 || !ws || !out || fmri_images_u8_out_bytes(n, H, W, mode, R, nrow, padding) < 0 ||
+        ((uintptr_t)src16 & 15) || ((uintptr_t)ws & 3) || ((uintptr_t)out & 3) || ((uintptr_t)slot_dev & 7) ||
+        (slot_dev && (slot_mod < 1 || slot_stride < 0 || (slot_stride & 3))))
+        return FMRI_E_BADARG;
+    // a smaller output would drop source pixels from the image, the scripts' range is that of the RESIZED image
+    if (mode == 0 && R != 0 && (R < H || R < W)) return FMRI_E_UNSUPPORTED;
+    return images_u8_launch((const half_t*)src16, n, H, W, mode, R, nrow, padding, ws, ws_bytes, out, slot_dev, slot_stride,
+                            slot_mod, present_dev, S(stream));
+}
+int fmri_images_u8_open(const int64_t* slot_dev, int slot_mod, int64_t* opened_dev, uint8_t* present_dev,
+                        int64_t present_stride, int kinds, void* stream) {
+    if (!slot_dev || !opened_dev || !present_dev || slot_mod < 1 || present_stride < slot_mod || kinds < 1 ||
+        ((uintptr_t)slot_dev & 7) || ((uintptr_t)opened_dev & 7))
+        return FMRI_E_BADARG;
+    return images_u8_open_launch(slot_dev, slot_mod, opened_dev, present_dev, present_stride, kinds, S(stream));
+}
 
 int fmri_version(void) { return 100; }
 

@@ -321,5 +321,13 @@ int64_t nway_ws_bytes(int n, int H, int W);
 int nway_scores_launch(const half_t* pred, const half_t* truth, int n, int H, int W, int C, int top,
                        const int64_t* rng_state, int sid, void* ws, int64_t ws_bytes, float* s_pcc, float* s_ssim,
                        int32_t* distractors, float* out8, double* acc6, int acc_mode, hipStream_t st);
+// csrc/egress.hip
+int64_t images_u8_ws_bytes(int n);
+int64_t images_u8_out_bytes(int n, int H, int W, int mode, int R, int nrow, int padding);
+int images_u8_launch(const half_t* src, int n, int H, int W, int mode, int R, int nrow, int padding, void* ws,
+                     int64_t ws_bytes, uint8_t* out, const int64_t* slot_dev, int64_t slot_stride, int slot_mod,
+                     uint8_t* present_dev, hipStream_t st);
+int images_u8_open_launch(const int64_t* slot_dev, int slot_mod, int64_t* opened_dev, uint8_t* present_dev,
+                          int64_t present_stride, int kinds, hipStream_t st);
 
 }  // namespace fmri

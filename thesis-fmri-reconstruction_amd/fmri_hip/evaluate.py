@@ -35,6 +35,12 @@ before the batch's advance, which stays ``blocks(b * latent_dim)`` where the for
 other column, has the same bits with and without ``identify`` -- and is ``blocks(b * (top - 1))`` where it does not and an
 ``rng`` was given.  Without an ``rng`` the two sampled columns are NaN.
 
+``grids=`` / ``dump=`` / ``generate=`` add the pictures of the scripts' epoch (fmri_hip/egress.py, csrc/egress.hip): the
+``make_grid`` of the training batch, its reconstruction, the validation output and ``model(None, g)`` into a device ring
+whose slot follows this evaluator's pass counter, and ``evaluate(save=True)``'s per-image uint8 dumps.  The draw of
+``generate`` is stream SID_GENERATE at the generator's offset at the end of the pass and moves nothing: every column
+keeps its bits.
+
 A pass leaves training where it was: ``bn.eval_mode`` is set for the pass and restored, no running statistic and no
 ``num_batches_tracked`` moves, nothing the step owns is written or re-bound (latent range scratch, noise, batch buffers and
 the generator are the evaluator's own), and a step recorded with ``capture()`` before or after replays unchanged.  The pass
@@ -55,7 +61,7 @@ import torch
 from . import lib, ops
 from .feed import DeviceDataset
 from .ops import nhwc_to_images, pad8
-from .rng import SID_DISTRACT, SID_EPS, DeviceRng, blocks
+from .rng import SID_DISTRACT, SID_EPS, SID_GENERATE, DeviceRng, blocks
 from .schedule import TrainLog
 
 _P = lib.ptr
@@ -79,12 +85,18 @@ class Evaluator:
     normalisation, as DeviceFeed.  ``denorm``: metrics on v * std + mean (``evaluate(norm=True)``, denormalize_image)
     instead of the normalised images.  ``capacity``: rows of the ring.  ``identify``: None, or the ``top`` of n-way
     identification (above); every batch of a pass, the last included, then needs at least two images.
+    ``grids`` (egress.GridSink): the scripts' epoch-end image grids as uint8 pixels -- ``train_batch()`` writes the first
+    ``count`` rows of the training truth and of the train-mode ``x_tilde``, ``run()`` those of the last batch's images and
+    reconstructions and, with ``generate=g > 0`` (needs an ``rng``), of an eval-mode decoder forward of g rows of N(0, I)
+    (``model(None, g)``).  ``dump`` (egress.ImageDump): ``run()`` also writes every reconstruction and every ingested
+    image of the pass, normalised per image and resized, as ``evaluate(save=True)`` writes its files.  Without the three
+    a pass enqueues exactly what it did before them.
 
     With ``distributed=True`` steps every rank evaluates the whole set by itself: there is no collective in a pass."""
 
     def __init__(self, step, dataset: DeviceDataset, batch: int, rng: Optional[DeviceRng] = None,
                  mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), denorm: bool = False, capacity: int = 1024,
-                 identify: Optional[int] = None):
+                 identify: Optional[int] = None, grids=None, dump=None, generate: int = 0):
         from .steps import CognitiveStep, Stage1Step
         from .wae_steps import WaeStep
         if isinstance(step, WaeStep):
@@ -170,6 +182,25 @@ class Evaluator:
             cols += [(name, self._id_out.view(-1), (len(self.ranges) - 1) * 8 + 4 + k) for k, name in enumerate(NWAY)]
         self.log = TrainLog(capacity)
         self.log.attach(dev, cols, ())
+        # the pictures (fmri_hip/egress.py): opt-in, without them a pass enqueues what it did before
+        if int(generate) != generate or generate < 0:
+            raise ValueError("Evaluator: generate must be an integer >= 0")
+        self.grids, self.dump, self.generate = grids, dump, int(generate)
+        if self.generate:
+            if rng is None:
+                raise ValueError("Evaluator: generate draws the decoder's input on the device -- pass "
+                                 "rng=DeviceRng(seed, device)")
+            if grids is None:
+                raise ValueError("Evaluator: generate writes the `random` grid -- pass grids=GridSink(...)")
+            self._gen_rng = rng
+            self._gen_scale = 0.5 if isinstance(step, WaeStep) and step.stage == 1 else 1.0      # as SID_ZFAKE
+            self._gen32 = torch.empty(self.generate, Z, dtype=torch.float32, device=dev)
+            self._genz16 = torch.zeros(self.generate, pad8(Z), dtype=torch.float16, device=dev)
+            self._gen16 = torch.empty(self.generate, H, W, 8, dtype=torch.float16, device=dev)
+        if grids is not None:
+            grids.attach(dev, H, W, self.log.counter)
+        if dump is not None:
+            dump.attach(dev, N, H, W, B)
 
     # ---- the metrics of one batch: two launches ----------------------------------------------------------------------
     def _metrics(self, pred16: torch.Tensor, truth16: torch.Tensor, out7: torch.Tensor, acc, acc_mode: int):
@@ -222,6 +253,16 @@ class Evaluator:
         self._last_rows = b
         return pred16, x16
 
+    def _generate(self):
+        """The `random` grid: an eval-mode decoder forward of ``generate`` rows of N(0, I) (Stage-I WAE: times 0.5), drawn
+        on stream SID_GENERATE at the generator's offset at the end of the pass.  The offset is not advanced: ``eps``, the
+        distractor draws and with them every column have the bits of a pass without ``generate``."""
+        g, Z = self.generate, self.Z
+        self._gen_rng.normal(g, Z, SID_GENERATE, scale=self._gen_scale, out=self._gen32)
+        lib.call("fmri_rows_f32_to_f16", _P(self._gen32), _P(self._genz16), g, Z, self._genz16.shape[1], 1.0)
+        self.dec.forward(self._genz16, 1, out=self._gen16)
+        self.grids.write("random", self._gen16)
+
     def run(self):
         """One pass over the validation set in eval mode and one row in the ring; enqueues only."""
         ops.require_gpu(self.ds.images)
@@ -238,6 +279,14 @@ class Evaluator:
                     self._identify(pred16, x16, k)
                     if self._id_rng is not None:
                         self._id_rng.advance(blocks(b * (self.Z if self.samples else self.identify - 1)))
+                if self.dump is not None:
+                    self.dump.write(0, r0, pred16)
+                    self.dump.write(1, r0, x16)
+                if self.grids is not None and k == len(self.ranges) - 1:
+                    self.grids.write("valid_truth", x16)
+                    self.grids.write("valid_output", pred16)
+            if self.generate:
+                self._generate()
         finally:
             for bn, w in zip(bns, was):
                 bn.eval_mode = w
@@ -258,6 +307,9 @@ class Evaluator:
             B, d = fw["B"], fw["disc_in"]
             pred16, truth16 = d[B:2 * B], d[:B]
         self._metrics(pred16, truth16, self._train, None, 0)
+        if self.grids is not None:
+            self.grids.write("train_truth", truth16)
+            self.grids.write("train_output", pred16)
 
     # ---- reading back ---------------------------------------------------------------------------------------------------
     def history(self) -> Dict[str, np.ndarray]:

@@ -42,6 +42,8 @@ _SIGS = {
     "fmri_ssim_pairs": [_p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _l, _p],
     "fmri_image_metrics": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p, _i, _p],
     "fmri_nway_scores": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _p],
+    "fmri_images_u8": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _l, _i, _p, _p],
+    "fmri_images_u8_open": [_p, _i, _p, _p, _l, _i, _p],
     "fmri_unpack_grad": [_p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _l, _p],
     "fmri_igemm": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p],
     "fmri_igemm_ep": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _l, _p, _p,
@@ -159,7 +161,8 @@ EP_AFFINE_APPLIED = 0x20000000
 EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_test_fastdiv", "fmri_bn_ws_floats",
                              "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
                              "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
-                             "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes",
+                             "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes", "fmri_images_u8_ws_bytes",
+                             "fmri_images_u8_out_bytes",
                              "fmri_tensor_stats_ws_bytes"])
 
 _lib = None
@@ -202,6 +205,10 @@ def load():
     lib.fmri_image_metrics_ws_bytes.argtypes = [_i, _i, _i]
     lib.fmri_nway_ws_bytes.restype = _l
     lib.fmri_nway_ws_bytes.argtypes = [_i, _i, _i]
+    lib.fmri_images_u8_ws_bytes.restype = _l
+    lib.fmri_images_u8_ws_bytes.argtypes = [_i]
+    lib.fmri_images_u8_out_bytes.restype = _l
+    lib.fmri_images_u8_out_bytes.argtypes = [_i, _i, _i, _i, _i, _i, _i]
     lib.fmri_tensor_stats_ws_bytes.restype = _i
     lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
     _lib = lib

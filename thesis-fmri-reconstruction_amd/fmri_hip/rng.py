@@ -25,6 +25,7 @@ SID_ZFAKE = 3          # WAE prior sample (before the factor 0.5)
 SID_FLIP = 8           # per-image horizontal flip
 SID_SHIFT = 9          # per-image (rows, cols) shift
 SID_DISTRACT = 10      # distractors of n-way identification (fmri_nway_scores)
+SID_GENERATE = 11      # decoder input of the evaluator's `random` grid (fmri_hip/evaluate.py generate=)
 SID_PERM = 16          # the epoch sampler's round function (fmri_sampler_indices; a counter layout of its own)
 
 _I64 = (1 << 64) - 1
