@@ -514,15 +514,15 @@ def test_gated_weight_gradient_launch(case):
     was = ops._DET["on"]
     ops.set_deterministic(True)           # slab outputs (plain stores): two launches give the same bits
     try:
-        ref, _ = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad)
-        on, _ = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad, gate=flag)
-        hold = {}
+        ref = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad).buf
+        on = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad, gate=flag).buf
+        hold = ops.GradHold()
         ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad, hold=hold)          # allocates the persistent buffer
-        buf = [v for kk, v in hold.items() if kk != "busy"][0]
+        buf = list(hold.bufs.values())[0]
         buf.fill_(7.0)
-        hold["busy"] = False
+        hold.busy = False
         flag.zero_()
-        off, _ = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad, hold=hold, gate=flag)
+        off = ops.run_wgrad(P, Q, N, Yc, Yc, A, Hq, Hq, Bc, k, s, pad, hold=hold, gate=flag).buf
         torch.cuda.synchronize()
     finally:
         ops.set_deterministic(was)

@@ -123,6 +123,34 @@ def test_fused_step_equals_separate_calls(deterministic):
     _assert_same_bits(a.state_dict(), b.state_dict(), "fused vs separate")
 
 
+def test_dcgan_step_on_two_streams_equals_one_stream(deterministic):
+    """Mode 'dcgan' trains no encoder, so its backward pass ends with the decoder's: the weight gradients still running
+    on the side stream have to be joined there, before the updates read them.  Three steps with the side stream against
+    three steps on one stream: the same bits."""
+    from oracle import vaegan_oracle as O
+    from fmri_hip import ops
+    from fmri_hip.params import ArchConfig
+    from fmri_hip.steps import Stage1Step
+    data = O.synth_batch(8, O.ArchCfg.px64(), seed=1234, steps=1)
+    args = (data["x"].to(DEV), data["noise"][0, 0].to(DEV), data["noise"][0, 1].to(DEV))
+    a, b = (Stage1Step(ArchConfig.px64(), DEV, mode="dcgan") for _ in range(2))
+    a.load_recipe(0, True)
+    b.load_state_dict(a.state_dict())
+    side_was = ops._SIDE["on"]
+    try:
+        for st, side in ((a, True), (b, False)):
+            ops._SIDE["on"] = side
+            for _ in range(3):
+                st.step(*args)
+            _finish()
+    finally:
+        ops._SIDE["on"] = side_was
+    _assert_same_logs(a.logs(), b.logs(), "dcgan, two streams vs one")
+    _assert_same_bits(a.state_dict(), b.state_dict(), "dcgan, two streams vs one")
+    for n in ("opt_dec", "opt_dis"):
+        assert torch.equal(getattr(a, n).s1, getattr(b, n).s1), f"{n}: RMSprop state differs"
+
+
 @pytest.mark.parametrize("B", [8, 256])
 def test_one_launch_update_equals_separate_launches(deterministic, B):
     """fmri_apply_batch (``Stage1Step.step``: weight gradients stay in their GEMM layout until ONE launch per sub-network
@@ -470,6 +498,7 @@ def test_one_launch_update_in_the_default_reduction_mode():
     After every ``step()`` each such buffer is zero again in ALL its columns (the narrow kernel keeps a bias gradient in a
     spare column behind the taps); the first step agrees with forward / gate / backward / apply to the run-to-run spread
     of the atomics."""
+    from fmri_hip import ops
     B = 256
     a, b, args, _ = _stage1_pair(B)
     for it in range(3):
@@ -489,11 +518,11 @@ def test_one_launch_update_in_the_default_reduction_mode():
         for layer in vars(net).values():
             for lay in (layer if isinstance(layer, (list, tuple)) else [layer]):
                 for obj in [lay] + [v for v in vars(lay).values()] if hasattr(lay, "__dict__") else []:
-                    hold = getattr(obj, "_ghold", None)
-                    if not isinstance(hold, dict):
+                    hold = getattr(obj, "ghold", None)
+                    if not isinstance(hold, ops.GradHold):
                         continue
-                    for key, buf in hold.items():
-                        if key != "busy" and getattr(buf, "_fmri_clear", False):
+                    for (_, zeroed), buf in hold.bufs.items():
+                        if zeroed:                      # a buffer the kernel adds into
                             held += 1
                             assert float(buf.abs().max()) == 0.0, f"{type(obj).__name__}: accumulation buffer not cleared"
     assert held >= 3, f"only {held} accumulation buffers found: the walk over the layers missed them"

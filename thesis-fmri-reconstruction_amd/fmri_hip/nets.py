@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from typing import List, Optional
 
+import ctypes
 import os
 
 import torch
@@ -116,7 +117,7 @@ def refresh_net(net):
     repack_group(net.group)
     for bn in net.all_bns():
         bn._params()
-        if getattr(bn, "_lazy", False):
+        if bn._lazy:
             bn._running_in()             # reloads only after an outside write of the buffers (load_state_dict)
     heads = getattr(net, "heads", None)
     if heads is not None:
@@ -494,10 +495,12 @@ class DiscriminatorNet(_JoinedBackward):
 
     def _backward(self, ctx, dlogit16: Optional[torch.Tensor], scale_a: float, dfeat16: Optional[torch.Tensor],
                  scale_b: float, train: bool, img_rows: Optional[slice], img_streams=(True, True),
-                 train_b: bool = False):
+                 train_b: bool = False, stack: Optional[torch.Tensor] = None, zero_tail: int = 0):
         """Two cotangent streams through one saved forward:
              A: d(sum bce)/d logit  (dlogit16 [3B,8], scale_a) -- accumulates discriminator grads if ``train``
              B: d(sum mse)/d raw conv-3 features (dfeat16 [3B,h,w,c], scale_b) -- data gradient only
+           ``stack`` [6B,h,w,c]: the buffer ``dfeat16`` is the second half of; ``zero_tail``: that many last rows of
+           ``dfeat16`` are exact zeros (both from steps._start_cotangents).
            Returns (dimg_A, dimg_B): cotangents w.r.t. input images ``img_rows`` (None if not requested)."""
         n3 = ctx["x"].shape[0]
         streams = []
@@ -519,7 +522,8 @@ class DiscriminatorNet(_JoinedBackward):
             d3 = dflat.reshape(ctx["acts"][3].shape)
             # caller-provided stack [A rows | B rows] with B already in place (steps._start_cotangents): A goes into its
             # first half and the two-stream batch needs no concatenation copy
-            stack = getattr(dfeat16, "_fmri_stack", None) if dfeat16 is not None else None
+            if dfeat16 is None:
+                stack = None
             if stack is not None and stack.shape[0] != 2 * n3:
                 stack = None
             draw3, _ = self.bns[2].backward(ctx["raws"][2], d3, ctx["svs"][2], True, scale_a if train else None,
@@ -549,7 +553,7 @@ class DiscriminatorNet(_JoinedBackward):
                 # the data gradient's epilogue masks with block li-1's ReLU and reduces its BatchNorm backward sums, one
                 # statistics group per cotangent stream (all read the same saved forward tensor)
                 epi = _bwd_epi(bn=self.bns[li - 1], x=ctx["raws"][li - 1], groups=[(0, ctx["svs"][li - 1])] * S)
-                ztail = getattr(dfeat16, "_fmri_zero_tail", 0) if (li == 2 and dfeat16 is not None and S > 1) else 0
+                ztail = zero_tail if (li == 2 and dfeat16 is not None and S > 1) else 0
                 if ztail and epi is None and d.shape[0] == S * n3:
                     # stream B enters at conv3's raw output with exact zeros on the sampled images' rows -- the last rows
                     # of the stack: conv3's data gradient (per image) skips them, its result there is zero
@@ -648,7 +652,6 @@ class WaeDiscriminatorNet(_JoinedBackward):
 
     @staticmethod
     def _ptrs(tensors):
-        import ctypes
         arr = (ctypes.c_void_p * len(tensors))()
         for i, t in enumerate(tensors):
             arr[i] = None if t is None else t.data_ptr()
@@ -656,7 +659,6 @@ class WaeDiscriminatorNet(_JoinedBackward):
 
     def forward(self, z16: torch.Tensor):
         if self._fused_ok(z16):
-            import ctypes
             M, Zp = z16.shape
             dev = z16.device
             ws = [l.pw_f.get() for l in self.layers]
@@ -696,7 +698,6 @@ class WaeDiscriminatorNet(_JoinedBackward):
     def _backward_fused(self, ctx, dlogit16, scale, train: bool, need_dz: bool):
         """One launch for the data path (cotangents of the four hidden pre-activations, bias gradients, dz); the five
         weight gradients -- reductions over all rows -- are fmri_wgrad launches on the side stream."""
-        import ctypes
         hs = ctx["hs"]
         z16 = hs[0]
         M, Zp = z16.shape

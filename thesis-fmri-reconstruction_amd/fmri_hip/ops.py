@@ -9,7 +9,7 @@ they are unpacked into the fp32 ``.grad`` buffers.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import ctypes
 import os
@@ -96,8 +96,10 @@ class PackedWeight:
         # zero once: the pack kernels' fast paths only rewrite the valid region, padding stays zero
         self.buf = torch.zeros(total, dtype=torch.float16, device=master.device)
         self.version = -1
-        if not hasattr(group, "packed"):
-            group.packed = []
+        # another PackedWeight this one is made from by fmri_transpose_f16_batch (set by the layers, read by _repack_group)
+        self.transpose_of: Optional[PackedWeight] = None   # a dense layer's second orientation
+        self.taps_of: Optional[PackedWeight] = None         # the parity-class blocks of a stride-2 (transposed) convolution
+        grad_queue(group)                # (a stand-in group gets its queue and its ``packed`` list here)
         group.packed.append(self)
 
     def _items(self):
@@ -119,7 +121,7 @@ def _repack_group(group, skip=()):
     (fmri_pack_weight_batch, device-resident table built once) + the few weights that need another pack path.
     ``skip``: PackedWeights that are already current (written by fmri_apply_batch together with the update)."""
     packed = group.packed
-    tabs = group.__dict__.setdefault("_pack_tables", {})
+    tabs = grad_queue(group).pack_tables
     key = (len(packed),) + tuple(sorted(id(pw) for pw in skip))
     tab = tabs.get(key)
     if tab is None:
@@ -131,13 +133,13 @@ def _repack_group(group, skip=()):
         for pw in packed:
             if id(pw) in skipped:
                 continue
-            src = getattr(pw, "transpose_of", None)
+            src = pw.transpose_of
             if src is not None and _TRANSPOSE_ON:
                 # a dense layer's second orientation: the transpose of its first fp16 copy
                 R, Cc = src.specs[0].rows, pw.specs[0].rows
                 transposes.append((_P(src.buf), _P(pw.buf), R, Cc, src.rows_pad, src.kpads[0], src.kpads[0], pw.kpads[0]))
                 continue
-            src = getattr(pw, "taps_of", None)
+            src = pw.taps_of
             if src is not None and _TRANSPOSE_ON:
                 # the four parity classes of a stride-2 transposed convolution: tap t' of a class block is the transpose
                 # of tap t = (py + 2 ty) * k + (px + 2 tx) of the single-block copy [rows][t * Bp + b]
@@ -341,21 +343,28 @@ def deterministic() -> bool:
 _SIDE = {"on": os.environ.get("FMRI_SIDE_STREAM") != "off", "streams": {}, "pending": []}
 
 
+class SideStream:
+    """A device's side stream with everything the fork / join below needs, looked up once: the switch to the side stream
+    and back is two _cuda_setStream calls (the ``torch.cuda.stream`` context manager costs ~25 us of Python per use, 55
+    times per step), the fork and join events are two reused Event objects (a wait captures the event's state when it is
+    issued, so re-recording the same event later is well defined)."""
+    __slots__ = ("stream", "ids", "fork", "join")
+
+    def __init__(self, stream):
+        self.stream = stream
+        self.ids = (stream.stream_id, stream.device_index, stream.device_type)
+        self.fork = torch.cuda.Event()
+        self.join = torch.cuda.Event()
+
+
 def _side_stream(device):
     if not _SIDE["on"]:
         return None
     key = (device.type, device.index)
-    st = _SIDE["streams"].get(key)
-    if st is None:
-        st = _SIDE["streams"][key] = torch.cuda.Stream(device)
-        # everything the fork / join below needs, looked up once: the switch to the side stream and back is two
-        # _cuda_setStream calls (the ``torch.cuda.stream`` context manager costs ~25 us of Python per use, 55 times per
-        # step), the fork and join events are two reused Event objects (a wait captures the event's state when it is
-        # issued, so re-recording the same event later is well defined)
-        st._fmri_ids = (st.stream_id, st.device_index, st.device_type)
-        st._fmri_fork = torch.cuda.Event()
-        st._fmri_join = torch.cuda.Event()
-    return st
+    side = _SIDE["streams"].get(key)
+    if side is None:
+        side = _SIDE["streams"][key] = SideStream(torch.cuda.Stream(device))
+    return side
 
 
 _set_stream = torch._C._cuda_setStream
@@ -365,20 +374,20 @@ def side_run(device, fn, *keep):
     """Run ``fn`` (kernel launches only) on the side stream, ordered after everything issued so far on the current
     stream.  ``keep``: tensors ``fn`` reads -- referenced until ``join_side`` so that the caching allocator cannot hand
     their memory to later current-stream work while the side stream still reads it."""
-    st = _side_stream(device)
-    if st is None:
+    side = _side_stream(device)
+    if side is None:
         fn()
         return
     cur = torch.cuda.current_stream(device)
-    st._fmri_fork.record(cur)
-    st.wait_event(st._fmri_fork)
-    sid, didx, dtype = st._fmri_ids
+    side.fork.record(cur)
+    side.stream.wait_event(side.fork)
+    sid, didx, dtype = side.ids
     _set_stream(stream_id=sid, device_index=didx, device_type=dtype)
     try:
         fn()
     finally:
         _set_stream(stream_id=cur.stream_id, device_index=cur.device_index, device_type=cur.device_type)
-    _SIDE["pending"].append((st, keep))
+    _SIDE["pending"].append((side, keep))
 
 
 def join_side(device=None):
@@ -386,18 +395,19 @@ def join_side(device=None):
     if not _SIDE["pending"]:
         return
     seen = []
-    for st, _ in _SIDE["pending"]:
-        if st not in seen:
-            seen.append(st)
-    for st in seen:
-        st._fmri_join.record(st)
-        torch.cuda.current_stream(st.device).wait_event(st._fmri_join)
+    for side, _ in _SIDE["pending"]:
+        if side not in seen:
+            seen.append(side)
+    for side in seen:
+        side.join.record(side.stream)
+        torch.cuda.current_stream(side.stream.device).wait_event(side.join)
     _SIDE["pending"].clear()
 
 
 def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0, hold=None, gate=None):
-    """Returns the packed fp32 gradient [apad][ldo].  ``hold``: see ``_grad_buffer``.  ``flops``: algorithmic FLOPs of the layer's weight gradient (for
-    the profiling hook of lib.call; 0 = 2 * rows * A * Bc * k^2 of the padded operands)."""
+    """Returns the packed fp32 gradient [apad][ldo] (or its slabs) as a ``WgradOut``.  ``hold``: see ``_grad_buffer``.
+    ``flops``: algorithmic FLOPs of the layer's weight gradient (for the profiling hook of lib.call; 0 = 2 * rows * A *
+    Bc * k^2 of the padded operands)."""
     ba = tile_for(A)
     apad = ceil_to(A, ba)
     ldo = ceil_to(k * k * Bc, 128)
@@ -416,11 +426,11 @@ def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0,
         splits = max(4, budget // groups)                               # block budget per group over the 4 planes
         nslabs = lib.load().fmri_wgrad_slabs(N, Yc, Xc, k, pad, splits)
         slabs = nslabs <= _WW_SLABS or _DET["on"]                       # few splits: per-split slabs, else atomics
-        out = _grad_buffer(hold, (nslabs, apad, ldo) if slabs else (apad, ldo), not slabs, P.device)
+        out = _wgrad_out(hold, (nslabs, apad, ldo) if slabs else (apad, ldo), not slabs, P.device, ldo)
         note("fmri::wgrad_win_kernel")
-        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k, stride,
-                 pad, flip, apad, ba, ldo, splits, 2 if slabs else 1)
-        return out, ldo
+        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
+                 stride, pad, flip, apad, ba, ldo, splits, 2 if slabs else 1)
+        return out
     if (stride == 1 and k == 5 and pad == 2 and A == 32 and Bc == 8 and Yc == Hq and Xc == Wq and _WN_ON
             and N * ((Yc + 7) // 8) * ((Xc + 7) // 8) >= 32768):
         # wave-private window kernel (csrc/wgrad_narrow.hip): atomic accumulation into zeroed 32 x ldo slab(s).  It
@@ -429,12 +439,12 @@ def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0,
         nslabs = 4                   # blocks add into slab (block index % 4): a quarter of the same-address atomics
         if _DET["on"]:               # one slab per block: every element is added once, onto zero
             nslabs = lib.load().fmri_wgrad_narrow_blocks(N, Yc, Xc)
-        out = _grad_buffer(hold, (nslabs, apad, ldo), True, P.device)
+        # (colsum: column 200 of every slab row a holds sum_m P[m][a])
+        out = _wgrad_out(hold, (nslabs, apad, ldo), True, P.device, ldo, colsum=True)
         note("fmri::wgrad_narrow_kernel")
-        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad,
-                 flip, apad, ba, ldo, nslabs, 3)
-        out._fmri_colsum = True            # column 200 of every slab row a holds sum_m P[m][a]
-        return out, ldo
+        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
+                 stride, pad, flip, apad, ba, ldo, nslabs, 3)
+        return out
     tiles = (ldo // 128) * (apad // ba)
     steps = (N * Yc * Xc + 63) // 64
     splits = 1
@@ -447,15 +457,13 @@ def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0,
         # zero-filled: the library re-derives the split count from the K steps (ceil(steps / ceil(steps / splits)), which
         # can be smaller than ``splits`` -- e.g. 18 of 19 at the 100-px encoder conv.0 with 4 images) and stores only that
         # many slabs, while unpack_grad / fmri_apply_batch sum all of them
-        out = _grad_buffer(hold, (splits, apad, ldo), True, P.device)
-    elif splits > 1:
-        out = _grad_buffer(hold, (apad, ldo), True, P.device)
+        out = _wgrad_out(hold, (splits, apad, ldo), True, P.device, ldo)
     else:
-        out = _grad_buffer(hold, (apad, ldo), False, P.device)
+        out = _wgrad_out(hold, (apad, ldo), splits > 1, P.device, ldo)
     note("fmri::wgrad_kernel")
-    lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad,
-             flip, apad, ba, ldo, splits, mode)
-    return out, ldo
+    lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
+             stride, pad, flip, apad, ba, ldo, splits, mode)
+    return out
 
 
 def unpack_grad(packed, grad_view, sp: PackSpec, ld: int, scale: float):
@@ -465,157 +473,298 @@ def unpack_grad(packed, grad_view, sp: PackSpec, ld: int, scale: float):
              sp.py, sp.px, sp.step, sp.TH, sp.TW, ld, float(scale), 1, nslabs, packed.shape[-2] * packed.shape[-1])
 
 
+# ------------------------------------------------------------------------------------------------
+# deferred weight gradients: GEMM-layout results queued for the sub-network's one-launch update
+# ------------------------------------------------------------------------------------------------
+class GradHold:
+    """A layer's persistent weight-gradient buffers while its group defers gradients: ``bufs[(shape, zeroed)]``, and
+    ``busy`` from the launch that took a buffer until the queue has consumed it."""
+    __slots__ = ("busy", "bufs")
+
+    def __init__(self):
+        self.busy = False
+        self.bufs = {}
+
+
+class WgradOut(NamedTuple):
+    """Result of ``run_wgrad``."""
+    buf: torch.Tensor                # packed fp32 gradient [apad][ld] or slabs [nslabs][apad][ld]
+    ld: int
+    clear: bool                      # a persistent buffer the kernel ADDS into: whoever consumes it hands it back zeroed
+    hold: Optional[GradHold]         # the hold ``buf`` was taken from (released by the queue), None for a fresh tensor
+    colsum: bool                     # narrow kernel: the spare column behind the taps holds the bias gradient's sums
+
+
+class GradEntry(NamedTuple):
+    """A queued weight gradient: ``grad_view`` += ``scale`` * (``out`` mapped through ``spec``)."""
+    out: WgradOut
+    grad_view: torch.Tensor
+    spec: PackSpec
+    scale: float
+
+
 def _grad_buffer(hold, shape, zeroed: bool, device):
-    """Output buffer of a weight-gradient launch.  ``hold`` is None: a fresh tensor per call (zeroed when the kernel
-    adds into it).  Otherwise (deferred gradients, ``begin_grads``): the layer's persistent buffer -- its address sits
-    in the device table of fmri_apply_batch, which also writes the zeros back after it has consumed the sums."""
-    if hold is None or hold.get("busy"):
-        out = (torch.zeros if zeroed else torch.empty)(shape, dtype=torch.float32, device=device)
-        out._fmri_clear = False
-        return out
+    """Output buffer of a weight-gradient launch.  ``hold`` is None or busy (a second gradient of the layer in one pass):
+    a fresh tensor per call (zeroed when the kernel adds into it).  Otherwise (deferred gradients, ``begin_grads``): the
+    layer's persistent buffer -- its address sits in the device table of fmri_apply_batch, which also writes the zeros
+    back after it has consumed the sums."""
+    if hold is None or hold.busy:
+        return (torch.zeros if zeroed else torch.empty)(shape, dtype=torch.float32, device=device)
     key = (tuple(shape), zeroed)
-    out = hold.get(key)
+    out = hold.bufs.get(key)
     if out is None:
-        if len(hold) > 6:                # (a batch size that keeps changing: do not collect a buffer per shape)
-            for k in [k for k in hold if k != "busy"]:
-                del hold[k]
-        out = hold[key] = torch.zeros(shape, dtype=torch.float32, device=device)
-        out._fmri_clear = zeroed
-        out._fmri_hold = hold
-    hold["busy"] = True
+        if len(hold.bufs) >= 6:          # (a batch size that keeps changing: do not collect a buffer per shape)
+            hold.bufs.clear()
+        out = hold.bufs[key] = torch.zeros(shape, dtype=torch.float32, device=device)
+    hold.busy = True
     return out
 
 
-def emit_grad(group, packed, grad_view, sp: PackSpec, ld: int, scale: float):
-    """What a weight-gradient launch does with its packed result: added to the reference-layout gradient now
-    (fmri_unpack_grad), or -- between ``begin_grads(group, defer=True)`` and ``apply_group`` -- queued for the
-    sub-network's one fmri_apply_batch launch."""
-    if getattr(group, "defer_grads", False):
-        group.pending.append((packed, grad_view, sp, ld, scale))
-    else:
-        unpack_grad(packed, grad_view, sp, ld, scale)
-
-
-def _hold_of(layer):
-    """The layer's persistent gradient buffers while its group defers gradients, else None."""
-    if not getattr(layer.group, "defer_grads", False):
-        return None
-    h = layer.__dict__.get("_ghold")
-    if h is None:
-        h = layer._ghold = {}
-    return h
-
-
-def _gate_of(layer):
-    """The device flag the layer's weight-gradient launch is conditioned on (``begin_grads(..., gate=)``), or None."""
-    g = layer.group
-    return getattr(g, "grad_gate", None) if getattr(g, "defer_grads", False) else None
+def _wgrad_out(hold, shape, zeroed: bool, device, ld: int, colsum: bool = False) -> WgradOut:
+    held = hold is not None and not hold.busy
+    buf = _grad_buffer(hold, shape, zeroed, device)          # (a module global at call time: tests wrap it)
+    return WgradOut(buf, ld, held and zeroed, hold if held else None, colsum)
 
 
 _FUSED_APPLY = os.environ.get("FMRI_FUSED_APPLY") != "off"
 _GATE_SKIP = os.environ.get("FMRI_GATE_SKIP") != "off"
 
 
-def begin_grads(group, defer: bool, gate: Optional[torch.Tensor] = None):
-    """Start of a backward pass over ``group`` (replaces ``zero_grad``).  ``defer``: the caller will hand the whole
-    group to ``apply_group`` right after the pass and nobody reads reference-layout gradients in between -- weight
-    gradients then stay in their GEMM layout until that one launch, and only the 1-D parameters' gradient segments
-    (which the backward pass accumulates in place) are cleared here instead of the whole buffer."""
-    defer = bool(defer and _FUSED_APPLY)
-    group.drop_pending()
-    group.defer_grads = defer
-    group.grads_consumed = False
-    # ``gate``: device int the group's update is conditioned on (the equilibrium gate's train_dis / train_dec): its
-    # weight-gradient GEMMs are launched with fmri_wgrad_if and do nothing in a step that does not train the group --
-    # the reference does not run that loss.backward() at all (train_vgan_stage1.py:420-431)
-    group.grad_gate = gate if (defer and _GATE_SKIP) else None
-    plan = getattr(group, "_flat_clear", None) if defer else None
-    if plan is not None and plan["flat"] is not None:
-        lib.call("fmri_apply_batch", _P(plan["flat"]), plan["flat_n"], plan["flat_tiles"], 2, None, 0.0, 0.0, 1.0,
-                 None, 0.0, None, 0)
-        group._cleared = plan["sig"]
-    else:
-        group.grad.zero_()
-        group._cleared = "all"
+class GradQueue:
+    """Per-group state of the deferred weight-gradient path (``begin_grads`` -> ``emit_grad`` -> ``materialize_grads`` /
+    ``apply_group`` / ``flush_pending``) and the caches of the group's device tables."""
 
+    def __init__(self, group):
+        self.group = group
+        self.defer = False               # between begin(defer=True) and apply / flush: emit() queues instead of unpacking
+        self.gate: Optional[torch.Tensor] = None     # device flag the weight-gradient launches are conditioned on
+        self.pending: List[GradEntry] = []           # queued, still in GEMM layout
+        self.materialized: List[GradEntry] = []      # already in the reference layout (materialize), update still due
+        self.consumed = False            # the last pass ended in the one-launch update: ``group.grad`` is an older pass
+        self.cleared = "all"             # what the start of the pass cleared of ``group.grad``: "all" or (offset, n) segments
+        self.flat_clear: Optional[dict] = None       # the plan whose flat table begin() clears the 1-D segments with
+        self.plans = {}                  # fmri_apply_batch tables by the buffers they describe (plan())
+        self.no_state: Optional[torch.Tensor] = None # the optimizer-state argument of the modes that have none
+        self.pack_tables = {}            # fmri_pack_weight_batch / fmri_transpose_f16_batch tables (_repack_group)
 
-def _plan_apply(group, state, update=True, pend=None):
-    """Device table of fmri_apply_batch for the pending gradients of ``group`` (cached while the same buffers come
-    back), or None when some tensor cannot go through it."""
-    L = lib.load()
-    pend = group.pending if pend is None else pend
-    key = tuple((p[0].data_ptr(), tuple(p[0].shape), p[1].data_ptr(), p[3], p[4]) for p in pend) + \
-        (state.data_ptr(), update)
-    plans = group.__dict__.setdefault("_apply_plans", {})
-    plan = plans.get(key)
-    if plan is not None:
-        return plan
-    nbytes = L.fmri_apply_entry_bytes()
-    g0, n_all = group.grad.data_ptr(), group.grad.numel()
-    rows, flat_rows, covered, fused, tiles = [], [], [], [], 0
-    by_master = {}
-    for pw in getattr(group, "packed", []):
-        if len(pw.specs) == 1:
-            by_master.setdefault(pw.master.data_ptr(), []).append(pw)
-    for packed, gv, sp, ld, scale in pend:
-        off = (gv.data_ptr() - g0) // 4
-        if not (0 <= off and off + gv.numel() <= n_all) or not gv.is_contiguous():
-            return None
-        if any(off < o + n and o < off + gv.numel() for o, n in covered):
-            return None                                   # two gradients of one tensor in one pass: separate launches
-        nsl = packed.shape[0] if packed.dim() == 3 else 1
-        pk, kpad = None, 0
-        for pw in by_master.get(group.data.data_ptr() + 4 * off, []) if update else ():
-            if pw.specs[0] == sp and pw.rows_pad >= sp.rows:
-                pk, kpad = pw.buf.data_ptr() + 2 * pw.offsets[0], pw.kpads[0]
-                fused.append(pw)
-                break
-        host = ctypes.create_string_buffer(nbytes)
-        n = L.fmri_apply_entry_fill(host, packed.data_ptr(), group.data.data_ptr() + 4 * off,
-                                    state.data_ptr() + (4 * off if update else 0), gv.data_ptr(), pk, sp.sa, sp.sta, sp.sb, sp.stb, sp.A, sp.TA, sp.B, sp.KW, sp.py,
-                                    sp.px, sp.step, sp.TH, sp.TW, ld, kpad, nsl, packed.shape[-2] * packed.shape[-1],
-                                    1 if getattr(packed, "_fmri_clear", False) else 0, float(scale), 0, tiles)
-        if n < 0:
-            lib.check(n, "fmri_apply_entry_fill")
-        if n == 0:
-            return None
-        rows.append(host.raw)
-        tiles += n
-        covered.append((off, gv.numel()))
-    # everything else of the buffer: 1-D parameters (and tensors without a weight-gradient GEMM), updated from the
-    # reference-layout gradient the backward pass accumulated in place
-    covered.sort()
-    segs, at = [], 0
-    for o, n in covered + [(n_all, 0)]:
-        if o > at:
-            segs.append((at, o - at))
-        at = max(at, o + n)
-    ftiles = 0
-    for o, n in segs:
-        for tile0, dst in ((tiles, rows), (ftiles, flat_rows)):
+    def _retire(self, entries, unpack=False, zero=False):
+        """Queue entries leave the queue: optionally added to the reference layout first (``unpack``), their accumulating
+        buffers handed back zeroed (``zero``: where no fmri_apply_batch launch has done it), their holds released."""
+        for e in entries:
+            if unpack:
+                unpack_grad(e.out.buf, e.grad_view, e.spec, e.out.ld, e.scale)
+            if zero and e.out.clear:
+                e.out.buf.zero_()
+            if e.out.hold is not None:
+                e.out.hold.busy = False
+
+    def drop_pending(self):
+        """Forget weight gradients that were queued for fmri_apply_batch and never applied; their persistent buffers go
+        back to the state the next weight-gradient launch expects."""
+        self._retire(self.pending, zero=True)
+        self.pending, self.materialized = [], []
+        self.defer, self.gate = False, None
+
+    def zero_grad(self):
+        self.drop_pending()
+        self.group.grad.zero_()
+        self.cleared, self.consumed = "all", False
+
+    def check_grads_readable(self):
+        """Raises when the last backward pass over the group ended in the one-launch update (``apply``): its weight
+        gradients went from the GEMM layout straight into the optimizer and ``grads`` still holds an older pass."""
+        if self.consumed or self.defer:
+            raise RuntimeError("the gradients of the last step() were consumed by its fused update and never stored in the "
+                               "reference layout: run forward() / gate() / backward() (and apply()) to inspect them")
+
+    def begin(self, defer: bool, gate: Optional[torch.Tensor] = None):
+        defer = bool(defer and _FUSED_APPLY)
+        self.drop_pending()
+        self.defer, self.consumed = defer, False
+        # ``gate``: device int the group's update is conditioned on (the equilibrium gate's train_dis / train_dec): its
+        # weight-gradient GEMMs are launched with fmri_wgrad_if and do nothing in a step that does not train the group --
+        # the reference does not run that loss.backward() at all (train_vgan_stage1.py:420-431)
+        self.gate = gate if (defer and _GATE_SKIP) else None
+        plan = self.flat_clear if defer else None
+        if plan is not None and plan["flat"] is not None:
+            lib.call("fmri_apply_batch", _P(plan["flat"]), plan["flat_n"], plan["flat_tiles"], 2, None, 0.0, 0.0, 1.0,
+                     None, 0.0, None, 0)
+            self.cleared = plan["sig"]
+        else:
+            self.group.grad.zero_()
+            self.cleared = "all"
+
+    def emit(self, out: WgradOut, grad_view, sp: PackSpec, scale: float):
+        if self.defer:
+            self.pending.append(GradEntry(out, grad_view, sp, scale))
+        else:
+            unpack_grad(out.buf, grad_view, sp, out.ld, scale)
+
+    def plan(self, state, update=True, pend=None):
+        """Device table of fmri_apply_batch for the pending gradients (cached while the same buffers come back), or None
+        when some tensor cannot go through it."""
+        L = lib.load()
+        group = self.group
+        pend = self.pending if pend is None else pend
+        key = tuple((e.out.buf.data_ptr(), tuple(e.out.buf.shape), e.grad_view.data_ptr(), e.out.ld, e.scale)
+                    for e in pend) + (state.data_ptr(), update)
+        plan = self.plans.get(key)
+        if plan is not None:
+            return plan
+        nbytes = L.fmri_apply_entry_bytes()
+        g0, n_all = group.grad.data_ptr(), group.grad.numel()
+        rows, flat_rows, covered, fused, tiles = [], [], [], [], 0
+        by_master = {}
+        for pw in group.packed:
+            if len(pw.specs) == 1:
+                by_master.setdefault(pw.master.data_ptr(), []).append(pw)
+        for (packed, ld, clear, _, _), gv, sp, scale in pend:
+            off = (gv.data_ptr() - g0) // 4
+            if not (0 <= off and off + gv.numel() <= n_all) or not gv.is_contiguous():
+                return None
+            if any(off < o + n and o < off + gv.numel() for o, n in covered):
+                return None                                   # two gradients of one tensor in one pass: separate launches
+            nsl = packed.shape[0] if packed.dim() == 3 else 1
+            pk, kpad = None, 0
+            for pw in by_master.get(group.data.data_ptr() + 4 * off, []) if update else ():
+                if pw.specs[0] == sp and pw.rows_pad >= sp.rows:
+                    pk, kpad = pw.buf.data_ptr() + 2 * pw.offsets[0], pw.kpads[0]
+                    fused.append(pw)
+                    break
             host = ctypes.create_string_buffer(nbytes)
-            k = L.fmri_apply_entry_fill(host, None, group.data.data_ptr() + 4 * o,
-                                        state.data_ptr() + (4 * o if update else 0), g0 + 4 * o,
-                                        None, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 1, 1, 1, 0, 0, 1, 0, 0, 1.0, n, tile0)
-            if k <= 0:
-                lib.check(k if k < 0 else -1, "fmri_apply_entry_fill")
-            dst.append(host.raw)
-        tiles += k
-        ftiles += k
-    up = lambda rr: torch.frombuffer(bytearray(b"".join(rr)), dtype=torch.uint8).to(group.device) if rr else None
-    plan = dict(key=key, table=up(rows), n=len(rows), tiles=tiles, flat=up(flat_rows), flat_n=len(flat_rows),
-                flat_tiles=ftiles, sig=tuple(segs), covered=covered, fused=fused)
-    if len(plans) >= 8:              # (buffers that keep changing, e.g. a varying batch size: do not collect tables)
-        keep = getattr(group, "_flat_clear", None)
-        plans.clear()
-        if keep is not None:
-            plans[keep["key"]] = keep
-    plans[key] = plan
-    if getattr(group, "_flat_clear", None) is None:
-        # what begin_grads clears from now on: the first table's flat segments -- every 1-D parameter is in them (and,
-        # when the table was built for a part of the group, tensors of the rest: cleared for nothing, a few MB)
-        group._flat_clear = plan
-    return plan
+            n = L.fmri_apply_entry_fill(host, packed.data_ptr(), group.data.data_ptr() + 4 * off,
+                                        state.data_ptr() + (4 * off if update else 0), gv.data_ptr(), pk, sp.sa, sp.sta,
+                                        sp.sb, sp.stb, sp.A, sp.TA, sp.B, sp.KW, sp.py, sp.px, sp.step, sp.TH, sp.TW, ld,
+                                        kpad, nsl, packed.shape[-2] * packed.shape[-1], 1 if clear else 0, float(scale), 0,
+                                        tiles)
+            if n < 0:
+                lib.check(n, "fmri_apply_entry_fill")
+            if n == 0:
+                return None
+            rows.append(host.raw)
+            tiles += n
+            covered.append((off, gv.numel()))
+        # everything else of the buffer: 1-D parameters (and tensors without a weight-gradient GEMM), updated from the
+        # reference-layout gradient the backward pass accumulated in place
+        covered.sort()
+        segs, at = [], 0
+        for o, n in covered + [(n_all, 0)]:
+            if o > at:
+                segs.append((at, o - at))
+            at = max(at, o + n)
+        ftiles = 0
+        for o, n in segs:
+            for tile0, dst in ((tiles, rows), (ftiles, flat_rows)):
+                host = ctypes.create_string_buffer(nbytes)
+                k = L.fmri_apply_entry_fill(host, None, group.data.data_ptr() + 4 * o,
+                                            state.data_ptr() + (4 * o if update else 0), g0 + 4 * o,
+                                            None, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 1, 1, 1, 0, 0, 1, 0, 0, 1.0, n, tile0)
+                if k <= 0:
+                    lib.check(k if k < 0 else -1, "fmri_apply_entry_fill")
+                dst.append(host.raw)
+            tiles += k
+            ftiles += k
+        up = lambda rr: torch.frombuffer(bytearray(b"".join(rr)), dtype=torch.uint8).to(group.device) if rr else None
+        plan = dict(key=key, table=up(rows), n=len(rows), tiles=tiles, flat=up(flat_rows), flat_n=len(flat_rows),
+                    flat_tiles=ftiles, sig=tuple(segs), covered=covered, fused=fused)
+        if len(self.plans) >= 8:         # (buffers that keep changing, e.g. a varying batch size: do not collect tables)
+            self.plans.clear()
+            if self.flat_clear is not None:                   # (begin() launches from this one's table: it stays)
+                self.plans[self.flat_clear["key"]] = self.flat_clear
+        self.plans[key] = plan
+        if self.flat_clear is None:
+            # what begin() clears from now on: the first table's flat segments -- every 1-D parameter is in them (and,
+            # when the table was built for a part of the group, tensors of the rest: cleared for nothing, a few MB)
+            self.flat_clear = plan
+        return plan
+
+    def flush(self, keep=()):
+        """Deferred gradients -> the reference-layout gradient buffer (what the separate launches would have left there).
+        ``keep``: queue entries whose gradients ``materialize`` has already put there."""
+        grad = self.group.grad
+        pend, self.pending = self.pending, []
+        self.defer = False
+        if self.cleared != "all":
+            # only the 1-D segments were cleared at the start of this pass: clear what the tensors' ranges still hold
+            g0 = grad.data_ptr()
+            holes = sorted(list(self.cleared) + [((e.grad_view.data_ptr() - g0) // 4, e.grad_view.numel()) for e in keep])
+            at = 0
+            for o, n in holes + [(grad.numel(), 0)]:
+                if o > at:
+                    grad[at:o].zero_()
+                at = max(at, o + n)
+            self.cleared = "all"
+        self._retire(pend, unpack=True, zero=True)
+
+    def materialize(self):
+        """Deferred gradients -> reference-layout gradient buffer in ONE launch (fmri_apply_batch mode 0: slab sums mapped
+        and stored, no read-modify-write, no memset in front) -- what a data-parallel step does before the gradient
+        all-reduce.  May be called for a part of the group's tensors (the ones queued so far)."""
+        if not self.defer or not self.pending:
+            return
+        if self.no_state is None:
+            self.no_state = torch.zeros(1, dtype=torch.float32, device=self.group.device)
+        plan = self.plan(self.no_state, update=False)
+        if plan is None:
+            # (keep what an earlier partial call has already put into the reference layout -- it may be mid-reduction)
+            self.flush(keep=self.materialized)
+            return
+        lib.note(bytes=8.0 * self.group.numel)
+        lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], 0, None, 0.0, 0.0, 1.0, None, 0.0, None, 0)
+        self._retire(self.pending)
+        self.materialized = self.materialized + self.pending
+        self.pending = []                # (``defer`` stays on: the rest of the pass may queue more)
+
+    def apply(self, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0, stats: Optional[int] = None) -> bool:
+        if not self.defer:
+            return False
+        group = self.group
+        done, self.materialized = self.materialized, []
+        plan, mode = None, 1
+        if self.pending and not done:
+            plan = self.plan(state)
+        elif done and not self.pending:
+            # data parallel: every gradient already sits in the reference layout (materialize, all-reduced since); the
+            # same table drives the update from there (mode 3)
+            mode = 3
+            plan = self.plan(state, pend=done)
+        if plan is None or not _segments_within(plan["sig"], self.cleared):
+            self.flush(keep=done)
+            return False
+        lib.note(bytes=22.0 * group.numel)
+        gate = self.gate
+        gated = 1 if (gate is not None and flag is not None and gate.data_ptr() == flag.data_ptr()) else 0
+        if stats is None:
+            lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps, 1.0,
+                     _P(gdev), clamp, _P(flag), gated)
+        else:
+            part = plan.get("stat_part")
+            if part is None:                  # two fmri_stat records per block, allocated with the plan
+                part = plan["stat_part"] = torch.empty(max(1, 2 * plan["tiles"]) * lib.STAT_BYTES, dtype=torch.uint8,
+                                                       device=group.device)
+            lib.call("fmri_apply_batch_stats", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps,
+                     1.0, _P(gdev), clamp, _P(flag), gated, _P(part))
+            lib.call("fmri_stat_fold", _P(part), plan["tiles"], _P(flag), stats)
+        self._retire(self.pending)
+        self.pending = []
+        self.defer = False
+        self.consumed = mode == 1        # the reference-layout gradient buffer was never written in this pass
+        group.version += 1
+        for pw in plan["fused"]:
+            pw.version = group.version
+        _repack_group(group, skip=plan["fused"])
+        return True
+
+
+def grad_queue(group) -> GradQueue:
+    """The group's queue.  A FlatGroup makes its own; a stand-in that only carries what a single layer needs
+    (nets._Versioned, the tests' minimal groups) gets one -- and its ``packed`` list -- attached at its first use here.
+    Nobody calls ``begin_grads`` on a stand-in, so its queue never defers."""
+    q = getattr(group, "gq", None)
+    if q is None:
+        q = group.gq = GradQueue(group)
+        group.packed = []
+    return q
 
 
 def _segments_within(segs, cleared) -> bool:
@@ -627,51 +776,44 @@ def _segments_within(segs, cleared) -> bool:
     return all(any(co <= o and o + n <= co + cn for co, cn in cleared) for o, n in segs)
 
 
+# The entry points the steps, the tests and the tools call: the queue's methods by their group.
+def begin_grads(group, defer: bool, gate: Optional[torch.Tensor] = None):
+    """Start of a backward pass over ``group`` (replaces ``zero_grad``).  ``defer``: the caller will hand the whole
+    group to ``apply_group`` right after the pass and nobody reads reference-layout gradients in between -- weight
+    gradients then stay in their GEMM layout until that one launch, and only the 1-D parameters' gradient segments
+    (which the backward pass accumulates in place) are cleared here instead of the whole buffer."""
+    grad_queue(group).begin(defer, gate)
+
+
+def emit_grad(group, packed: WgradOut, grad_view, sp: PackSpec, ld: int, scale: float):
+    """What a weight-gradient launch does with its packed result: added to the reference-layout gradient now
+    (fmri_unpack_grad), or -- between ``begin_grads(group, defer=True)`` and ``apply_group`` -- queued for the
+    sub-network's one fmri_apply_batch launch."""
+    assert ld == packed.ld
+    grad_queue(group).emit(packed, grad_view, sp, scale)
+
+
+def _hold_of(layer) -> Optional[GradHold]:
+    """The layer's persistent gradient buffers while its group defers gradients, else None."""
+    return layer.ghold if grad_queue(layer.group).defer else None
+
+
+def _gate_of(layer):
+    """The device flag the layer's weight-gradient launch is conditioned on (``begin_grads(..., gate=)``), or None."""
+    q = grad_queue(layer.group)
+    return q.gate if q.defer else None
+
+
+def _plan_apply(group, state, update=True, pend=None):
+    return grad_queue(group).plan(state, update, pend)
+
+
 def flush_pending(group, keep=()):
-    """Deferred gradients -> the reference-layout gradient buffer (what the separate launches would have left there).
-    ``keep``: queue entries whose gradients materialize_grads has already put there."""
-    pend, group.pending = getattr(group, "pending", []), []
-    group.defer_grads = False
-    if getattr(group, "_cleared", "all") != "all":
-        # only the 1-D segments were cleared at the start of this pass: clear what the tensors' ranges still hold
-        g0 = group.grad.data_ptr()
-        holes = sorted(list(group._cleared) + [((p[1].data_ptr() - g0) // 4, p[1].numel()) for p in keep])
-        at = 0
-        for o, n in holes + [(group.grad.numel(), 0)]:
-            if o > at:
-                group.grad[at:o].zero_()
-            at = max(at, o + n)
-        group._cleared = "all"
-    for packed, gv, sp, ld, scale in pend:
-        unpack_grad(packed, gv, sp, ld, scale)
-        if getattr(packed, "_fmri_clear", False):
-            packed.zero_()
-        if getattr(packed, "_fmri_hold", None) is not None:
-            packed._fmri_hold["busy"] = False
+    grad_queue(group).flush(keep)
 
 
 def materialize_grads(group):
-    """Deferred gradients -> reference-layout gradient buffer in ONE launch (fmri_apply_batch mode 0: slab sums mapped
-    and stored, no read-modify-write, no memset in front) -- what a data-parallel step does before the gradient
-    all-reduce.  May be called for a part of the group's tensors (the ones queued so far)."""
-    if not getattr(group, "defer_grads", False) or not group.pending:
-        return
-    st = group.__dict__.get("_no_state")
-    if st is None:
-        st = group._no_state = torch.zeros(1, dtype=torch.float32, device=group.device)
-    plan = _plan_apply(group, st, update=False)
-    if plan is None:
-        # (keep what an earlier partial call has already put into the reference layout -- it may be mid-reduction)
-        flush_pending(group, keep=getattr(group, "materialized", []))
-        return
-    lib.note(bytes=8.0 * group.numel)
-    lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], 0, None, 0.0, 0.0, 1.0, None, 0.0, None, 0)
-    for p in group.pending:
-        h = getattr(p[0], "_fmri_hold", None)
-        if h is not None:
-            h["busy"] = False
-    group.materialized = getattr(group, "materialized", []) + group.pending
-    group.pending = []            # (defer_grads stays on: the rest of the pass may queue more)
+    grad_queue(group).materialize()
 
 
 def apply_group(group, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0, stats: Optional[int] = None) -> bool:
@@ -681,47 +823,7 @@ def apply_group(group, state, lr_dev, alpha, eps, flag, gdev, clamp=0.0, stats: 
     (nothing deferred, or a tensor the table cannot describe); the caller then runs the optimizer and the re-pack.
     ``stats``: device address of the numerics monitor's (gradient, weights) record pair (fmri_hip/monitor.py): the
     update then also writes per-block statistics, folded into that pair behind it."""
-    if not getattr(group, "defer_grads", False):
-        return False
-    done = getattr(group, "materialized", [])
-    group.materialized = []
-    plan, mode = None, 1
-    if group.pending and not done:
-        plan = _plan_apply(group, state)
-    elif done and not group.pending:
-        # data parallel: every gradient already sits in the reference layout (materialize_grads, all-reduced since); the
-        # same table drives the update from there (mode 3)
-        mode = 3
-        plan = _plan_apply(group, state, pend=done)
-    if plan is None or not _segments_within(plan["sig"], group._cleared):
-        flush_pending(group, keep=done)
-        return False
-    lib.note(bytes=22.0 * group.numel)
-    gate = getattr(group, "grad_gate", None)
-    gated = 1 if (gate is not None and flag is not None and gate.data_ptr() == flag.data_ptr()) else 0
-    if stats is None:
-        lib.call("fmri_apply_batch", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps, 1.0,
-                 _P(gdev), clamp, _P(flag), gated)
-    else:
-        part = plan.get("stat_part")
-        if part is None:                  # two fmri_stat records per block, allocated with the plan
-            part = plan["stat_part"] = torch.empty(max(1, 2 * plan["tiles"]) * lib.STAT_BYTES, dtype=torch.uint8,
-                                                   device=group.device)
-        lib.call("fmri_apply_batch_stats", _P(plan["table"]), plan["n"], plan["tiles"], mode, _P(lr_dev), alpha, eps,
-                 1.0, _P(gdev), clamp, _P(flag), gated, _P(part))
-        lib.call("fmri_stat_fold", _P(part), plan["tiles"], _P(flag), stats)
-    for p in group.pending:
-        h = getattr(p[0], "_fmri_hold", None)
-        if h is not None:
-            h["busy"] = False
-    group.pending = []
-    group.defer_grads = False
-    group.grads_consumed = mode == 1      # the reference-layout gradient buffer was never written in this pass
-    group.version += 1
-    for pw in plan["fused"]:
-        pw.version = group.version
-    _repack_group(group, skip=plan["fused"])
-    return True
+    return grad_queue(group).apply(state, lr_dev, alpha, eps, flag, gdev, clamp, stats)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -740,6 +842,13 @@ class ConvLayer:
         self.bg = group.grads[bkey] if bkey else None
         self.cin, self.cout, self.k, self.stride, self.pad, self.out_pad = cin, cout, k, stride, pad, out_pad
         self.cinp, self.coutp = pad8(cin), pad8(cout)
+        self.ghold = GradHold()
+        # epilogue scratch and what the last launch's epilogue did (forward: take_stats / aff_applied, dgrad:
+        # take_bwd_stats / act_applied)
+        self._stat_part: Optional[torch.Tensor] = None
+        self._bwd_part: Optional[torch.Tensor] = None
+        self._stat_rows = self._bwd_rows = 0
+        self.aff_applied = self.act_applied = False
         kk = k * k
         self.t_out, self.t_in = tile_for(cout), tile_for(cin)
         if kind == "conv":
@@ -787,7 +896,7 @@ class ConvLayer:
         self._stat_rows = 0
         if bn_groups > 0 and _EPI_STATS and N % bn_groups == 0:
             cap = (N // bn_groups) * Ho * Wo // 128 + 8
-            part = getattr(self, "_stat_part", None)
+            part = self._stat_part
             if part is None or part.shape[0] < bn_groups or part.shape[1] < cap:
                 part = self._stat_part = torch.empty(bn_groups, cap, 2, self.coutp, dtype=torch.float32,
                                                      device=x.device)
@@ -803,7 +912,7 @@ class ConvLayer:
 
     def take_stats(self, g: int = 0) -> Optional[torch.Tensor]:
         """Rows [P][2][coutp] with the per-block batch statistics of group ``g`` of the last forward, or None."""
-        return self._stat_part[g, :self._stat_rows] if getattr(self, "_stat_rows", 0) > 0 else None
+        return self._stat_part[g, :self._stat_rows] if self._stat_rows > 0 else None
 
     def _flops(self, N, Hi, Wi, Ho, Wo):
         """Algorithmic FLOPs of one pass (fwd == dgrad == wgrad): 2 * pixels * cin * cout * k^2, pixels = conv
@@ -836,7 +945,7 @@ class ConvLayer:
             bn, G = bn_bwd["bn"], len(bn_bwd["groups"])
             if bn.C == self.cinp and not bn.perm and N % G == 0 and G <= 4:
                 cap = (N // G) * hi * wi // 128 + 8
-                part = getattr(self, "_bwd_part", None)
+                part = self._bwd_part
                 if part is None or part.shape[0] < G or part.shape[1] < cap:
                     part = self._bwd_part = torch.empty(max(G, 2), cap, 2, self.cinp, dtype=torch.float32,
                                                         device=dy.device)
@@ -857,7 +966,7 @@ class ConvLayer:
 
     def take_bwd_stats(self):
         """(rows tensor [G][cap][2][cinp], valid rows per group) of the last ``dgrad(..., bn_bwd=...)``, or None."""
-        return (self._bwd_part, self._bwd_rows) if getattr(self, "_bwd_rows", 0) > 0 else None
+        return (self._bwd_part, self._bwd_rows) if self._bwd_rows > 0 else None
 
     def wgrad(self, x: torch.Tensor, dy: torch.Tensor, scale: float, bias_too: bool = False):
         """weight.grad += (1/scale) * dW(x, dy)  (on the side stream: ops.join_side() before the gradient is read).
@@ -873,24 +982,25 @@ class ConvLayer:
                                           "reduce the bias gradient with act_backward(colsum=...) as DecoderNet does")
             # exchange the roles (dW[co][ci][k] = sum_m' X[m'][ci] * dY[m' + pad - k][co]) so that the gathered
             # operand is the narrow one: rows ci, columns (tap, co)
-            packed, ldo = run_wgrad(x, dy, N, Hi, Wi, self.cinp, Ho, Wo, self.coutp, self.k, 1, self.pad, flip=1,
-                                    flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
+            out = run_wgrad(x, dy, N, Hi, Wi, self.cinp, Ho, Wo, self.coutp, self.k, 1, self.pad, flip=1,
+                            flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
             kk = self.k * self.k
             spec = PackSpec(sa=kk, sta=0, A=self.cin, TA=1, sb=self.cin * kk, stb=1, B=self.cout, KW=self.k,
                             TH=self.k, TW=self.k)
-            emit_grad(self.group, packed, self.wg, spec, ldo, 1.0 / scale)
+            emit_grad(self.group, out, self.wg, spec, out.ld, 1.0 / scale)
             return
         if self.kind == "conv":
-            packed, ldo = run_wgrad(dy, x, N, Ho, Wo, self.coutp, Hi, Wi, self.cinp, self.k, self.stride, self.pad,
-                                    flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
+            out = run_wgrad(dy, x, N, Ho, Wo, self.coutp, Hi, Wi, self.cinp, self.k, self.stride, self.pad,
+                            flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
         else:
-            packed, ldo = run_wgrad(x, dy, N, Hi, Wi, self.cinp, Ho, Wo, self.coutp, self.k, 2, self.pad,
-                                    flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
-        emit_grad(self.group, packed, self.wg, self.gspec, ldo, 1.0 / scale)
+            out = run_wgrad(x, dy, N, Hi, Wi, self.cinp, Ho, Wo, self.coutp, self.k, 2, self.pad,
+                            flops=self._flops(N, Hi, Wi, Ho, Wo), hold=_hold_of(self), gate=_gate_of(self))
+        emit_grad(self.group, out, self.wg, self.gspec, out.ld, 1.0 / scale)
         if bias_too:
             # bias.grad += (1/scale) * sum over pixels of dy: the narrow kernel's spare column, else a reduction
-            if getattr(packed, "_fmri_colsum", False):
+            if out.colsum:
                 # slabs [nslabs][apad][ldo]: element (a, column k*k*cinp) of every slab
+                packed = out.buf
                 colsum_acc(packed[0, 0, self.k * self.k * self.cinp:], packed.shape[0], self.cout,
                            packed.shape[1] * packed.shape[2], packed.shape[2], 1.0 / scale, self.bg)
             else:
@@ -921,6 +1031,7 @@ class DenseLayer:
             self.b, self.bg = bkey if bkey else (None, None)
         self.k_in, self.n_out = k_in, n_out
         self.kp, self.np_ = pad8(k_in), pad8(n_out)
+        self.ghold = GradHold()
         # 64-wide output tiles for the dense layers: they run on a few hundred rows, so the launch is filled by split-K
         # slabs -- twice the tiles halve the slabs (and their fp32 write + re-read): -15...-20 % on the two
         # 16384-wide layers, nothing lost on the others (tools/probes/dense_tiles.py, profiles/r04_dense_tiles.log)
@@ -987,9 +1098,9 @@ class DenseLayer:
 
     def _wgrad(self, x: torch.Tensor, dy: torch.Tensor, scale: float):
         M = x.shape[0]
-        packed, ldo = run_wgrad(dy, x, M, 1, 1, self.np_, 1, 1, self.kp, 1, 1, 0, flops=2.0 * M * self.k_in * self.n_out,
-                                hold=_hold_of(self), gate=_gate_of(self))
-        emit_grad(self.group, packed, self.wg, self.gspec, ldo, 1.0 / scale)
+        out = run_wgrad(dy, x, M, 1, 1, self.np_, 1, 1, self.kp, 1, 1, 0, flops=2.0 * M * self.k_in * self.n_out,
+                        hold=_hold_of(self), gate=_gate_of(self))
+        emit_grad(self.group, out, self.wg, self.gspec, out.ld, 1.0 / scale)
 
     def bias_grad(self, dy: torch.Tensor, scale: float):
         if self.bg is not None:
@@ -1027,6 +1138,8 @@ class BatchNorm:
         self.reducer = None
         self.eval_mode = False
         self._v = -1
+        # lazy running statistics (enable_lazy_running): on, the buf_version the engine-order copies were loaded at, written
+        self._lazy, self._run_v, self._run_dirty = False, -1, False
         if perm:
             dev = self.gamma.device
             self.gamma_e = torch.empty(C, dtype=torch.float32, device=dev)
@@ -1050,13 +1163,13 @@ class BatchNorm:
     # loaded when the buffers were written from outside (FlatGroup.buf_version) and written back when somebody reads the
     # buffers (FlatGroup.flush_hooks, i.e. state_dict()).
     def enable_lazy_running(self):
-        if self.perm and not getattr(self, "_lazy", False):
+        if self.perm and not self._lazy:
             self._lazy, self._run_v, self._run_dirty = True, -1, False
             self.group.flush_hooks.append(self.flush_running)
 
     def _running_in(self):
         if self.perm:
-            if getattr(self, "_lazy", False):
+            if self._lazy:
                 if self._run_v == self.group.buf_version:
                     return
                 self._run_v, self._run_dirty = self.group.buf_version, False
@@ -1066,7 +1179,7 @@ class BatchNorm:
 
     def _running_out(self):
         if self.perm:
-            if getattr(self, "_lazy", False):
+            if self._lazy:
                 self._run_dirty = True
                 return
             c0, hw = self.perm
@@ -1077,7 +1190,7 @@ class BatchNorm:
         """Lazy mode: write the engine-order running_mean / running_var back to the reference-order buffers.  Done whenever
         the engine-order copies are the loaded, current ones -- a replayed HIP graph updates them without passing through
         ``_running_out``, so there is no reliable dirty flag."""
-        if self.perm and getattr(self, "_lazy", False) and self._run_v == self.group.buf_version:
+        if self.perm and self._lazy and self._run_v == self.group.buf_version:
             c0, hw = self.perm
             lib.call("fmri_permute_chw", _P(self.rm_e), _P(self.rm), c0, hw, 0, 1.0, 0)
             lib.call("fmri_permute_chw", _P(self.rv_e), _P(self.rv), c0, hw, 0, 1.0, 0)

@@ -18,6 +18,8 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
+from .ops import GradQueue
+
 
 @dataclass(frozen=True)
 class ArchConfig:
@@ -196,6 +198,8 @@ class FlatGroup:
         self.version = 0      # bumped whenever ``data`` changes -> packed fp16 copies are stale
         self.buf_version = 0  # bumped whenever ``bufs`` are written from outside (load_state_dict)
         self.flush_hooks = [] # callables bringing ``bufs`` up to date before they are read (lazy engine-order shadows)
+        self.packed = []      # the layers' fp16 GEMM copies of ``data`` (ops.PackedWeight), in registration order
+        self.gq = GradQueue(self)   # weight gradients kept in GEMM layout until the one-launch update (ops.begin_grads)
 
     # ---- state dict ------------------------------------------------------------------------
     def state_dict(self, prefix: str = "") -> Dict[str, torch.Tensor]:
@@ -228,31 +232,15 @@ class FlatGroup:
         sd = {k: torch.from_numpy(v) for k, v in recipe_fill(self.spec, rs, perturb).items()}
         self.load_state_dict(sd)
 
+    # ---- deferred weight gradients (ops.GradQueue) ------------------------------------------
     def drop_pending(self):
-        """Forget weight gradients that were queued for fmri_apply_batch (ops.begin_grads) and never applied; their
-        persistent buffers go back to the state the next weight-gradient launch expects."""
-        for p in getattr(self, "pending", None) or ():
-            if getattr(p[0], "_fmri_clear", False):
-                p[0].zero_()
-            if getattr(p[0], "_fmri_hold", None) is not None:
-                p[0]._fmri_hold["busy"] = False
-        self.pending = []
-        self.materialized = []
-        self.defer_grads = False
-        self.grad_gate = None
+        self.gq.drop_pending()
 
     def zero_grad(self):
-        self.drop_pending()
-        self.grad.zero_()
-        self._cleared = "all"
-        self.grads_consumed = False
+        self.gq.zero_grad()
 
     def check_grads_readable(self):
-        """Raises when the last backward pass over this group ended in the one-launch update (ops.apply_group): its weight
-        gradients went from the GEMM layout straight into the optimizer and ``grads`` still holds an older pass."""
-        if getattr(self, "grads_consumed", False) or getattr(self, "defer_grads", False):
-            raise RuntimeError("the gradients of the last step() were consumed by its fused update and never stored in the "
-                               "reference layout: run forward() / gate() / backward() (and apply()) to inspect them")
+        self.gq.check_grads_readable()
 
 
 # ------------------------------------------------------------------------------------------------

@@ -156,7 +156,8 @@ class _GanStepBase(_StepBase):
         return dlogit16
 
     def _start_cotangents(self, B):
-        """fp16 starting cotangents of stream A (logits) and stream B (raw conv-3 features)."""
+        """fp16 starting cotangents of stream A (logits) and stream B (raw conv-3 features), and what
+        ``DiscriminatorNet.backward`` may know about the latter (its ``stack`` / ``zero_tail`` arguments)."""
         feat = self.fw["feat"]
         dev = feat.device
         dlogit16 = self._logit_cotangent(B)
@@ -164,10 +165,9 @@ class _GanStepBase(_StepBase):
         # discriminator's conv backward (DiscriminatorNet fills the first half with stream A: no concatenation copy)
         stack = torch.empty((2 * feat.shape[0],) + tuple(feat.shape[1:]), dtype=feat.dtype, device=dev)
         dfeat16 = stack[feat.shape[0]:]
-        dfeat16._fmri_stack = stack
-        dfeat16._fmri_zero_tail = B          # the rows of the sampled images are exact zeros (fmri_feat_mse_bwd)
         lib.call("fmri_feat_mse_bwd", _P(feat), B, feat[0].numel(), _P(dfeat16), self.sc.b, _P(self._slot(S_NB)))
-        return dlogit16, dfeat16
+        # (zero_tail: the rows of the sampled images are exact zeros)
+        return dlogit16, dfeat16, dict(stack=stack, zero_tail=B)
 
     def _encoder_cotangent(self, dz, norm_slot: int, kl_dev=None, extra_dmu=None):
         """Decoder-side dz (carried at the device factor of ``norm_slot``: S_NB or S_NP) -> the encoder's fp16 head
@@ -320,7 +320,7 @@ class Stage1Step(_GanStepBase):
         ops.begin_grads(self.enc.group, fuse)
         ops.begin_grads(self.dec.group, fuse, gate=self._gate_flag(1))
         ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
-        dlogit16, dfeat16 = self._start_cotangents(B)
+        dlogit16, dfeat16, stacked = self._start_cotangents(B)
         # weight gradients run on the side stream (ops.side_run) and are joined once, at the end of the backward pass, so
         # that a sub-network's last weight gradients overlap the next one's backward
         dp = self.dd.on
@@ -331,7 +331,7 @@ class Stage1Step(_GanStepBase):
         early = early_apply and ops._SIDE["on"] and self.dd.recorder is None
         self._applied_early = early
         dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B),
-                                           join=dp and not early)
+                                           join=dp and not early, **stacked)
         if early:
             ops.side_run(dev, lambda: self._reduce_apply(self.opt_dis, self.dis, self.flags[0:1], S_NA))
         else:
@@ -407,7 +407,9 @@ class Stage1Step(_GanStepBase):
                   b_dev=self._slot(S_C2))
             axpby(dimg_a[B:], None, -sc.dec / sc.a, 0.0, out=cot[B:], a_dev=self._slot(S_C2))
             entries = [dict(g=0, scale=sc.dec, train=True), dict(g=1, scale=sc.dec, train=True)]
-            self.dec.backward(fw["dctx"], cot, entries, join=dp)
+            # (joined on one GPU too: no encoder pass follows whose join would cover the weight gradients still running
+            # on the side stream, and ``apply`` reads them on this one)
+            self.dec.backward(fw["dctx"], cot, entries)
             self.dd.all_reduce_async(self.dec.group.grad)
             self.dd.wait_all()
             return
@@ -702,13 +704,13 @@ class CognitiveStep(_GanStepBase):
         fuse = fuse and self.dd.recorder is None
         if self.mode == "vae":
             return self._backward_pixel(fuse)
-        dlogit16, dfeat16 = self._start_cotangents(B)
+        dlogit16, dfeat16, stacked = self._start_cotangents(B)
         # (gate flags: see Stage1Step -- no gradients for a sub-network the gate does not train)
         if self.stage == 2:
             ops.begin_grads(self.cog.group, fuse)
             ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
             _, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 2 * B),
-                                          img_streams=(False, True))
+                                          img_streams=(False, True), **stacked)
             self._reduce_async(self.dis.group)                  # under the decoder / cognitive-encoder backward
             entries = [dict(g=fw["g_tilde"], scale=sc.b, train=False, need_dz=True)]
             dz = self.dec.backward(fw["dctx"], dimg_b, entries)[0]
@@ -719,7 +721,8 @@ class CognitiveStep(_GanStepBase):
         else:
             ops.begin_grads(self.dec.group, fuse, gate=self._gate_flag(1))
             ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
-            dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B))
+            dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B),
+                                               **stacked)
             self._reduce_async(self.dis.group)                  # under the decoder backward
             cot = axpby(dimg_b, dimg_a, sc.dec / sc.b, -sc.dec / sc.a, a_dev=self._slot(S_C1), b_dev=self._slot(S_C2))
             entries = [dict(g=0, scale=sc.dec, train=True), dict(g=1, scale=sc.dec, train=True)]

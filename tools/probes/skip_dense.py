@@ -23,13 +23,12 @@ def fake_gemm(self, x, pw, M, Ci, Co, CoStore, tile, bias, act, want16, want32):
 def fake_wg(self, x, dy, scale):
     k = (id(self), "w")
     if k in cache:
-        packed, ldo = cache[k]
-        ops.emit_grad(self.group, packed, self.wg, self.gspec, ldo, 1.0 / scale)
+        out = cache[k]
+        ops.emit_grad(self.group, out, self.wg, self.gspec, out.ld, 1.0 / scale)
         return
     M = x.shape[0]
-    packed, ldo = ops.run_wgrad(dy, x, M, 1, 1, self.np_, 1, 1, self.kp, 1, 1, 0, hold=ops._hold_of(self))
-    cache[k] = (packed, ldo)
-    ops.emit_grad(self.group, packed, self.wg, self.gspec, ldo, 1.0 / scale)
+    out = cache[k] = ops.run_wgrad(dy, x, M, 1, 1, self.np_, 1, 1, self.kp, 1, 1, 0, hold=ops._hold_of(self))
+    ops.emit_grad(self.group, out, self.wg, self.gspec, out.ld, 1.0 / scale)
 def timed(run, n=60):
     for _ in range(8): run()
     torch.cuda.synchronize(); t0 = time.perf_counter()
