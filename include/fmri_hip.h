@@ -604,6 +604,24 @@ int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream);
 int fmri_gan_head_bwd(const float* logit, int ldl, int B, void* dlogit, int ldg, float gscale, const float* norm,
                       void* stream);
 int fmri_feat_mse_bwd(const void* feat, int B, int F, void* dfeat, float gscale, const float* norm, void* stream);
+/* fmri_feat_mse / fmri_feat_mse_bwd for WIDE feature rows (the raw output of discriminator block 1 or 2, recon_level
+ * 1 / 2: F = 131 072 / 65 536 at 64 px).  feat: fp16 [3B][F] (orig | pred | sampled rows), F a multiple of 8.  The unit of
+ * work is a (row, column chunk) pair of fmri_feat_mse_wide_chunk() halves and the grid is sized from the device's CU
+ * count, not from B.
+ *   fmri_feat_mse_wide: per-chunk fp32 partial sums go to ws (>= fmri_feat_mse_wide_ws_floats(B, F) floats, caller-owned;
+ *     FMRI_E_WORKSPACE if smaller) and are folded in index order by a one-block launch: mse_rows[b] (optional) = row
+ *     sums, *mse_total (optional) += their sum.  No atomics: the bits are a function of (feat, B, F) alone, with
+ *     fmri_set_deterministic on or off, whatever the grid.
+ *   fmri_feat_mse_bwd_wide: dfeat rows [0, B) = +d, [B, 2B) = -d with d = fp16((f_o - f_p) * gscale * (*norm)) -- the
+ *     bits fmri_feat_mse_bwd writes; rows [2B, 3B) are written (zeros) only if write_zero_rows, otherwise left untouched
+ *     (a caller whose next kernel does not read them).
+ * Enqueue-only, no allocation, no host sync. */
+int fmri_feat_mse_wide_chunk(void);
+int64_t fmri_feat_mse_wide_ws_floats(int B, int F);
+int fmri_feat_mse_wide(const void* feat, int B, int F, float* mse_rows, float* mse_total, float* ws, int64_t ws_floats,
+                       void* stream);
+int fmri_feat_mse_bwd_wide(const void* feat, int B, int F, void* dfeat, float gscale, const float* norm,
+                           int write_zero_rows, void* stream);
 /* out = a * (*a_dev) * x + b * y   (fp16 tensors, fp32 math; y and a_dev may be NULL) */
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream);

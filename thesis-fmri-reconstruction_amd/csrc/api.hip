@@ -1113,6 +1113,20 @@ int fmri_feat_mse_bwd(const void* feat, int B, int F, void* dfeat, float gscale,
     if (!feat || !dfeat || (F & 7)) return FMRI_E_BADARG;
     return feat_mse_bwd_launch((const half_t*)feat, B, F, (half_t*)dfeat, gscale, norm, S(stream));
 }
+int fmri_feat_mse_wide_chunk(void) { return feat_mse_wide_chunk(); }
+int64_t fmri_feat_mse_wide_ws_floats(int B, int F) { return (B < 1 || F < 8) ? 0 : feat_mse_wide_ws_floats(B, F); }
+int fmri_feat_mse_wide(const void* feat, int B, int F, float* mse_rows, float* mse_total, float* ws, int64_t ws_floats,
+                       void* stream) {
+    if (!feat || !ws || B < 1 || F < 8 || (F & 7)) return FMRI_E_BADARG;
+    if (ws_floats < feat_mse_wide_ws_floats(B, F)) return FMRI_E_WORKSPACE;
+    return feat_mse_wide_launch((const half_t*)feat, B, F, mse_rows, mse_total, ws, S(stream));
+}
+int fmri_feat_mse_bwd_wide(const void* feat, int B, int F, void* dfeat, float gscale, const float* norm,
+                           int write_zero_rows, void* stream) {
+    if (!feat || !dfeat || B < 1 || F < 8 || (F & 7)) return FMRI_E_BADARG;
+    return feat_mse_bwd_wide_launch((const half_t*)feat, B, F, (half_t*)dfeat, gscale, norm, write_zero_rows ? 1 : 0,
+                                    S(stream));
+}
 int fmri_pixel_sq(const void* x, const void* xt, int64_t npix, int C, int Cp, float* total, void* dxt, float gscale,
                   void* stream) {
     if (!x || !xt) return FMRI_E_BADARG;

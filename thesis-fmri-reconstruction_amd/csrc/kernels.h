@@ -249,6 +249,13 @@ int latent_bwd_launch(const float* head, const float* eps, const float* dz, int 
 int feat_mse_launch(const half_t* feat, int B, int F, float* mse_rows, float* mse_total, hipStream_t st);
 int feat_mse_bwd_launch(const half_t* feat, int B, int F, half_t* dfeat, float gscale, const float* norm,
                         hipStream_t st);
+// featloss.hip: the feature-matching term for wide rows (recon_level 1 / 2), (row, column chunk) tasks on a CU-sized grid
+int feat_mse_wide_chunk();
+int64_t feat_mse_wide_ws_floats(int B, int F);
+int feat_mse_wide_launch(const half_t* feat, int B, int F, float* mse_rows, float* mse_total, float* ws,
+                         hipStream_t st);
+int feat_mse_bwd_wide_launch(const half_t* feat, int B, int F, half_t* dfeat, float gscale, const float* norm,
+                             int zero_rows, hipStream_t st);
 int pixel_sq_launch(const half_t* x, const half_t* xt, int64_t npix, int C, int Cp, float* total, half_t* dxt,
                     float gscale, hipStream_t st);
 int gan_head_launch(const float* logit, int ldl, int B, float* prob, float* scal, int parts, hipStream_t st);

@@ -86,6 +86,8 @@ _SIGS = {
     "fmri_latent_bwd": [_p, _p, _p, _i, _f, _f, _p, _i, _i, _f, _p, _p, _i, _p],
     "fmri_feat_mse": [_p, _i, _i, _p, _p, _p],
     "fmri_feat_mse_bwd": [_p, _i, _i, _p, _f, _p, _p],
+    "fmri_feat_mse_wide": [_p, _i, _i, _p, _p, _p, _l, _p],
+    "fmri_feat_mse_bwd_wide": [_p, _i, _i, _p, _f, _p, _i, _p],
     "fmri_pixel_sq": [_p, _p, _l, _i, _i, _p, _p, _f, _p],
     "fmri_gan_head": [_p, _i, _i, _p, _p, _p],
     "fmri_gan_head_bwd": [_p, _i, _i, _p, _i, _f, _p, _p],
@@ -163,7 +165,7 @@ EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_
                              "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
                              "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes", "fmri_images_u8_ws_bytes",
                              "fmri_images_u8_out_bytes",
-                             "fmri_tensor_stats_ws_bytes"])
+                             "fmri_tensor_stats_ws_bytes", "fmri_feat_mse_wide_chunk", "fmri_feat_mse_wide_ws_floats"])
 
 _lib = None
 
@@ -211,6 +213,10 @@ def load():
     lib.fmri_images_u8_out_bytes.argtypes = [_i, _i, _i, _i, _i, _i, _i]
     lib.fmri_tensor_stats_ws_bytes.restype = _i
     lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
+    lib.fmri_feat_mse_wide_chunk.restype = _i
+    lib.fmri_feat_mse_wide_chunk.argtypes = []
+    lib.fmri_feat_mse_wide_ws_floats.restype = _l
+    lib.fmri_feat_mse_wide_ws_floats.argtypes = [_i, _i]
     _lib = lib
     return lib
 

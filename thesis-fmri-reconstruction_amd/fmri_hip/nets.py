@@ -441,6 +441,13 @@ class DiscriminatorNet(_JoinedBackward):
     def all_bns(self):
         return self.bns + [self.fc_bn]
 
+    def reads_zero_tail(self) -> bool:
+        """Whether the two-stream ``backward`` reads the ``zero_tail`` rows of stream B's starting cotangent (the sampled
+        images' rows), i.e. whether the caller has to write those zeros: the join layer's data gradient skips them
+        unless it runs with the BatchNorm-backward epilogue (ops._EPI_BWD; block 1's data gradient has none above it)."""
+        from . import ops
+        return self.level > 1 and ops._EPI_BWD
+
     def forward(self, x16: torch.Tensor, train_stats: bool = True, conv_updates: int = 2, fc_updates: int = 1,
                 head: bool = True):
         """x16 [3B,H,W,8] = cat(orig, predicted, sampled).  One pass produces both reference outputs:
@@ -498,18 +505,21 @@ class DiscriminatorNet(_JoinedBackward):
                  train_b: bool = False, stack: Optional[torch.Tensor] = None, zero_tail: int = 0):
         """Two cotangent streams through one saved forward:
              A: d(sum bce)/d logit  (dlogit16 [3B,8], scale_a) -- accumulates discriminator grads if ``train``
-             B: d(sum mse)/d raw conv-3 features (dfeat16 [3B,h,w,c], scale_b) -- data gradient only
+             B: d(sum mse)/d raw features of block ``recon_level`` (dfeat16 [3B,h,w,c], scale_b) -- data gradient only
            ``stack`` [6B,h,w,c]: the buffer ``dfeat16`` is the second half of; ``zero_tail``: that many last rows of
            ``dfeat16`` are exact zeros (both from steps._start_cotangents).
+           With both streams and ``recon_level`` L < 3, A runs alone through the head and blocks 3 .. L+1 (one-stream
+           BatchNorm backward, its weight gradients) and B joins at the BatchNorm backward into block L's raw output:
+           that pass writes A's rows into the first half of ``stack``; from block L down both streams run together.
            Returns (dimg_A, dimg_B): cotangents w.r.t. input images ``img_rows`` (None if not requested)."""
         n3 = ctx["x"].shape[0]
         streams = []
-        top = 2                             # block whose raw output the cotangents enter at (index into convs / raws)
+        join = self.level - 1               # block whose raw output stream B enters at (index into convs / raws)
+        top = 2                             # block whose raw output the first cotangent enters at
         if dlogit16 is None and dfeat16 is not None:
-            top = self.level - 1             # a 'REC' call alone: the feature cotangent enters at block ``recon_level``
-        elif dfeat16 is not None and self.level != 3:
-            raise NotImplementedError("two cotangent streams through one discriminator pass (the fused steps) are "
-                                      "implemented for recon_level=3; other levels run through the module API")
+            top = join                       # a 'REC' call alone: the feature cotangent enters at block ``recon_level``
+        both = dlogit16 is not None and dfeat16 is not None
+        late = None                          # stream B while stream A is still alone above the join
         if dlogit16 is not None:
             if train:
                 self.fc3.wgrad(ctx["hfc"], dlogit16, scale_a)
@@ -527,13 +537,17 @@ class DiscriminatorNet(_JoinedBackward):
             if stack is not None and stack.shape[0] != 2 * n3:
                 stack = None
             draw3, _ = self.bns[2].backward(ctx["raws"][2], d3, ctx["svs"][2], True, scale_a if train else None,
-                                            out=stack[:n3].reshape(ctx["raws"][2].shape) if stack is not None else None)
+                                            out=stack[:n3].reshape(ctx["raws"][2].shape)
+                                            if (stack is not None and join == 2) else None)
             streams.append(dict(d=draw3, scale=scale_a, train=train, img=img_streams[0]))
         else:
             stack = None
         if dfeat16 is not None:
-            streams.append(dict(d=dfeat16.reshape(ctx["raws"][top].shape), scale=scale_b, train=train_b,
-                                img=img_streams[1]))
+            sb = dict(d=dfeat16.reshape(ctx["raws"][join].shape), scale=scale_b, train=train_b, img=img_streams[1])
+            if both and join < 2:
+                late = sb
+            else:
+                streams.append(sb)
         S = len(streams)
         if S > 1 and stack is not None:
             d = stack.reshape((2 * n3,) + tuple(ctx["raws"][2].shape[1:]))
@@ -542,8 +556,10 @@ class DiscriminatorNet(_JoinedBackward):
         rows = lambda t, i: t[i * n3:(i + 1) * n3]
         # conv3 .. conv1 (from block ``top`` down)
         for li in range(top, -1, -1):
-            def wgrads(li=li, d=d):             # (issued after the layer's data gradient: see EncoderNet._backward)
-                for si, s in enumerate(streams):
+            S = len(streams)
+            def wgrads(li=li, d=d, active=tuple(streams)):
+                # (issued after the layer's data gradient: see EncoderNet._backward)
+                for si, s in enumerate(active):
                     if s["train"]:
                         self.convs[li].wgrad(ctx["acts"][li], rows(d, si), s["scale"])
             _, hi, wi, _ = ctx["acts"][li].shape
@@ -553,10 +569,11 @@ class DiscriminatorNet(_JoinedBackward):
                 # the data gradient's epilogue masks with block li-1's ReLU and reduces its BatchNorm backward sums, one
                 # statistics group per cotangent stream (all read the same saved forward tensor)
                 epi = _bwd_epi(bn=self.bns[li - 1], x=ctx["raws"][li - 1], groups=[(0, ctx["svs"][li - 1])] * S)
-                ztail = zero_tail if (li == 2 and dfeat16 is not None and S > 1) else 0
+                ztail = zero_tail if (li == join and both and S > 1) else 0
                 if ztail and epi is None and d.shape[0] == S * n3:
-                    # stream B enters at conv3's raw output with exact zeros on the sampled images' rows -- the last rows
-                    # of the stack: conv3's data gradient (per image) skips them, its result there is zero
+                    # stream B enters at block ``recon_level``'s raw output with exact zeros on the sampled images' rows
+                    # -- the last rows of the stack: that block's data gradient (per image) skips them, its result there
+                    # is zero
                     live = d.shape[0] - ztail
                     dact = torch.empty(d.shape[0], hi, wi, self.convs[li].cinp, dtype=torch.float16, device=d.device)
                     self.convs[li].dgrad(d[:live], hi, wi, out=dact[:live])
@@ -565,6 +582,19 @@ class DiscriminatorNet(_JoinedBackward):
                     dact = self.convs[li].dgrad(d, hi, wi, bn_bwd=epi)
                 wgrads()
                 stat = self.convs[li].take_bwd_stats()
+                if late is not None and li - 1 == join:
+                    # stream B joins here: A's BatchNorm backward into block ``recon_level``'s raw output writes the first
+                    # half of the caller's stack, whose second half already holds B (no concatenation copy)
+                    raw_j = ctx["raws"][join]
+                    use = stack is not None
+                    dn, _ = self.bns[join].backward(raw_j, dact, ctx["svs"][join], True,
+                                                    streams[0]["scale"] if streams[0]["train"] else None,
+                                                    out=stack[:n3].reshape(raw_j.shape) if use else None, stat=stat)
+                    d = (stack.reshape((2 * n3,) + tuple(raw_j.shape[1:])) if use
+                         else torch.cat([dn, late["d"]], 0))
+                    streams.append(late)
+                    late = None
+                    continue
                 dn = torch.empty_like(dact)
                 if S == 2 and not streams[1]["train"]:
                     # both streams in one pass over the saved forward tensor (gamma / beta gradients from stream A only)
@@ -594,7 +624,17 @@ class DiscriminatorNet(_JoinedBackward):
                 if nd is None:
                     dacts.append(None)
                     continue
-                dacts.append(self.convs[0].dgrad(rows(d, si)[nd], hi, wi, relu_y=a0[nd]))
+                ds = rows(d, si)[nd]
+                live = ds.shape[0] - zero_tail
+                if both and join == 0 and si == 1 and nd.stop == n3 and 0 < live < ds.shape[0]:
+                    # recon_level 1: stream B entered at block 1's raw output, this is the join layer's data gradient --
+                    # the sampled images' rows (the last of the stack) are exact zeros and are skipped
+                    da = torch.empty(ds.shape[0], hi, wi, self.convs[0].cinp, dtype=torch.float16, device=d.device)
+                    self.convs[0].dgrad(ds[:live], hi, wi, out=da[:live], relu_y=a0[nd][:live])
+                    da[live:].zero_()
+                    dacts.append(da)
+                else:
+                    dacts.append(self.convs[0].dgrad(ds, hi, wi, relu_y=a0[nd]))
                 masked[si] = self.convs[0].act_applied
         outs = []
         for si, s in enumerate(streams):

@@ -126,7 +126,13 @@ class _GanStepBase(_StepBase):
         F = feat[0].numel()
         prob = torch.empty(3 * B, dtype=torch.float32, device=dev)
         lib.call("fmri_gan_head_parts", _P(logit32), 1, B, _P(prob), _P(self.scal), self._dis_parts())
-        lib.call("fmri_feat_mse", _P(feat), B, F, None, _P(self._slot(S_MSE)))
+        if self.dis.level == 3:
+            lib.call("fmri_feat_mse", _P(feat), B, F, None, _P(self._slot(S_MSE)))
+        else:
+            # recon_level 1 / 2: rows of 131 072 / 65 536 halves at 64 px -- the chunked head (csrc/featloss.hip)
+            n = lib.load().fmri_feat_mse_wide_ws_floats(B, F)
+            ws = torch.empty(n, dtype=torch.float32, device=dev)
+            lib.call("fmri_feat_mse_wide", _P(feat), B, F, None, _P(self._slot(S_MSE)), _P(ws), n)
         lib.call("fmri_pixel_sq", _P(x16), _P(xt16), B * H * W, 3, 8, _P(self._slot(S_NLE)), None, 1.0)
         if not getattr(self, "_defer_loss_reduce", False):
             self.dd.all_reduce(self.scal[:N_REDUCED])
@@ -156,8 +162,9 @@ class _GanStepBase(_StepBase):
         return dlogit16
 
     def _start_cotangents(self, B):
-        """fp16 starting cotangents of stream A (logits) and stream B (raw conv-3 features), and what
-        ``DiscriminatorNet.backward`` may know about the latter (its ``stack`` / ``zero_tail`` arguments)."""
+        """fp16 starting cotangents of stream A (logits) and stream B (the raw features of discriminator block
+        ``recon_level``: shapes are taken from ``fw["feat"]``), and what ``DiscriminatorNet.backward`` may know about the
+        latter (its ``stack`` / ``zero_tail`` arguments)."""
         feat = self.fw["feat"]
         dev = feat.device
         dlogit16 = self._logit_cotangent(B)
@@ -165,7 +172,12 @@ class _GanStepBase(_StepBase):
         # discriminator's conv backward (DiscriminatorNet fills the first half with stream A: no concatenation copy)
         stack = torch.empty((2 * feat.shape[0],) + tuple(feat.shape[1:]), dtype=feat.dtype, device=dev)
         dfeat16 = stack[feat.shape[0]:]
-        lib.call("fmri_feat_mse_bwd", _P(feat), B, feat[0].numel(), _P(dfeat16), self.sc.b, _P(self._slot(S_NB)))
+        if self.dis.level == 3:
+            lib.call("fmri_feat_mse_bwd", _P(feat), B, feat[0].numel(), _P(dfeat16), self.sc.b, _P(self._slot(S_NB)))
+        else:
+            # the sampled images' zero rows are written only if the join layer's data gradient reads them
+            lib.call("fmri_feat_mse_bwd_wide", _P(feat), B, feat[0].numel(), _P(dfeat16), self.sc.b,
+                     _P(self._slot(S_NB)), 1 if self.dis.reads_zero_tail() else 0)
         # (zero_tail: the rows of the sampled images are exact zeros)
         return dlogit16, dfeat16, dict(stack=stack, zero_tail=B)
 
@@ -206,8 +218,14 @@ class Stage1Step(_GanStepBase):
 
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
-                 monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None):
-        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+                 monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None,
+                 recon_level: int = 3):
+        """``recon_level`` (1, 2 or 3; the scripts' ``--recon_level``, train_vgan_stage1.py:62,237): the discriminator
+        block whose raw convolution output is the feature tensor of the ``mse`` term.  The parameters, and so
+        ``state_dict()``, are the same at every level.  Below 3 the feature cotangent joins the logit cotangent below the
+        top block (DiscriminatorNet.backward) and the loss head runs on the chunked kernels of csrc/featloss.hip; 3 (the
+        default) issues the launches it always did.
+        ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``); the epoch-end block of the scripts -- lr decay,
         margin / equilibrium / lambda_mse decays with their clamps -- then happens on the device, as the first launch of
         the step whose batch opens a new epoch, recorded steps included; ``self.hp`` keeps the base values.
@@ -233,7 +251,7 @@ class Stage1Step(_GanStepBase):
         self.enc = EncoderNet(cfg, device)
         self.dec = DecoderNet(cfg, device, self.enc.size)
         self.dec.fc_bn.enable_lazy_running()
-        self.dis = DiscriminatorNet(cfg, device)
+        self.dis = DiscriminatorNet(cfg, device, recon_level)
         self._init_common(device, hp, scales, distributed, sync_bn, (self.enc, self.dec, self.dis))
         self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self._init_rng(rng, feed)
@@ -558,7 +576,9 @@ class CognitiveStep(_GanStepBase):
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
                  rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None):
-        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+        """The discriminator keeps ``recon_level`` 3: the Stage-II / Stage-III scripts build theirs with the default
+        (train_vgan_stage2.py:213, train_vgan_stage3.py:231), so there is no such option here.
+        ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule`` / ``log``: device-side epoch-end schedule and per-step training log (see Stage1Step).
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(fmri, image)`` then draws ``eps``, ``z_p`` and -- where the teacher
         samples (stage 2, mode 'vae-gan') -- ``eps_teacher`` on the device (see Stage1Step).

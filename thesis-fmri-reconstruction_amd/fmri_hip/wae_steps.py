@@ -338,15 +338,17 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
                  mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None):
-        """``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
+                 schedule=None, log=None, recon_level: int = 3):
+        """``recon_level``: the script's ``--recon_level`` (wae_vgan_stage1.py:71,199), as in Stage1Step.
+        ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
         (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step).
         ``schedule`` / ``log``: see Stage1Step.  By default the lr schedule covers what ``set_hyper(lr=)`` covers:
         encoder, decoder and image discriminator; the latent discriminator (registered fourth) keeps its rate.  The
         script itself rebinds ``lr_discriminator`` to the LATENT discriminator's scheduler (wae_vgan_stage1.py:246-250), so
         there the image discriminator's rate never decays and the latent discriminator's does:
         ``EpochSchedule(..., lr_mask=(True, True, False, True))`` reproduces that literally."""
-        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng, feed=feed)
+        super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng, feed=feed,
+                         recon_level=recon_level)
         hp = self.hp
         self.lam = lam
         self.torch14 = torch14_zero_grad
