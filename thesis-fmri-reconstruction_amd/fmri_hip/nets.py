@@ -10,14 +10,14 @@ saved forward pass (the two-stream trick of SURVEY 8a-14).
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import ctypes
 import os
 
 import torch
 
-from . import lib
+from . import lib, ops
 from .ops import (ACT_NONE, ACT_RELU, ACT_TANH, BatchNorm, ConvLayer, DenseLayer, act_backward, join_side, pad8,
                   repack_group)
 from .params import (ArchConfig, FlatGroup, cognitive_encoder_spec, decoder_spec, discriminator_spec, encoder_spec,
@@ -81,24 +81,21 @@ class FusedHeads:
         if self.direct:
             self.dense.wgrad(h16, dhead16, scale)        # side stream, accumulates into the flat gradient buffer
             self.dense.bias_grad(dhead16, scale)
-            if need_dgrad:
-                dh, _ = self.dense.dgrad(dhead16)
-                return dh
+        else:
+            self._sync()
+            g = self.group.grads
+            z = self.z
+            self.gw.zero_()
+            self.dense._wgrad(h16, dhead16, scale)      # current stream: gw is read right below
+            g["l_mu.weight"].add_(self.gw[:z])
+            g["l_var.weight"].add_(self.gw[z:])
+            bs = dhead16.float().sum(0) * (1.0 / scale)
+            g["l_mu.bias"].add_(bs[:z])
+            g["l_var.bias"].add_(bs[z:2 * z])
+        if not need_dgrad:
             return None
-        self._sync()
-        g = self.group.grads
-        z = self.z
-        self.gw.zero_()
-        self.dense._wgrad(h16, dhead16, scale)      # current stream: gw is read right below
-        g["l_mu.weight"].add_(self.gw[:z])
-        g["l_var.weight"].add_(self.gw[z:])
-        bs = dhead16.float().sum(0) * (1.0 / scale)
-        g["l_mu.bias"].add_(bs[:z])
-        g["l_var.bias"].add_(bs[z:2 * z])
-        if need_dgrad:
-            dh, _ = self.dense.dgrad(dhead16)
-            return dh
-        return None
+        dh, _ = self.dense.dgrad(dhead16)
+        return dh
 
 
 _MLP_ON = os.environ.get("FMRI_MLP") != "off"        # fused latent-discriminator kernels (csrc/mlp.hip)
@@ -106,8 +103,119 @@ _MLP_ON = os.environ.get("FMRI_MLP") != "off"        # fused latent-discriminato
 
 def _bwd_epi(**kw):
     """``bn_bwd`` argument of ``ConvLayer.dgrad`` when the BatchNorm-backward epilogue is switched on (ops._EPI_BWD)."""
-    from . import ops
     return kw if ops._EPI_BWD else None
+
+
+class ConvBlock:
+    """One conv / deconv + BatchNorm(+ ReLU) block: the two steps every network writes the same way.  The BatchNorm half
+    of the forward stays with the networks (``BatchNorm.forward`` per call against the decoder's ``forward_groups``
+    over its call groups: with SyncBN these exchange and finalize differently)."""
+
+    def __init__(self, conv: ConvLayer, bn: BatchNorm):
+        self.conv, self.bn = conv, bn
+
+    def conv_forward(self, h: torch.Tensor, groups: int = 1, keep_raw: bool = False):
+        """The convolution of the block on ``h`` -> (tensor, whether it already is the BatchNorm's output).
+        eval: the BatchNorm rides in the convolution's epilogue where its kernel has one (no raw tensor then), unless
+        the caller needs the raw tensor (``keep_raw``); train: the epilogue is asked for the batch statistics of each
+        of ``groups`` equal image ranges (``conv.take_stats(g)``)."""
+        conv, bn = self.conv, self.bn
+        if bn.eval_mode and not bn.perm and not keep_raw:
+            out = conv.forward(h, affine=bn.eval_affine())
+            return out, conv.aff_applied
+        return conv.forward(h, bn_groups=0 if bn.eval_mode else groups), False
+
+    def dgrad_below(self, draw: torch.Tensor, below: "ConvBlock", raw_below, groups, hi: int, wi: int):
+        """Data gradient of this block's convolution into the block ``below`` -> (cotangent of below's activation,
+        ``take_bwd_stats()``).  With the BatchNorm-backward epilogue on, the kernel masks with below's ReLU and reduces
+        its BatchNorm backward sums: one statistics group (first image of ``raw_below``, BNSaved) per cotangent block."""
+        d = self.conv.dgrad(draw, hi, wi, bn_bwd=_bwd_epi(bn=below.bn, x=raw_below, groups=groups))
+        return d, self.conv.take_bwd_stats()
+
+
+class Cot(NamedTuple):
+    """One cotangent block of B rows through a saved forward pass: ``g`` = forward call group whose activations it
+    belongs to, ``scale`` = loss scale it carries, ``train`` = accumulate parameter gradients, ``img`` = its image
+    gradient is wanted (discriminator), ``need_dz`` = its latent gradient is wanted (decoder)."""
+    g: int
+    scale: float
+    train: bool
+    img: bool = True
+    need_dz: bool = False
+
+
+def _rows(t: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
+    """Rows lo .. hi-1 of ``t``; ``t`` itself where that is all of it (one cotangent block, one forward group: the
+    backward passes of the encoder and the discriminator build no views)."""
+    return t if lo == 0 and hi == t.shape[0] else t[lo:hi]
+
+
+def _bn_backward_blocks(bn: BatchNorm, raw_all, sv_all, cots, B: int, d_all, draw_all, stat):
+    """BatchNorm backward of every cotangent block of one layer: ``d_all`` -> ``draw_all`` ([E*B, ...] both), block e
+    through rows g*B.. of ``raw_all`` and ``sv_all[g]``.  Two adjacent blocks through the same forward activations, at
+    most one of them training, are one two-stream pass (the gamma / beta gradients come from whichever trains).  With
+    SyncBN the reductions of all blocks run first (phase 1) into one [2E][C] buffer that is exchanged ONCE, then the
+    apply passes (phase 2).  The discriminator's two streams are the pair (A, B): paired with the parameter gradients
+    from A whenever B does not train.  Its callers never train B next to A (the fused steps pass train=True,
+    train_b=False; the module API passes one stream), so the pairing with the gradients from B, and the single
+    exchange for two training streams, are the decoder's cases only."""
+    E = len(cots)
+    sync = bn.reducer is not None
+    sums_all = torch.empty(2 * E, bn.C, dtype=torch.float32, device=d_all.device) if sync else None
+    for phase in ((1, 2) if sync else (3,)):
+        if phase == 2:
+            bn.reducer(sums_all)
+        e = 0
+        while e < E:
+            en = cots[e]
+            nx = cots[e + 1] if e + 1 < E else None
+            sm = sums_all[2 * e:] if sync else None
+            if nx is not None and nx.g == en.g and not (nx.train and en.train):
+                ps = 1 if nx.train else 0
+                tr = nx if nx.train else en
+                bn.backward2(_rows(raw_all, en.g * B, (en.g + 1) * B), _rows(d_all, e * B, (e + 2) * B), sv_all[en.g],
+                             True, tr.scale if tr.train else None, out=_rows(draw_all, e * B, (e + 2) * B),
+                             param_stream=ps, stat=stat, stat_group=e, sums=sm[:4] if sync else None, phase=phase)
+                e += 2
+            else:
+                bn.backward(_rows(raw_all, en.g * B, (en.g + 1) * B), _rows(d_all, e * B, (e + 1) * B), sv_all[en.g],
+                            True, en.scale if en.train else None, out=_rows(draw_all, e * B, (e + 1) * B), stat=stat,
+                            stat_group=e, sums=sm[:2] if sync else None, phase=phase)
+                e += 1
+
+
+def _wgrad_runs(cots):
+    """Weight-gradient runs [(first block, blocks, first forward group, scale)]: consecutive training blocks with the same
+    scale through consecutive forward groups are one launch over all their rows (2 x 256 images as one 512-image launch:
+    638 vs 806 us for the decoder's four conv layers, tools/probes/wgrad_n512.py).  The discriminator's streams all go
+    through group 0 and never merge: one run per training stream."""
+    runs, e, E = [], 0, len(cots)
+    while e < E:
+        if not cots[e].train:
+            e += 1
+            continue
+        f = e
+        while (f + 1 < E and cots[f + 1].train and cots[f + 1].scale == cots[e].scale
+               and cots[f + 1].g == cots[f].g + 1):
+            f += 1
+        runs.append((e, f - e + 1, cots[e].g, cots[e].scale))
+        e = f + 1
+    return runs
+
+
+def _wgrad_blocks(layer, x_all, d_all, runs, B: int):
+    """Issue ``layer``'s weight gradient (side stream) for every run of ``_wgrad_runs``."""
+    for e0, n, g0, scale in runs:
+        layer.wgrad(_rows(x_all, g0 * B, (g0 + n) * B), _rows(d_all, e0 * B, (e0 + n) * B), scale)
+
+
+def _dgrad_live(conv: ConvLayer, d: torch.Tensor, live: int, hi: int, wi: int, relu_y=None):
+    """Data gradient of ``d`` whose rows from ``live`` on are exact zeros: the kernel (per image) skips them, the result
+    there is zero."""
+    out = torch.empty(d.shape[0], hi, wi, conv.cinp, dtype=torch.float16, device=d.device)
+    conv.dgrad(d[:live], hi, wi, out=out[:live], relu_y=relu_y)
+    out[live:].zero_()
+    return out
 
 
 def refresh_net(net):
@@ -153,12 +261,11 @@ class EncoderNet(_JoinedBackward):
         self.cfg = cfg
         self.group = FlatGroup(encoder_spec(cfg, channel_in), device)
         g = self.group
-        self.convs, self.bns = [], []
+        self.blocks = []
         cin = channel_in
         for i, c in enumerate(cfg.encoder_channels[:3]):
-            self.convs.append(ConvLayer(g, f"conv.{i}.conv.weight", None, "conv", cin, c, cfg.kernel_size, cfg.stride,
-                                        cfg.padding))
-            self.bns.append(BatchNorm(g, f"conv.{i}.bn.", c))
+            self.blocks.append(ConvBlock(ConvLayer(g, f"conv.{i}.conv.weight", None, "conv", cin, c, cfg.kernel_size,
+                                                   cfg.stride, cfg.padding), BatchNorm(g, f"conv.{i}.bn.", c)))
             cin = c
         self.size = cin
         hw = cfg.fc_input * cfg.fc_input
@@ -167,7 +274,7 @@ class EncoderNet(_JoinedBackward):
         self.heads = FusedHeads(g, cfg.fc_output, cfg.latent_dim)
 
     def all_bns(self):
-        return self.bns + [self.fc_bn]
+        return [blk.bn for blk in self.blocks] + [self.fc_bn]
 
     def forward(self, x16: torch.Tensor, train_stats: bool = True, updates: Optional[int] = None):
         """x16 [B,H,W,8] fp16 -> (head32 [B,2z], ctx).  ``updates`` = number of running-stat updates this call
@@ -175,18 +282,12 @@ class EncoderNet(_JoinedBackward):
         acts, raws, svs = [x16], [], []
         h = x16
         upd = (1 if train_stats else 0) if updates is None else updates
-        for conv, bn in zip(self.convs, self.bns):
-            if bn.eval_mode and not bn.perm:
-                # eval: the BatchNorm rides in the convolution's epilogue where its kernel has one (no raw tensor then)
-                out = conv.forward(h, affine=bn.eval_affine())
-                if conv.aff_applied:
-                    raws.append(None); svs.append(None); acts.append(out)
-                    h = out
-                    continue
-                raw = out
+        for blk in self.blocks:
+            raw, done = blk.conv_forward(h)
+            if done:
+                h, raw, sv = raw, None, None
             else:
-                raw = conv.forward(h, bn_groups=0 if bn.eval_mode else 1)
-            h, sv = bn.forward(raw, relu=True, updates=upd, stat_acc=conv.take_stats())
+                h, sv = blk.bn.forward(raw, relu=True, updates=upd, stat_acc=blk.conv.take_stats())
             raws.append(raw)
             svs.append(sv)
             acts.append(h)
@@ -212,18 +313,19 @@ class EncoderNet(_JoinedBackward):
         dflat, _ = self.fc.dgrad(draw_fc)
         d = dflat.reshape(ctx["acts"][3].shape)
         stat = None
+        one, n = (Cot(0, scale, True),), d.shape[0]
+        raws, svs = ctx["raws"], ctx["svs"]
         # Issue order inside a layer: the data gradient (main stream: the next link of the backward chain) BEFORE the weight
         # gradient (side stream) -- both become ready at the same moment, and the one issued first gets the free CUs first
         # (same-call A/B of the order, three pairs: 6.540-6.546 ms against 6.562-6.593 per step).
         for i in (2, 1, 0):
-            draw, _ = self.bns[i].backward(ctx["raws"][i], d, ctx["svs"][i], True, scale, stat=stat)
+            blk = self.blocks[i]
+            draw = torch.empty_like(d)
+            _bn_backward_blocks(blk.bn, raws[i], [svs[i]], one, n, d, draw, stat)
             if i > 0:
                 _, hi, wi, _ = ctx["acts"][i].shape
-                # the data gradient's epilogue masks with block i-1's ReLU and reduces its BatchNorm backward sums
-                d = self.convs[i].dgrad(draw, hi, wi, bn_bwd=_bwd_epi(bn=self.bns[i - 1], x=ctx["raws"][i - 1],
-                                                                      groups=[(0, ctx["svs"][i - 1])]))
-                stat = self.convs[i].take_bwd_stats()
-            self.convs[i].wgrad(ctx["acts"][i], draw, scale)
+                d, stat = blk.dgrad_below(draw, self.blocks[i - 1], raws[i - 1], [(0, svs[i - 1])], hi, wi)
+            blk.conv.wgrad(ctx["acts"][i], draw, scale)
 
 
 class CognitiveEncoderNet(_JoinedBackward):
@@ -262,16 +364,14 @@ class DecoderNet(_JoinedBackward):
         self.fc = DenseLayer(g, "fc.0.weight", None, cfg.latent_dim, hw * size, out_perm=(size, hw))
         self.fc_bn = BatchNorm(g, "fc.1.", hw * size, perm=(size, hw))
         chans = [(size, size), (size, cfg.decoder_channels[1]), (cfg.decoder_channels[1], cfg.decoder_channels[2])]
-        self.deconvs, self.bns = [], []
-        for i, (ci, co) in enumerate(chans):
-            self.deconvs.append(ConvLayer(g, f"conv.{i}.conv.weight", None, "deconv", ci, co, cfg.kernel_size,
-                                          cfg.stride, cfg.padding, 1 if cfg.output_pad_dec[i] else 0))
-            self.bns.append(BatchNorm(g, f"conv.{i}.bn.", co))
+        self.blocks = [ConvBlock(ConvLayer(g, f"conv.{i}.conv.weight", None, "deconv", ci, co, cfg.kernel_size, cfg.stride,
+                                           cfg.padding, 1 if cfg.output_pad_dec[i] else 0),
+                                 BatchNorm(g, f"conv.{i}.bn.", co)) for i, (ci, co) in enumerate(chans)]
         self.c3 = ConvLayer(g, "conv.3.0.weight", "conv.3.0.bias", "conv", cfg.decoder_channels[2],
                             cfg.decoder_channels[3], 5, 1, 2)
 
     def all_bns(self):
-        return [self.fc_bn] + self.bns
+        return [self.fc_bn] + [blk.bn for blk in self.blocks]
 
     def forward(self, z16: torch.Tensor, groups: int, out: Optional[torch.Tensor] = None, train_stats: bool = True,
                 stat_order=None, zscale: Optional[torch.Tensor] = None):
@@ -293,23 +393,17 @@ class DecoderNet(_JoinedBackward):
         sv_fc = self.fc_bn.forward_groups(grows(raw_fc), True, upd, grows(act_fc), [None] * groups, order, in_scales=ins)
         h = act_fc.reshape(GB, f, f, self.size0)
         acts, raws, svs = [h], [], []
-        for dc, bn in zip(self.deconvs, self.bns):
-            if bn.eval_mode and not bn.perm:
-                # eval: the BatchNorm rides in the transposed convolution's epilogue where its kernel has one
-                out_e = dc.forward(h, affine=bn.eval_affine())
-                if dc.aff_applied:
-                    raws.append(None); svs.append([None] * groups); acts.append(out_e)
-                    h = out_e
-                    continue
-                raw = out_e
+        for blk in self.blocks:
+            raw, done = blk.conv_forward(h, groups)
+            if done:
+                h, raw, sl = raw, None, [None] * groups
             else:
-                raw = dc.forward(h, bn_groups=0 if bn.eval_mode else groups)
-            act = torch.empty_like(raw)
-            sl = bn.forward_groups(grows(raw), True, upd, grows(act), [dc.take_stats(gi) for gi in range(groups)], order)
+                h = torch.empty_like(raw)
+                sl = blk.bn.forward_groups(grows(raw), True, upd, grows(h),
+                                           [blk.conv.take_stats(gi) for gi in range(groups)], order)
             raws.append(raw)
             svs.append(sl)
-            acts.append(act)
-            h = act
+            acts.append(h)
         y = self.c3.forward(h, ACT_TANH, out=out)
         return y, dict(z=z16, raw_fc=raw_fc, sv_fc=sv_fc, acts=acts, raws=raws, svs=svs, y=y, B=B, groups=groups,
                        zscale=zscale)
@@ -319,95 +413,48 @@ class DecoderNet(_JoinedBackward):
         dict(g=<forward group whose activations it belongs to>, scale=<float>, train=<accumulate param grads>,
         need_dz=<bool>).  Returns {e: dz fp32 [B, z] (true scale)} for entries with need_dz."""
         B = ctx["B"]
-        E = len(entries)
+        cots = [Cot(en["g"], en["scale"], en["train"], need_dz=bool(en.get("need_dz"))) for en in entries]
+        E = len(cots)
         rows = lambda t, i: t[i * B:(i + 1) * B]
-        # weight-gradient runs: consecutive training blocks with the same scale through consecutive forward groups are
-        # one launch over all their rows (2 x 256 images as one 512-image launch: 638 vs 806 us for the decoder's four
-        # conv layers, tools/probes/wgrad_n512.py)
-        runs, e = [], 0
-        while e < E:
-            if not entries[e]["train"]:
-                e += 1
-                continue
-            f = e
-            while (f + 1 < E and entries[f + 1]["train"] and entries[f + 1]["scale"] == entries[e]["scale"]
-                   and entries[f + 1]["g"] == entries[f]["g"] + 1):
-                f += 1
-            runs.append((e, f))
-            e = f + 1
-
-        def wgrads(layer, x_all, d_all):
-            for e0, e1 in runs:
-                g0 = entries[e0]["g"]
-                layer.wgrad(x_all[g0 * B:(g0 + e1 - e0 + 1) * B], d_all[e0 * B:(e1 + 1) * B], entries[e0]["scale"])
-
+        runs = _wgrad_runs(cots)
         y = ctx["y"]
+        raws, svs = ctx["raws"], ctx["svs"]
         dpre = torch.empty_like(cot)
-        for e, en in enumerate(entries):
+        for e, en in enumerate(cots):
             colsum = None
-            if en["train"]:
+            if en.train:
                 colsum = torch.empty(2 * pad8(self.c3.cout), dtype=torch.float32, device=cot.device)
             # the bias gradient of conv.3 rides in the fold of the column sums (its first cout entries)
-            act_backward(rows(y, en["g"]), rows(cot, e), ACT_TANH, colsum, out=rows(dpre, e),
-                         dbias=self.c3.bg if en["train"] else None, dbias_scale=1.0 / en["scale"])
-        wgrads(self.c3, ctx["acts"][3], dpre)
+            act_backward(rows(y, en.g), rows(cot, e), ACT_TANH, colsum, out=rows(dpre, e),
+                         dbias=self.c3.bg if en.train else None, dbias_scale=1.0 / en.scale)
+        _wgrad_blocks(self.c3, ctx["acts"][3], dpre, runs, B)
         _, hi, wi, _ = ctx["acts"][3].shape
         d = self.c3.dgrad(dpre, hi, wi)
         stat = None
-        def bn_backward(bn, raw_all, sv_all, d_all, draw_all, stat):
-            """BatchNorm backward of every cotangent block of one layer.  With SyncBN the reductions of all blocks run
-            first (phase 1) into one [2E][C] buffer that is exchanged ONCE, then the apply passes (phase 2)."""
-            sync = bn.reducer is not None
-            sums_all = torch.empty(2 * E, bn.C, dtype=torch.float32, device=d_all.device) if sync else None
-            for phase in ((1, 2) if sync else (3,)):
-                if phase == 2:
-                    bn.reducer(sums_all)
-                e = 0
-                while e < E:
-                    en = entries[e]
-                    nx = entries[e + 1] if e + 1 < E else None
-                    sm = sums_all[2 * e:] if sync else None
-                    if nx is not None and nx["g"] == en["g"] and not (nx["train"] and en["train"]):
-                        # two adjacent blocks through the same forward activations: one pass over them for both; the
-                        # gamma / beta gradients come from whichever of the two trains
-                        ps = 1 if nx["train"] else 0
-                        tr = nx if nx["train"] else en
-                        bn.backward2(rows(raw_all, en["g"]), d_all[e * B:(e + 2) * B], sv_all[en["g"]], True,
-                                     tr["scale"] if tr["train"] else None, out=draw_all[e * B:(e + 2) * B],
-                                     param_stream=ps, stat=stat, stat_group=e, sums=sm[:4] if sync else None, phase=phase)
-                        e += 2
-                    else:
-                        bn.backward(rows(raw_all, en["g"]), rows(d_all, e), sv_all[en["g"]], True,
-                                    en["scale"] if en["train"] else None, out=rows(draw_all, e), stat=stat,
-                                    stat_group=e, sums=sm[:2] if sync else None, phase=phase)
-                        e += 1
-
         for i in (2, 1, 0):
+            blk = self.blocks[i]
             draw = torch.empty_like(d)
-            bn_backward(self.bns[i], ctx["raws"][i], ctx["svs"][i], d, draw, stat)
+            _bn_backward_blocks(blk.bn, raws[i], svs[i], cots, B, d, draw, stat)
             _, hi, wi, _ = ctx["acts"][i].shape
             if i > 0:
-                # block i-1's ReLU mask and BatchNorm backward sums come out of this data gradient's epilogue: one
-                # statistics group per cotangent block (its forward call's rows of the saved tensor and statistics)
-                d = self.deconvs[i].dgrad(draw, hi, wi, bn_bwd=_bwd_epi(
-                    bn=self.bns[i - 1], x=ctx["raws"][i - 1],
-                    groups=[(en["g"] * B, ctx["svs"][i - 1][en["g"]]) for en in entries]))
-                stat = self.deconvs[i].take_bwd_stats()
+                # one statistics group per cotangent block: its forward call's rows of the saved tensor and statistics
+                d, stat = blk.dgrad_below(draw, self.blocks[i - 1], raws[i - 1],
+                                          [(en.g * B, svs[i - 1][en.g]) for en in cots], hi, wi)
             else:
-                d = self.deconvs[i].dgrad(draw, hi, wi)
-            wgrads(self.deconvs[i], ctx["acts"][i], draw)       # (after the data gradient: see EncoderNet._backward)
+                d = blk.conv.dgrad(draw, hi, wi)
+            _wgrad_blocks(blk.conv, ctx["acts"][i], draw, runs, B)     # (after the data gradient: see EncoderNet._backward)
         dflat = d.reshape(E * B, -1)
         draw_fc = torch.empty_like(dflat)
         out = {}
-        bn_backward(self.fc_bn, ctx["raw_fc"], ctx["sv_fc"], dflat, draw_fc, None)
-        wgrads(self.fc, ctx["z"], draw_fc)
-        for e, en in enumerate(entries):
-            if en.get("need_dz"):
+        _bn_backward_blocks(self.fc_bn, ctx["raw_fc"], ctx["sv_fc"], cots, B, dflat, draw_fc, None)
+        _wgrad_blocks(self.fc, ctx["z"], draw_fc, runs, B)
+        for e, en in enumerate(cots):
+            if en.need_dz:
                 _, dz32 = self.fc.dgrad(rows(draw_fc, e).contiguous(), want32=True)
-                out[e] = dz32 * (1.0 / en["scale"])
+                out[e] = dz32 * (1.0 / en.scale)
                 if ctx.get("zscale") is not None:
                     # the group's rows were stored as s * z: d/dz = s * d/d(stored rows)
-                    out[e] *= ctx["zscale"][en["g"]:en["g"] + 1]
+                    out[e] *= ctx["zscale"][en.g:en.g + 1]
         return out
 
 
@@ -426,12 +473,11 @@ class DiscriminatorNet(_JoinedBackward):
         g = self.group
         d = cfg.discrim_channels
         self.c0 = ConvLayer(g, "conv.0.0.weight", "conv.0.0.bias", "conv", 3, d[0], 5, cfg.stride_gan, 2)
-        self.convs, self.bns = [], []
+        self.blocks = []                    # blocks[i] = the reference's conv.{i + 1}
         cin = d[0]
         for i in (1, 2, 3):
-            self.convs.append(ConvLayer(g, f"conv.{i}.conv.weight", None, "conv", cin, d[i], cfg.kernel_size,
-                                        cfg.stride, cfg.padding))
-            self.bns.append(BatchNorm(g, f"conv.{i}.bn.", d[i]))
+            self.blocks.append(ConvBlock(ConvLayer(g, f"conv.{i}.conv.weight", None, "conv", cin, d[i], cfg.kernel_size,
+                                                   cfg.stride, cfg.padding), BatchNorm(g, f"conv.{i}.bn.", d[i])))
             cin = d[i]
         hw = cfg.fc_input_gan * cfg.fc_input_gan
         self.fc0 = DenseLayer(g, "fc.0.weight", None, hw * cin, cfg.fc_output_gan, in_perm=(cin, hw))
@@ -439,13 +485,12 @@ class DiscriminatorNet(_JoinedBackward):
         self.fc3 = DenseLayer(g, "fc.3.weight", "fc.3.bias", cfg.fc_output_gan, 1)
 
     def all_bns(self):
-        return self.bns + [self.fc_bn]
+        return [blk.bn for blk in self.blocks] + [self.fc_bn]
 
     def reads_zero_tail(self) -> bool:
         """Whether the two-stream ``backward`` reads the ``zero_tail`` rows of stream B's starting cotangent (the sampled
         images' rows), i.e. whether the caller has to write those zeros: the join layer's data gradient skips them
         unless it runs with the BatchNorm-backward epilogue (ops._EPI_BWD; block 1's data gradient has none above it)."""
-        from . import ops
         return self.level > 1 and ops._EPI_BWD
 
     def forward(self, x16: torch.Tensor, train_stats: bool = True, conv_updates: int = 2, fc_updates: int = 1,
@@ -458,22 +503,17 @@ class DiscriminatorNet(_JoinedBackward):
         acts, raws, svs = [a0], [], []
         h = a0
         lv = self.level
-        for li, (conv, bn) in enumerate(zip(self.convs, self.bns)):
+        for li, blk in enumerate(self.blocks):
             if not head and li >= lv:
                 break                     # a 'REC' call ends at block ``recon_level`` (models/vae_gan.py:166-173)
-            if bn.eval_mode and not bn.perm and li != lv - 1:   # (block ``recon_level``'s RAW output is the 'REC' tensor)
-                out_e = conv.forward(h, affine=bn.eval_affine())
-                if conv.aff_applied:
-                    raws.append(None); svs.append(None); acts.append(out_e)
-                    h = out_e
-                    continue
-                raw = out_e
+            raw, done = blk.conv_forward(h, keep_raw=li == lv - 1)   # (block ``recon_level``'s RAW output is 'REC')
+            if done:
+                h, raw, sv = raw, None, None
             else:
-                raw = conv.forward(h, bn_groups=0 if bn.eval_mode else 1)
-            # one pass standing for the reference's REC + GAN passes (conv_updates = 2): the REC pass never reaches the
-            # blocks above ``recon_level``, they take the GAN pass's update only
-            upd = conv_updates if li < lv else min(conv_updates, 1)
-            h, sv = bn.forward(raw, relu=True, updates=upd if train_stats else 0, stat_acc=conv.take_stats())
+                # one pass standing for the reference's REC + GAN passes (conv_updates = 2): the REC pass never reaches
+                # the blocks above ``recon_level``, they take the GAN pass's update only
+                upd = conv_updates if li < lv else min(conv_updates, 1)
+                h, sv = blk.bn.forward(raw, relu=True, updates=upd if train_stats else 0, stat_acc=blk.conv.take_stats())
             raws.append(raw)
             svs.append(sv)
             acts.append(h)
@@ -496,9 +536,9 @@ class DiscriminatorNet(_JoinedBackward):
     def conv_running_again(self, ctx, updates: int = 1):
         """Apply the conv blocks' BatchNorm running-statistics update once more with the batch statistics saved in ``ctx``
         (a repeated forward call on the same input, see BatchNorm.update_running_again)."""
-        for bn, sv in zip(self.bns, ctx["svs"]):
+        for blk, sv in zip(self.blocks, ctx["svs"]):
             if sv is not None:
-                bn.update_running_again(sv, updates)
+                blk.bn.update_running_again(sv, updates)
 
     def _backward(self, ctx, dlogit16: Optional[torch.Tensor], scale_a: float, dfeat16: Optional[torch.Tensor],
                  scale_b: float, train: bool, img_rows: Optional[slice], img_streams=(True, True),
@@ -513,110 +553,105 @@ class DiscriminatorNet(_JoinedBackward):
            that pass writes A's rows into the first half of ``stack``; from block L down both streams run together.
            Returns (dimg_A, dimg_B): cotangents w.r.t. input images ``img_rows`` (None if not requested)."""
         n3 = ctx["x"].shape[0]
-        streams = []
-        join = self.level - 1               # block whose raw output stream B enters at (index into convs / raws)
-        top = 2                             # block whose raw output the first cotangent enters at
-        if dlogit16 is None and dfeat16 is not None:
-            top = join                       # a 'REC' call alone: the feature cotangent enters at block ``recon_level``
+        join = self.level - 1               # block whose raw output stream B enters at (index into blocks / raws)
         both = dlogit16 is not None and dfeat16 is not None
-        late = None                          # stream B while stream A is still alone above the join
-        if dlogit16 is not None:
-            if train:
-                self.fc3.wgrad(ctx["hfc"], dlogit16, scale_a)
-                self.fc3.bias_grad(dlogit16, scale_a)
-            dh, _ = self.fc3.dgrad(dlogit16)
-            draw_fc, _ = self.fc_bn.backward(ctx["raw_fc"], dh, ctx["svfc"], True, scale_a if train else None)
-            if train:
-                self.fc0.wgrad(ctx["flat"], draw_fc, scale_a)
-            dflat, _ = self.fc0.dgrad(draw_fc)
-            d3 = dflat.reshape(ctx["acts"][3].shape)
-            # caller-provided stack [A rows | B rows] with B already in place (steps._start_cotangents): A goes into its
-            # first half and the two-stream batch needs no concatenation copy
-            if dfeat16 is None:
-                stack = None
-            if stack is not None and stack.shape[0] != 2 * n3:
-                stack = None
-            draw3, _ = self.bns[2].backward(ctx["raws"][2], d3, ctx["svs"][2], True, scale_a if train else None,
-                                            out=stack[:n3].reshape(ctx["raws"][2].shape)
-                                            if (stack is not None and join == 2) else None)
-            streams.append(dict(d=draw3, scale=scale_a, train=train, img=img_streams[0]))
-        else:
+        # caller-provided stack [A rows | B rows] with B already in place (steps._start_cotangents): A goes into its
+        # first half and the two-stream batch needs no concatenation copy
+        if stack is not None and (not both or stack.shape[0] != 2 * n3):
             stack = None
+        sa = Cot(0, scale_a, train, img_streams[0])
+        sb = Cot(0, scale_b, train_b, img_streams[1])
+        streams, d, late = [], None, None
+        if dlogit16 is not None:
+            half = stack[:n3].reshape(ctx["raws"][2].shape) if (stack is not None and join == 2) else None
+            d = self._backward_head(ctx, dlogit16, sa, half)
+            streams.append(sa)
         if dfeat16 is not None:
-            sb = dict(d=dfeat16.reshape(ctx["raws"][join].shape), scale=scale_b, train=train_b, img=img_streams[1])
+            db = dfeat16.reshape(ctx["raws"][join].shape)
             if both and join < 2:
-                late = sb
+                late = (sb, db)              # stream B while stream A is still alone above the join
             else:
                 streams.append(sb)
-        S = len(streams)
-        if S > 1 and stack is not None:
-            d = stack.reshape((2 * n3,) + tuple(ctx["raws"][2].shape[1:]))
-        else:
-            d = torch.cat([s["d"] for s in streams], 0) if S > 1 else streams[0]["d"]
-        rows = lambda t, i: t[i * n3:(i + 1) * n3]
-        # conv3 .. conv1 (from block ``top`` down)
-        for li in range(top, -1, -1):
+                if both:
+                    d = stack.reshape((2 * n3,) + tuple(db.shape[1:])) if stack is not None else torch.cat([d, db], 0)
+                else:
+                    d = db
+        # the first cotangent enters at block 3's raw output; a 'REC' call alone at block ``recon_level``'s
+        top = 2 if dlogit16 is not None else join
+        d, streams = self._backward_blocks(ctx, d, streams, late, top, stack, zero_tail)
+        outs = self._backward_images(ctx, d, streams, img_rows, zero_tail)
+        return (outs[0] if dlogit16 is not None else None), (outs[-1] if dfeat16 is not None else None)
+
+    def _backward_head(self, ctx, dlogit16, sa: Cot, out: Optional[torch.Tensor]):
+        """Stage 1 of ``_backward``: stream A through fc.3, the BatchNorm1d, fc.0 and block 3's BatchNorm.  Returns the
+        cotangent of block 3's raw output, written into ``out`` (the first half of the caller's stack) where given."""
+        pscale = sa.scale if sa.train else None
+        if sa.train:
+            self.fc3.wgrad(ctx["hfc"], dlogit16, sa.scale)
+            self.fc3.bias_grad(dlogit16, sa.scale)
+        dh, _ = self.fc3.dgrad(dlogit16)
+        draw_fc, _ = self.fc_bn.backward(ctx["raw_fc"], dh, ctx["svfc"], True, pscale)
+        if sa.train:
+            self.fc0.wgrad(ctx["flat"], draw_fc, sa.scale)
+        dflat, _ = self.fc0.dgrad(draw_fc)
+        d3 = dflat.reshape(ctx["acts"][3].shape)
+        if out is None:
+            out = torch.empty_like(d3)
+        _bn_backward_blocks(self.blocks[2].bn, ctx["raws"][2], [ctx["svs"][2]], (sa,), d3.shape[0], d3, out, None)
+        return out
+
+    def _backward_blocks(self, ctx, d, streams, late, top: int, stack, zero_tail: int):
+        """Stage 2 of ``_backward``: from block ``top`` down to block 1 (``blocks[top] .. blocks[0]``), per block its data
+        gradient, its weight gradients and the BatchNorm backward of the block below.  ``late`` = (stream B, its
+        cotangent) while A is alone above the join.  Returns (cotangent of block 1's raw output [S*3B, ...], streams)."""
+        n3 = ctx["x"].shape[0]
+        join = self.level - 1
+        acts, raws, svs = ctx["acts"], ctx["raws"], ctx["svs"]
+        runs = _wgrad_runs(streams)
+        for li in range(top, 0, -1):
+            blk, below = self.blocks[li], self.blocks[li - 1]
             S = len(streams)
-            def wgrads(li=li, d=d, active=tuple(streams)):
-                # (issued after the layer's data gradient: see EncoderNet._backward)
-                for si, s in enumerate(active):
-                    if s["train"]:
-                        self.convs[li].wgrad(ctx["acts"][li], rows(d, si), s["scale"])
-            _, hi, wi, _ = ctx["acts"][li].shape
-            if li == 0:
-                wgrads()
-            if li > 0:
-                # the data gradient's epilogue masks with block li-1's ReLU and reduces its BatchNorm backward sums, one
-                # statistics group per cotangent stream (all read the same saved forward tensor)
-                epi = _bwd_epi(bn=self.bns[li - 1], x=ctx["raws"][li - 1], groups=[(0, ctx["svs"][li - 1])] * S)
-                ztail = zero_tail if (li == join and both and S > 1) else 0
-                if ztail and epi is None and d.shape[0] == S * n3:
-                    # stream B enters at block ``recon_level``'s raw output with exact zeros on the sampled images' rows
-                    # -- the last rows of the stack: that block's data gradient (per image) skips them, its result there
-                    # is zero
-                    live = d.shape[0] - ztail
-                    dact = torch.empty(d.shape[0], hi, wi, self.convs[li].cinp, dtype=torch.float16, device=d.device)
-                    self.convs[li].dgrad(d[:live], hi, wi, out=dact[:live])
-                    dact[live:].zero_()
-                else:
-                    dact = self.convs[li].dgrad(d, hi, wi, bn_bwd=epi)
-                wgrads()
-                stat = self.convs[li].take_bwd_stats()
-                if late is not None and li - 1 == join:
-                    # stream B joins here: A's BatchNorm backward into block ``recon_level``'s raw output writes the first
-                    # half of the caller's stack, whose second half already holds B (no concatenation copy)
-                    raw_j = ctx["raws"][join]
-                    use = stack is not None
-                    dn, _ = self.bns[join].backward(raw_j, dact, ctx["svs"][join], True,
-                                                    streams[0]["scale"] if streams[0]["train"] else None,
-                                                    out=stack[:n3].reshape(raw_j.shape) if use else None, stat=stat)
-                    d = (stack.reshape((2 * n3,) + tuple(raw_j.shape[1:])) if use
-                         else torch.cat([dn, late["d"]], 0))
-                    streams.append(late)
-                    late = None
-                    continue
-                dn = torch.empty_like(dact)
-                if S == 2 and not streams[1]["train"]:
-                    # both streams in one pass over the saved forward tensor (gamma / beta gradients from stream A only)
-                    self.bns[li - 1].backward2(ctx["raws"][li - 1], dact, ctx["svs"][li - 1], True,
-                                               streams[0]["scale"] if streams[0]["train"] else None, out=dn, stat=stat)
-                else:
-                    for si, s in enumerate(streams):
-                        self.bns[li - 1].backward(ctx["raws"][li - 1], rows(dact, si), ctx["svs"][li - 1], True,
-                                                  s["scale"] if s["train"] else None, out=rows(dn, si), stat=stat,
-                                                  stat_group=si)
-                d = dn
-        # conv1 data gradient, conv0 (bias + ReLU).  Below the last BatchNorm the images are independent, so a stream
-        # that does not train the discriminator only needs the rows whose image gradient is wanted.
+            _, hi, wi, _ = acts[li].shape
+            if li == join and S > 1 and zero_tail and not ops._EPI_BWD:
+                # stream B entered at block ``recon_level``'s raw output with exact zeros on the sampled images' rows
+                # -- the last rows of the stack: that block's data gradient skips them
+                dact, stat = _dgrad_live(blk.conv, d, d.shape[0] - zero_tail, hi, wi), None
+            else:
+                # one statistics group per cotangent stream (all read the same saved forward tensor)
+                dact, stat = blk.dgrad_below(d, below, raws[li - 1], [(0, svs[li - 1])] * S, hi, wi)
+            _wgrad_blocks(blk.conv, acts[li], d, runs, n3)      # (after the data gradient: see EncoderNet._backward)
+            joining = late is not None and li - 1 == join
+            # stream B joins here: A's BatchNorm backward into block ``recon_level``'s raw output writes the first half of
+            # the caller's stack, whose second half already holds B (no concatenation copy)
+            dn = stack[:n3].reshape(dact.shape) if (joining and stack is not None) else torch.empty_like(dact)
+            _bn_backward_blocks(below.bn, raws[li - 1], [svs[li - 1]], streams, n3, dact, dn, stat)
+            d = dn
+            if joining:
+                d = stack.reshape((2 * n3,) + tuple(dn.shape[1:])) if stack is not None else torch.cat([dn, late[1]], 0)
+                streams, late = streams + [late[0]], None
+                runs = _wgrad_runs(streams)
+        # block 1's weight gradients are issued here, BEFORE conv.1's data gradient (the image side's first launch)
+        _wgrad_blocks(self.blocks[0].conv, acts[0], d, runs, n3)
+        return d, streams
+
+    def _backward_images(self, ctx, d, streams, img_rows: Optional[slice], zero_tail: int):
+        """Stage 3 of ``_backward``: conv.1's data gradient, conv.0 (bias + ReLU).  Returns per stream the cotangent
+        w.r.t. the input images ``img_rows``, or None."""
+        n3 = ctx["x"].shape[0]
+        S = len(streams)
+        rows = lambda t, i: t[i * n3:(i + 1) * n3]
+        conv1 = self.blocks[0].conv
+        # Below the last BatchNorm the images are independent, so a stream that does not train the discriminator only
+        # needs the rows whose image gradient is wanted.
         a0 = ctx["acts"][0]
         _, hi, wi, _ = a0.shape
         full = slice(0, n3)
-        need = [full if s["train"] else (img_rows if (img_rows is not None and s["img"]) else None) for s in streams]
+        need = [full if s.train else (img_rows if (img_rows is not None and s.img) else None) for s in streams]
         # conv0's ReLU backward rides in the epilogue of conv1's data gradient where its kernel has one (act_applied),
         # and the bias gradient comes out of the weight-gradient kernel: no pass over the 64 x 64 x 32 cotangent
         masked = [False] * S
         if all(nd == full for nd in need):
-            dact = self.convs[0].dgrad(d, hi, wi)
+            dact = conv1.dgrad(d, hi, wi)
             dacts = [rows(dact, si) for si in range(S)]
         else:
             dacts = []
@@ -626,16 +661,13 @@ class DiscriminatorNet(_JoinedBackward):
                     continue
                 ds = rows(d, si)[nd]
                 live = ds.shape[0] - zero_tail
-                if both and join == 0 and si == 1 and nd.stop == n3 and 0 < live < ds.shape[0]:
+                if self.level == 1 and si == 1 and nd.stop == n3 and 0 < live < ds.shape[0]:
                     # recon_level 1: stream B entered at block 1's raw output, this is the join layer's data gradient --
                     # the sampled images' rows (the last of the stack) are exact zeros and are skipped
-                    da = torch.empty(ds.shape[0], hi, wi, self.convs[0].cinp, dtype=torch.float16, device=d.device)
-                    self.convs[0].dgrad(ds[:live], hi, wi, out=da[:live], relu_y=a0[nd][:live])
-                    da[live:].zero_()
-                    dacts.append(da)
+                    dacts.append(_dgrad_live(conv1, ds, live, hi, wi, relu_y=a0[nd][:live]))
                 else:
-                    dacts.append(self.convs[0].dgrad(ds, hi, wi, relu_y=a0[nd]))
-                masked[si] = self.convs[0].act_applied
+                    dacts.append(conv1.dgrad(ds, hi, wi, relu_y=a0[nd]))
+                masked[si] = conv1.act_applied
         outs = []
         for si, s in enumerate(streams):
             if need[si] is None:
@@ -643,30 +675,23 @@ class DiscriminatorNet(_JoinedBackward):
                 continue
             if masked[si]:
                 dpre = dacts[si]
-                if s["train"]:
-                    self.c0.wgrad(ctx["x"], dpre, s["scale"], bias_too=True)
+                if s.train:
+                    self.c0.wgrad(ctx["x"], dpre, s.scale, bias_too=True)
             else:
                 colsum = None
-                if s["train"]:
+                if s.train:
                     colsum = torch.empty(2 * self.c0.coutp, dtype=torch.float32, device=d.device)
                 dpre = act_backward(a0[need[si]], dacts[si], ACT_RELU, colsum,
-                                    dbias=self.c0.bg if s["train"] else None, dbias_scale=1.0 / s["scale"])
-                if s["train"]:
-                    self.c0.wgrad(ctx["x"], dpre, s["scale"])
-            if img_rows is not None and s["img"]:
+                                    dbias=self.c0.bg if s.train else None, dbias_scale=1.0 / s.scale)
+                if s.train:
+                    self.c0.wgrad(ctx["x"], dpre, s.scale)
+            if img_rows is not None and s.img:
                 _, xh, xw, _ = ctx["x"].shape
                 sub = dpre[img_rows] if need[si] == full else dpre
                 outs.append(self.c0.dgrad(sub.contiguous(), xh, xw))
             else:
                 outs.append(None)
-        res = [None, None]
-        k = 0
-        if dlogit16 is not None:
-            res[0] = outs[k]
-            k += 1
-        if dfeat16 is not None:
-            res[1] = outs[k]
-        return res[0], res[1]
+        return outs
 
 
 # ------------------------------------------------------------------------------------------------
@@ -747,7 +772,6 @@ class WaeDiscriminatorNet(_JoinedBackward):
         dz32 = torch.empty(M, Z, dtype=torch.float32, device=dev) if need_dz else None
         wds = [(self.layers[i].pw_d.get() if (i > 0 or need_dz) else None) for i in range(4)]
         kpd = (ctypes.c_int * 4)(*[self.layers[i].pw_d.kpads[0] for i in range(4)])
-        from . import ops
         det = ops.deterministic()        # bias gradients as fixed-order column sums instead of the kernel's atomics
         dbias = self._ptrs([l.bg for l in self.layers]) if (train and not det) else None
         lib.call("fmri_mlp_bwd", _P(dlogit16), dlogit16.shape[1], M, Zp, Z, 512, self._ptrs(hs[1:5]),

@@ -341,17 +341,17 @@ class _BlockNet:
         shape = (cout, cin, config.kernel_size, config.kernel_size) if kind == "conv" else \
             (cin, cout, config.kernel_size, config.kernel_size)
         self.group = FlatGroup([("conv.weight", shape, "w")] + _bn("bn.", cout), device)
-        self.conv = _ops.ConvLayer(self.group, "conv.weight", None, kind, cin, cout, config.kernel_size, config.stride,
-                                   config.padding, out_pad)
-        self.bn = _ops.BatchNorm(self.group, "bn.", cout)
+        self.block = _nets.ConvBlock(_ops.ConvLayer(self.group, "conv.weight", None, kind, cin, cout, config.kernel_size,
+                                                    config.stride, config.padding, out_pad),
+                                     _ops.BatchNorm(self.group, "bn.", cout))
         self.cout = cout
 
     def all_bns(self):
-        return [self.bn]
+        return [self.block.bn]
 
     def forward(self, x):
-        raw = self.conv.forward(_ops.images_to_nhwc(x), bn_groups=0 if self.bn.eval_mode else 1)
-        act, _ = self.bn.forward(raw, relu=True, updates=1, stat_acc=self.conv.take_stats())
+        raw, _ = self.block.conv_forward(_ops.images_to_nhwc(x), keep_raw=True)     # (the raw tensor is returned)
+        act, _ = self.block.bn.forward(raw, relu=True, updates=1, stat_acc=self.block.conv.take_stats())
         return _ops.nhwc_to_images(act, self.cout), raw
 
 

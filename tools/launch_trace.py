@@ -7,6 +7,8 @@ a float (pointers only as null / non-null: addresses differ between runs) and th
 appearance).  Under FMRI_DETERMINISTIC=1, with recipe weights and the oracle's synthetic batch (B = 4, 64 px, the voxel
 counts of the ``*_b4`` goldens) it runs every step class and launch mode and prints per configuration the number of
 launches, a SHA-256 of the trace and a SHA-256 of the state the steps left (scalar blocks, parameters, optimizer state).
+It also runs recon_level 1 and 2, an eval-mode forward and the drop-in module API (one Stage-I loop body, lone
+Encoder / Decoder blocks), hashing their outputs and parameter gradients in place of a state.
 Nothing is asserted about the hardware."""
 import argparse
 import ctypes
@@ -17,7 +19,7 @@ import sys
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.abspath(os.path.join(os.path.dirname(__file__), "..")),
                 help="the checkout whose package, oracle and goldens are used (default: this one)")
-ap.add_argument("--only", default="", help="run only the configurations whose name contains this")
+ap.add_argument("--only", default="", help="run only the configurations whose name contains one of these (comma-separated)")
 args = ap.parse_args()
 ROOT = os.path.abspath(args.root)
 os.environ["FMRI_DETERMINISTIC"] = "1"
@@ -58,8 +60,7 @@ def golden_v(name):
     return int(np.load(os.path.join(ROOT, "tests", "golden", name))["meta/V"])
 
 
-def state_hash(st):
-    h = hashlib.sha256()
+def state_tensors(st):
     tensors = [st.scal] + ([st.wscal] if hasattr(st, "wscal") else [])
     seen = set()
     for n in ("enc", "img_enc", "cog", "teacher_enc", "dec", "dis", "wd"):
@@ -71,6 +72,11 @@ def state_hash(st):
         o = getattr(st, n, None)
         if o is not None:
             tensors += [t for t in (o.s1, o.s2, o.lr_dev, o.t_dev) if t is not None]
+    return tensors
+
+
+def tensors_hash(tensors):
+    h = hashlib.sha256()
     torch.cuda.synchronize()
     for t in tensors:
         h.update(t.detach().cpu().contiguous().numpy().tobytes())
@@ -78,18 +84,21 @@ def state_hash(st):
 
 
 def run(name, make, drive):
-    """``make()`` -> step; ``drive(step)`` issues the launches that are traced."""
-    if args.only not in name:
+    """``make()`` -> step or module; ``drive(it)`` issues the launches that are traced and returns the tensors to hash
+    ("out"), or None for the state a step left ("state")."""
+    if not any(s in name for s in args.only.split(",")):
         return
     st = make()
-    st.load_recipe(0, True)
+    if hasattr(st, "load_recipe"):
+        st.load_recipe(0, True)
     torch.cuda.synchronize()
     TRACE.clear()
     STREAMS.clear()
-    drive(st)
+    outs = drive(st)
     ops.join_side()
     n, th = len(TRACE), hashlib.sha256("\n".join(TRACE).encode()).hexdigest()
-    print(f"{name:34s} launches {n:5d}  trace {th[:24]}  state {state_hash(st)[:24]}", flush=True)
+    what, hashed = ("state", state_tensors(st)) if outs is None else ("out", outs)
+    print(f"{name:34s} launches {n:5d}  trace {th[:24]}  {what} {tensors_hash(hashed)[:24]}", flush=True)
 
 
 def main():
@@ -102,7 +111,12 @@ def main():
         return d["x"].to(DEV), (d["fmri"].to(DEV) if V else None), nz
 
     x, _, nz = batch()
-    eager = lambda *a, **k: (lambda st: [st.step(*a, **k) for _ in range(2)])
+
+    def eager(*a, **k):
+        def drive(st):
+            for _ in range(2):
+                st.step(*a, **k)
+        return drive
 
     def recorded(*a):
         def drive(st):
@@ -115,6 +129,58 @@ def main():
         step = st.capture_forward(x, nz[0], nz[1])
         step()
         step()
+
+    def eval_forward(st):
+        """One forward with every BatchNorm in eval mode (the affine epilogue of the convolutions)."""
+        for net in (st.enc, st.dec, st.dis):
+            for bn in net.all_bns():
+                bn.eval_mode = True
+        fw = st.forward(x, nz[0], nz[1])
+        return [fw[k] for k in ("head32", "disc_in", "feat", "logit32")] + [st.scal]
+
+    # ---- the drop-in module API (models/vae_gan.py, imported as ``vg`` below): autograd bridges around the networks
+    def vaegan(level):
+        model = vg.VaeGan(device=DEV, z_size=128, recon_level=level).to(DEV)
+        model.load_state_dict(O.fill_state(O.vaegan_spec(cfg_o), 0, True))
+        return model
+
+    def api_loop(model):
+        """The Stage-I loop body (train_vgan_stage1.py) without the optimizers: forward, the three backward calls."""
+        hp = O.GanHyper()
+        model.train()
+        z_p = nz[1].clone().requires_grad_(True)
+        mus, lv = model.encoder(x)
+        x_tilde = model.decoder(nz[0] * torch.exp(0.5 * lv) + mus)
+        x_p = model.decoder(z_p)
+        disc_layer = model.discriminator(x, x_tilde, x_p, "REC")
+        disc_class = model.discriminator(x, x_tilde, x_p, "GAN")
+        nle, kld, mse, bo, bp, bs = vg.VaeGan.loss(x, x_tilde, disc_layer[:B], disc_layer[B:-B], disc_layer[-B:],
+                                                   disc_class[:B], disc_class[B:-B], disc_class[-B:], mus, lv)
+        loss_encoder = torch.sum(kld) + torch.sum(mse)
+        loss_discriminator = torch.sum(bo) + torch.sum(bp) + torch.sum(bs)
+        loss_decoder = torch.sum(hp.lambda_mse * mse) - (1.0 - hp.lambda_mse) * loss_discriminator
+        outs = [mus, lv, x_tilde, x_p, disc_layer, disc_class]
+        model.zero_grad()
+        for loss, part in ((loss_encoder, model.encoder), (loss_decoder, model.decoder),
+                           (loss_discriminator, model.discriminator)):
+            loss.backward(retain_graph=True)
+            outs += [p.grad.clone() for p in part.parameters()]
+            model.zero_grad()
+        return outs
+
+    def lone_block(kind):
+        torch.manual_seed(3)
+        blk = vg.EncoderBlock(64, 128) if kind == "enc" else vg.DecoderBlock(128, 64, out=True)
+        return blk.to(DEV)
+
+    def block_forward(kind, train):
+        def drive(blk):
+            blk.train(train)
+            xb = torch.randn(3, 64 if kind == "enc" else 128, 12, 12, generator=torch.Generator().manual_seed(4))
+            with torch.no_grad():
+                got = blk(xb.half().float().to(DEV), True) if kind == "enc" else blk(xb.half().float().to(DEV))
+            return list(got) if kind == "enc" else [got]
+        return drive
 
     for mode in ("vae-gan", "beta-vae", "dcgan", "vae"):
         run(f"stage1 {mode}", lambda: Stage1Step(cfg, DEV, mode=mode), eager(x, nz[0], nz[1]))
@@ -133,6 +199,22 @@ def main():
     run("stage1 capture", lambda: Stage1Step(cfg, DEV), recorded(x, nz[0], nz[1]))
     run("wae stage1 capture", lambda: WaeStep(cfg, DEV, 1), recorded(x, nz[2]))
     run("stage1 capture_forward", lambda: Stage1Step(cfg, DEV), hybrid)
+
+    # recon_level 1 / 2 (stream B joins the discriminator backward late), an eval-mode forward, the module API
+    for level in (1, 2):
+        run(f"stage1 vae-gan level{level}", lambda: Stage1Step(cfg, DEV, recon_level=level), eager(x, nz[0], nz[1]))
+    run("stage1 dcgan level1", lambda: Stage1Step(cfg, DEV, mode="dcgan", recon_level=1), eager(x, nz[0], nz[1]))
+    run("dual1 vae-gan level2", lambda: DualStage1Step(cfg, DEV, recon_level=2), eager(x, nz[0], nz[1], nz[2]))
+    run("stage1 eval forward", lambda: Stage1Step(cfg, DEV), eval_forward)
+    import configs.models_config as mc
+    mc.use_px64()
+    import models.vae_gan as vg
+    for level in (3, 2):
+        run(f"api stage1 loop level{level}", lambda: vaegan(level), api_loop)
+    for kind in ("enc", "dec"):
+        for train in (True, False):
+            run(f"api lone {kind} block {'train' if train else 'eval'}", lambda: lone_block(kind),
+                block_forward(kind, train))
 
     # the collective path with one rank (FMRI_FORCE_DIST=1), last: the process group stays up until the end
     if "dist" in args.only or not args.only:
