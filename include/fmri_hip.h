@@ -824,6 +824,56 @@ int fmri_epoch_begin(const int64_t* feed_state, fmri_schedule* sched, float* lr_
 int fmri_trainlog_append(const void* const* src_dev, const int32_t* kind_dev, int K, float* ring, int64_t capacity,
                          int64_t* counter, void* stream);
 
+/* ---- device-side training-state ring (csrc/state.hip; fmri_hip/state.py) --------------------------------------------
+ * What `if not idx_epoch % 5: torch.save(model.state_dict(), ...)` of the scripts' epoch loops (train_vgan_stage1.py:596)
+ * does on the host, for a step that runs from a recorded graph: ONE predicated launch that gathers every piece of
+ * training state -- weights, BatchNorm statistics, optimizer state, generator and feed position, the log -- into a slot of
+ * a device ring.  Whether the launch copies, and into which slot, is read on the device from the feed's state.
+ *
+ * A slot is a 64-byte header followed by the segments, each at a 16-byte boundary; a ring is `capacity` slots followed by
+ * one more, the "manual" slot (index `capacity`).  The header, eight int64 written by one thread when a copy fires and read
+ * by the host only: [FMRI_STATE_MAGIC, fingerprint, epoch, cursor, step, payload_bytes, 0, 0] -- epoch / cursor: the
+ * feed's position at the launch, the position a resume continues from (-1 without a feed); step: *log_counter (-1
+ * without one).
+ *
+ * One chunk (FMRI_STATE_CHUNK bytes of one segment) is what one 256-thread block moves: four 16-byte accesses per lane in
+ * flight when the segment's live address is 16-byte aligned (plus a dword tail), dword by dword otherwise.  Nothing
+ * outside a segment's bytes is written on either side.  Plain vector stores: no atomics, no memset, no allocation;
+ * enqueue-only and capturable. */
+#define FMRI_STATE_MAGIC 0x31544154534d4621ll    /* "!FMSTAT1" */
+#define FMRI_STATE_HEADER 64
+#define FMRI_STATE_CHUNK 16384
+typedef struct fmri_state_seg {
+    void* live;                                  /* device address of the tensor, a multiple of 4 */
+    int64_t offset;                              /* of its bytes in a slot: a multiple of 16, >= FMRI_STATE_HEADER */
+    int64_t bytes;                               /* a multiple of 4, >= 0 */
+    int64_t chunk0;                              /* chunks of the segments in front of it (the prefix a block searches) */
+} fmri_state_seg;                                /* 32 bytes */
+/* host only: the slot layout of nseg segments of bytes[i] each -- offsets_out[i] (may be NULL) and, returned, the slot
+ * size (a multiple of 16; 64 for nseg = 0).  nseg < 0, bytes NULL with nseg > 0, a negative byte count or one that is
+ * not a multiple of 4: FMRI_E_BADARG (negative). */
+int64_t fmri_state_layout(const int64_t* bytes, int nseg, int64_t* offsets_out);
+/* The slot side's access policy of every later fmri_state_copy of the process: 1 non-temporal loads / stores (the
+ * default; profiles/state_ring.md has the measurement it rests on), 0 plain ones; a negative value only asks.  Returns the
+ * policy that was in force.  The live side is always plain: the next step reads those tensors. */
+int fmri_state_nontemporal(int on);
+/* segs_host: the table in host memory, checked here on every call -- live addresses multiples of 4, byte counts of 4,
+ * offsets of 16, ascending and apart, inside a slot of slot_bytes, chunk0 the running chunk count -- and segs_dev its copy
+ * in device memory, which the kernel reads.  ring: 16-byte aligned, ring_bytes >= (capacity + 1) * slot_bytes.
+ * dir = 0 gathers live -> slot:
+ *   feed_state != NULL (the [seed, epoch, cursor] of fmri_sampler_indices) and every >= 1: the launch copies only when
+ *     cursor == 0, epoch >= 1 and (epoch - 1) % every == 0 -- the state at the end of epoch epoch - 1 where
+ *     idx_epoch % every == 0 -- into slot ((epoch - 1) / every) % capacity (capacity >= 1).  Every block evaluates this
+ *     from the same three words, which the launch does not write; when it is false every block returns at once and no
+ *     byte of the ring changes.
+ *   every == 0: unconditional, into the manual slot; feed_state (may be NULL) only fills the header's position.
+ * dir = 1 scatters slot `capacity` -> live, unconditionally (feed_state must be NULL, every 0); the header is not read.
+ * log_counter may be NULL.  Grid: min(chunks, 2048) blocks, grid-stride.  A table that fails the checks: FMRI_E_BADARG,
+ * nothing is launched. */
+int fmri_state_copy(const fmri_state_seg* segs_host, const fmri_state_seg* segs_dev, int nseg, void* ring,
+                    int64_t ring_bytes, int64_t slot_bytes, int dir, const int64_t* feed_state, int every, int capacity,
+                    uint64_t fingerprint, const int64_t* log_counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

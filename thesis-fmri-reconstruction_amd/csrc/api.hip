@@ -1274,6 +1274,26 @@ int fmri_trainlog_append(const void* const* src_dev, const int32_t* kind_dev, in
         return FMRI_E_BADARG;
     return trainlog_append_launch(src_dev, kind_dev, K, ring, capacity, counter, S(stream));
 }
+int64_t fmri_state_layout(const int64_t* bytes, int nseg, int64_t* offsets_out) {
+    if (nseg < 0 || (nseg > 0 && !bytes)) return FMRI_E_BADARG;
+    return state_layout(bytes, nseg, offsets_out);
+}
+int fmri_state_nontemporal(int on) { return state_nontemporal(on); }
+int fmri_state_copy(const fmri_state_seg* segs_host, const fmri_state_seg* segs_dev, int nseg, void* ring,
+                    int64_t ring_bytes, int64_t slot_bytes, int dir, const int64_t* feed_state, int every, int capacity,
+                    uint64_t fingerprint, const int64_t* log_counter, void* stream) {
+    if (nseg < 0 || (nseg > 0 && (!segs_host || !segs_dev || ((uintptr_t)segs_dev & 7))) || !ring ||
+        ((uintptr_t)ring & 15) || slot_bytes < FMRI_STATE_HEADER || (slot_bytes & 15) || capacity < 0 || every < 0 ||
+        (dir != 0 && dir != 1) || ((uintptr_t)feed_state & 7) || ((uintptr_t)log_counter & 7))
+        return FMRI_E_BADARG;
+    if (every > 0 && (!feed_state || capacity < 1)) return FMRI_E_BADARG;
+    if (dir == 1 && (feed_state || every)) return FMRI_E_BADARG;
+    if (slot_bytes > ring_bytes / ((int64_t)capacity + 1)) return FMRI_E_BADARG;
+    const int64_t chunks = state_table_chunks(segs_host, nseg, slot_bytes);
+    if (chunks < 0) return FMRI_E_BADARG;
+    return state_copy_launch(segs_dev, nseg, chunks, ring, slot_bytes, dir, feed_state, every, capacity, fingerprint,
+                             log_counter, S(stream));
+}
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream) {
     if (!x || !out || (n & 7)) return FMRI_E_BADARG;

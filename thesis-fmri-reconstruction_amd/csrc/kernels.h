@@ -284,6 +284,14 @@ int epoch_begin_launch(const int64_t* feed_state, void* sched, float* lr0, float
 int schedule_seek_host(void* sched, int64_t epoch, float* out7);
 int trainlog_append_launch(const void* const* src, const int32_t* kind, int K, float* ring, int64_t capacity,
                            int64_t* counter, hipStream_t st);
+// csrc/state.hip (`segs`: fmri_state_seg tables of include/fmri_hip.h; state_table_chunks: the host check of a table,
+// its chunk count or E_BADARG)
+int64_t state_layout(const int64_t* bytes, int nseg, int64_t* offsets_out);
+int state_nontemporal(int on);
+int64_t state_table_chunks(const void* segs_host, int nseg, int64_t slot_bytes);
+int state_copy_launch(const void* segs_dev, int nseg, int64_t chunks, void* ring, int64_t slot_bytes, int dir,
+                      const int64_t* feed_state, int every, int capacity, uint64_t fingerprint,
+                      const int64_t* log_counter, hipStream_t st);
 int axpby_f16_launch(const half_t* x, const half_t* y, half_t* out, int64_t n, float a, float b, const float* pa,
                      const float* pb, hipStream_t st);
 int sumsq_launch(const float* x, int64_t n, float* acc, hipStream_t st);

@@ -111,6 +111,8 @@ _SIGS = {
     "fmri_schedule_seek_host": [_p, _l, _p],
     "fmri_epoch_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _p],
     "fmri_trainlog_append": [_p, _p, _i, _p, _l, _p, _p],
+    "fmri_state_nontemporal": [_i],
+    "fmri_state_copy": [_p, _p, _i, _p, _l, _l, _i, _p, _i, _i, C.c_uint64, _p, _p],
     "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
     "fmri_sumsq": [_p, _l, _p, _p],
@@ -142,6 +144,11 @@ class StatSeg(C.Structure):
                 ("gate", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_float), ("clamp", C.c_float)]
 
 
+class StateSeg(C.Structure):
+    """``fmri_state_seg`` of include/fmri_hip.h (one segment of a training-state slot)."""
+    _fields_ = [("live", C.c_void_p), ("offset", C.c_int64), ("bytes", C.c_int64), ("chunk0", C.c_int64)]
+
+
 class Schedule(C.Structure):
     """``fmri_schedule`` of include/fmri_hip.h (the device-resident state of an epoch-end schedule)."""
     _fields_ = [("lr_base", C.c_double * 4), ("margin_base", C.c_double), ("equilibrium_base", C.c_double),
@@ -152,6 +159,9 @@ class Schedule(C.Structure):
 
 
 SCHED_MAX_LR = 4         # FMRI_SCHED_MAX_LR
+STATE_MAGIC = 0x31544154534d4621     # FMRI_STATE_MAGIC
+STATE_HEADER = 64        # FMRI_STATE_HEADER
+STATE_CHUNK = 16384      # FMRI_STATE_CHUNK
 STAT_BYTES = 32          # sizeof(fmri_stat)
 STAT_MAX_SEGS = 8        # FMRI_STAT_MAX_SEGS
 
@@ -164,7 +174,7 @@ EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_
                              "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
                              "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
                              "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes", "fmri_images_u8_ws_bytes",
-                             "fmri_images_u8_out_bytes",
+                             "fmri_images_u8_out_bytes", "fmri_state_layout",
                              "fmri_tensor_stats_ws_bytes", "fmri_feat_mse_wide_chunk", "fmri_feat_mse_wide_ws_floats"])
 
 _lib = None
@@ -211,6 +221,8 @@ def load():
     lib.fmri_images_u8_ws_bytes.argtypes = [_i]
     lib.fmri_images_u8_out_bytes.restype = _l
     lib.fmri_images_u8_out_bytes.argtypes = [_i, _i, _i, _i, _i, _i, _i]
+    lib.fmri_state_layout.restype = _l
+    lib.fmri_state_layout.argtypes = [_p, _i, _p]
     lib.fmri_tensor_stats_ws_bytes.restype = _i
     lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
     lib.fmri_feat_mse_wide_chunk.restype = _i

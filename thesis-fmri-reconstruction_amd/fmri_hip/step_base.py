@@ -10,14 +10,17 @@ import torch
 
 from . import lib, ops
 from .monitor import Monitored
+from .nets import refresh_net
 from .rng import DeviceRng, StepNoise
 from .schedule import EpochSchedule, TrainLog, lr_columns
+from .state import StateRing, TrainState, _Segment
 
 _P = lib.ptr
 
 # slots of the fp32 scalar block (csrc/loss.hip enum Slot)
 (S_BCE_O, S_BCE_P, S_BCE_S, S_KL, S_MSE, S_NLE, S_LENC, S_LDIS, S_LDEC, S_DL2, S_NA, S_NB, S_RATIO,
  S_ONE, S_ESQ, S_NE, S_NP, S_C1, S_C2, S_C3, S_GDEC, S_KLW) = range(22)
+OPTIM_NAMES = ("encoder", "decoder", "discriminator", "wae_discriminator")      # entries of ``optims``, in their order
 S_ZMAX = 22         # slots [22, 26): max |z| of the latent batch of decoder group 0..3 (ops.latent_ranged; zero at step start)
 
 
@@ -72,6 +75,12 @@ class _Optim:
         if mon is not None:
             mon.param_stats(g.data, flag, rec)
         g.version += 1
+
+
+def _host_copy(host: float, dev: float) -> float:
+    """The host's double of a restored fp32 device value: the one it has when that already rounds to the device value
+    (1e-4 stays 1e-4, not 9.99999974e-05), else the device value."""
+    return host if torch.tensor(host, dtype=torch.float32).item() == dev else float(dev)
 
 
 class _SegmentRecorder:
@@ -232,6 +241,7 @@ class _StepBase(Monitored):
 
     schedule: Optional[EpochSchedule] = None
     log: Optional[TrainLog] = None
+    checkpoints: Optional[StateRing] = None
     _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
@@ -281,12 +291,177 @@ class _StepBase(Monitored):
 
     def _epoch_begin(self):
         """The launch in FRONT of the feed's draws: the feed's state still holds the epoch of the batch about to be drawn.
-        Moves the schedule there and / or notes the epoch for the log; nothing for a step with neither."""
+        Moves the schedule there and / or notes the epoch for the log; nothing for a step with neither.  Behind it, the
+        predicated snapshot launch of a ``checkpoints=StateRing(every=...)``."""
+        self._epoch_note()
+        if self.checkpoints is not None and self.checkpoints.every is not None:
+            self._state_ready()
+            self.checkpoints.launch()
+
+    def _epoch_note(self):
         noted = self._epoch_dev if self.feed is not None else None
         if self.schedule is not None:
             self.schedule.launch(noted)
         elif noted is not None:
             lib.call("fmri_epoch_begin", _P(self.feed._state), None, None, None, None, None, None, _P(noted))
+
+    # ---- training state: snapshot and bit-exact resume (fmri_hip/state.py) ---------------------------------------------
+    def _state_groups(self):
+        """(state-dict prefix, network) in ``state_dict()`` order -- a network listed twice appears under both prefixes
+        (Stage II's ``teacher_net.decoder.`` aliases ``decoder.``).  Each step class states its networks once, here."""
+        raise NotImplementedError
+
+    def state_dict(self):
+        sd = {}
+        for pre, n in self._state_groups():
+            sd.update(n.group.state_dict(pre))
+        return sd
+
+    def _state_nets(self):
+        nets = []
+        for _, n in self._state_groups():
+            if all(n is not m for m in nets):
+                nets.append(n)
+        return nets
+
+    def _lazy_bns(self):
+        return [bn for n in self._state_nets() for bn in n.all_bns() if bn._lazy]
+
+    def _group_segments(self):
+        """(segment name, live tensor, its entries of ``TrainState.model``) of every network: the fp32 masters as one
+        segment per group, and the BatchNorm buffers -- of a lazy BatchNorm the engine-order copies, which are the live
+        ones (ops.BatchNorm.enable_lazy_running)."""
+        owner, entries = {}, {}
+        for pre, n in self._state_groups():
+            g = n.group
+            first = owner.setdefault(id(g), pre)
+            live = {}
+            for bn in n.all_bns():
+                if bn._lazy:
+                    live[bn.prefix + "running_mean"] = (bn.rm_e, bn.perm)
+                    live[bn.prefix + "running_var"] = (bn.rv_e, bn.perm)
+            for k, shape, _ in g.spec:
+                if k in g.views:
+                    seg, t, off, perm = f"group:{first}data", g.data, g.offsets[k], None
+                else:
+                    t, perm = live.get(k, (g.bufs[k], None))
+                    seg, off = f"buf:{first}{k}", 0
+                entries.setdefault(seg, (t, []))[1].append((pre + k, off, tuple(shape), perm))
+        return [(seg, t, model) for seg, (t, model) in entries.items()]
+
+    def _state_tensors(self) -> Dict[str, torch.Tensor]:
+        """name -> persistent device tensor of everything a run needs to continue bit for bit; the subclasses add theirs.
+        Out: gradients, activations, the packed fp16 weights (derived), the schedule's struct (it re-seeks from the epoch),
+        the monitor, the evaluator, and the scratch every step rewrites before it reads it."""
+        out = {seg: t for seg, t, _ in self._group_segments()}
+        for name, o in zip(OPTIM_NAMES, self.optims):
+            out[f"opt:{name}.s1"] = o.s1
+            if o.s2 is not None:
+                out[f"opt:{name}.s2"] = o.s2
+            out[f"opt:{name}.lr"] = o.lr_dev
+            if o.t_dev is not None:
+                out[f"opt:{name}.t"] = o.t_dev
+        if self.rng is not None:
+            out["rng"] = self.rng._state
+        if self.feed is not None:
+            out["feed"] = self.feed._state
+            if self.feed.rng is not None and self.feed.rng is not self.rng:
+                out["feed_rng"] = self.feed.rng._state
+        if self.log is not None:
+            out["log"] = self.log.blk
+            out["log_epoch"] = self._epoch_dev
+        return out
+
+    def _state_signature(self) -> List[str]:
+        """What a state must agree in before it is restored into this step, one line each (the segment list follows)."""
+        sig = [f"class={type(self).__name__}", f"config={self.cfg!r}"]
+        for a in ("mode", "stage", "penalty", "n_voxels"):
+            if hasattr(self, a):
+                sig.append(f"{a}={getattr(self, a)}")
+        if hasattr(getattr(self, "dis", None), "level"):
+            sig.append(f"recon_level={self.dis.level}")
+        sig.append("optims=" + ",".join(f"{n}:{o.kind}" for n, o in zip(OPTIM_NAMES, self.optims)))
+        sig.append("log=" + ("none" if self.log is None else ",".join(self.log.names) + f"@{self.log.capacity}"))
+        return sig
+
+    def _host_state(self) -> dict:
+        """Host-side counters a resumed run needs (TrainState.meta["host"]); none here."""
+        return {}
+
+    def _restored(self, host: dict):
+        """Host copies of restored device values (``restore`` has synchronised): learning rates, Adam's step count, the
+        feed's seed; the subclasses add theirs.  A scheduled optimizer keeps the BASE rate its schedule started from."""
+        for o in self.optims:
+            if not o.scheduled:
+                o._lr = _host_copy(o._lr, o.lr_dev.item())
+            if o.t_dev is not None:
+                o.t = int(o.t_dev.item())        # replays never advance ``t``: the device counter is the truth
+        if self.feed is not None:
+            self.feed._seed = int(self.feed._state[0].item())
+
+    def _init_checkpoints(self, ring: Optional[StateRing]):
+        """``checkpoints=`` of the step classes, after ``_init_log``."""
+        self.checkpoints = ring
+        if ring is None:
+            return
+        if ring.every is not None and self.feed is None:
+            raise ValueError(f"{type(self).__name__}: checkpoints=StateRing(every=...) needs feed=DeviceFeed(...): the "
+                             "feed is where the epoch lives (every=None takes manual snapshots only)")
+        model = {seg: m for seg, _, m in self._group_segments()}
+        segs = [_Segment(name, t, model.get(name)) for name, t in self._state_tensors().items()]
+        keys = [pre + k for pre, n in self._state_groups() for k, _, _ in n.group.spec]
+        ring.attach(self.device, segs, self._state_signature(), keys,
+                    self.feed._state if self.feed is not None else None,
+                    self.log.counter if self.log is not None else None, self._host_state)
+
+    def _state_ready(self, between_steps: bool = False):
+        """In front of a snapshot launch: the optimizer updates of the eager two-stream mode run on the side stream, so the
+        step must have joined; the engine-order BatchNorm statistics must be the loaded ones (a host check; they are after
+        the first step).  ``between_steps`` (a manual snapshot): no weight gradient may be waiting for its update -- a
+        snapshot between ``backward()`` and ``apply()`` would hold half a step."""
+        ops.join_side()
+        if between_steps:
+            for n in self._state_nets():
+                if n.group.gq.pending or n.group.gq.materialized:
+                    raise RuntimeError("snapshot between backward() and apply(): weight gradients are still queued")
+        for bn in self._lazy_bns():
+            bn._running_in()
+
+    def snapshot(self):
+        """The state now, into the manual slot of the step's ``checkpoints=StateRing(...)``: enqueue-only, between eager
+        steps or replays (``ring.states()`` reads it).  A fed step takes it where its own launch would: behind the
+        ``fmri_epoch_begin`` of the batch about to be drawn -- at an epoch boundary the learning rates and the gate's
+        parameters are the new epoch's already, which the next step would have written first thing anyway -- so a manual
+        snapshot at a boundary is bit for bit the slot the ring keeps there."""
+        if self.checkpoints is None:
+            raise RuntimeError("snapshot(): the step was constructed without checkpoints=StateRing(...)")
+        self._state_ready(between_steps=True)
+        if self.feed is not None:
+            self._epoch_note()
+        self.checkpoints.snapshot()
+
+    def restore(self, state: TrainState):
+        """Continue the run ``state`` was taken from: every tensor of ``_state_tensors()`` is overwritten (one host-to-device
+        copy, one launch), everything derived from the weights is refreshed NOW -- a recorded step updates its packed fp16
+        weights inside the graph and never looks at a version counter --, queued weight gradients are dropped and the
+        host's copies of device values follow.  A state of another class, config, mode, optimizer kind or log layout is
+        a ValueError naming the first difference, raised before any device byte changes.  Synchronises."""
+        ring = self.checkpoints
+        if ring is None:
+            raise RuntimeError("restore(): the step was constructed without checkpoints=StateRing(...)")
+        ring.check(state)
+        blob = ring.encode(state)
+        ops.join_side()
+        for bn in self._lazy_bns():
+            bn._running_in()                     # a pending reload from the reference-order buffers would undo the restore
+        ring.scatter(blob)
+        for n in self._state_nets():
+            n.group.drop_pending()
+            n.group.version += 1
+        self._restored(dict(state.meta["host"]))
+        for n in self._state_nets():
+            refresh_net(n)
+        torch.cuda.current_stream().synchronize()
 
     def _log_append(self):
         """The last launch of a step: behind the gate, the loss all-reduce and every kernel that writes a logged value."""

@@ -31,7 +31,7 @@ from .params import ArchConfig
 from .rng import SID_EPS, SID_EPS_TEACHER, SID_ZP, DeviceRng
 from .step_base import (S_BCE_O, S_BCE_P, S_BCE_S, S_KL, S_MSE, S_NLE, S_LENC, S_LDIS, S_LDEC, S_DL2, S_NA, S_NB,  # noqa: F401
                         S_RATIO, S_ONE, S_ESQ, S_NE, S_NP, S_C1, S_C2, S_C3, S_GDEC, S_KLW, S_ZMAX, _attach_reducers,
-                        _Dist, _Optim, _SegmentRecorder, _small_group, _SMALL_GROUP, _StepBase)
+                        _Dist, _host_copy, _Optim, _SegmentRecorder, _small_group, _SMALL_GROUP, _StepBase)
 
 _P = lib.ptr
 
@@ -200,10 +200,28 @@ class _GanStepBase(_StepBase):
         cols = [(k, self.scal, i) for i, k in enumerate(LOG_KEYS)]
         return cols + [("train_dis", self.flags, 0), ("train_dec", self.flags, 1)], LOG_KEYS
 
-    def _init_extras(self, schedule, log):
-        """``schedule=`` / ``log=`` once ``optims`` is complete.  lr: encoder, decoder, discriminator, as ``set_hyper``."""
+    def _init_extras(self, schedule, log, checkpoints=None):
+        """``schedule=`` / ``log=`` / ``checkpoints=`` once ``optims`` is complete.  lr: encoder, decoder, discriminator,
+        as ``set_hyper``."""
         self._init_schedule(schedule, [i < 3 for i in range(len(self.optims))], self.hp, self.hp_dev)
         self._init_log(log)
+        self._init_checkpoints(checkpoints)
+
+    def _state_tensors(self):
+        out = super()._state_tensors()
+        out["hp"] = self.hp_dev
+        return out
+
+    def _restored(self, host):
+        """``self.hp`` follows the restored device block -- under a schedule only ``beta``: the rest keeps the BASE values
+        the schedule started from (``set_hyper``)."""
+        super()._restored(host)
+        hp, v = self.hp, self.hp_dev.tolist()
+        hp.beta = _host_copy(hp.beta, v[3])
+        if self.schedule is None:
+            hp.lambda_mse, hp.equilibrium, hp.margin = (_host_copy(h, d) for h, d in
+                                                         zip((hp.lambda_mse, hp.equilibrium, hp.margin), v))
+            hp.lr = self.optims[0].lr
 
     def logs(self):
         v = self.scal.tolist()
@@ -219,8 +237,12 @@ class Stage1Step(_GanStepBase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
                  monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None,
-                 recon_level: int = 3):
-        """``recon_level`` (1, 2 or 3; the scripts' ``--recon_level``, train_vgan_stage1.py:62,237): the discriminator
+                 recon_level: int = 3, checkpoints=None):
+        """``checkpoints``: a fmri_hip.state.StateRing; with its ``every`` set, one predicated launch behind
+        ``fmri_epoch_begin`` keeps the whole training state of the epochs the scripts save (``idx_epoch % every == 0``) in a
+        device ring, recorded steps included; ``snapshot()`` takes the state now, ``ring.states()`` reads the ring with
+        one sync and ``restore(state)`` continues a run bit for bit (fmri_hip/state.py).  None: nothing is added.
+        ``recon_level`` (1, 2 or 3; the scripts' ``--recon_level``, train_vgan_stage1.py:62,237): the discriminator
         block whose raw convolution output is the feature tensor of the ``mse`` term.  The parameters, and so
         ``state_dict()``, are the same at every level.  Below 3 the feature cotangent joins the logit cotangent below the
         top block (DiscriminatorNet.backward) and the loss head runs on the chunked kernels of csrc/featloss.hip; 3 (the
@@ -265,7 +287,7 @@ class Stage1Step(_GanStepBase):
         self.extra_mu_decoder_pass = False   # DualStage1Step (wae_steps.py)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
-        self._init_extras(schedule, log)
+        self._init_extras(schedule, log, checkpoints)
 
     # ---- parameters -----------------------------------------------------------------------------
     def _subnets(self):
@@ -277,11 +299,8 @@ class Stage1Step(_GanStepBase):
         for _, n, _ in self._subnets():
             n.group.load_recipe(rs, perturb)
 
-    def state_dict(self):
-        sd = {}
-        for pre, n, _ in self._subnets():
-            sd.update(n.group.state_dict(pre))
-        return sd
+    def _state_groups(self):
+        return [(pre, n) for pre, n, _ in self._subnets()]
 
     def load_state_dict(self, sd):
         for pre, n, _ in self._subnets():
@@ -575,8 +594,9 @@ class CognitiveStep(_GanStepBase):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
-                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None):
-        """The discriminator keeps ``recon_level`` 3: the Stage-II / Stage-III scripts build theirs with the default
+                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None):
+        """``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step); the frozen networks and the teacher are state too.
+        The discriminator keeps ``recon_level`` 3: the Stage-II / Stage-III scripts build theirs with the default
         (train_vgan_stage2.py:213, train_vgan_stage3.py:231), so there is no such option here.
         ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule`` / ``log``: device-side epoch-end schedule and per-step training log (see Stage1Step).
@@ -614,7 +634,7 @@ class CognitiveStep(_GanStepBase):
         self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.cog), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
-        self._init_extras(schedule, log)
+        self._init_extras(schedule, log, checkpoints)
 
     def load_recipe(self, seed: int, perturb: bool = False):
         """Teacher VaeGan weights from seed, cognitive encoder from seed+100 (the golden-fixture recipe)."""
@@ -634,15 +654,11 @@ class CognitiveStep(_GanStepBase):
             nets.append(("teacher_net.encoder.", self.teacher_enc, None))
         return nets
 
-    def state_dict(self):
-        sd = {}
-        nets = self._subnets()
-        for pre, n, _ in nets:
-            sd.update(n.group.state_dict(pre))
+    def _state_groups(self):
+        nets = [(pre, n) for pre, n, _ in self._subnets()]
         if self.teacher_enc is not None:         # the teacher's decoder / discriminator are the model's own
-            for pre, n, _ in nets[1:3]:
-                sd.update(n.group.state_dict("teacher_net." + pre))
-        return sd
+            nets += [("teacher_net." + pre, n) for pre, n in nets[1:3]]
+        return nets
 
     def load_state_dict(self, sd):
         """A Stage-II / Stage-III checkpoint as the scripts write it (``model.state_dict()`` of ``VaeGanCognitive``):

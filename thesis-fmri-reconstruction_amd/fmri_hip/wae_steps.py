@@ -105,8 +105,9 @@ class WaeStep(_LatentDiscPhase, _StepBase):
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None):
-        """``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
+                 schedule=None, log=None, checkpoints=None):
+        """``checkpoints``: a fmri_hip.state.StateRing (see steps.Stage1Step); Adam's moments and step counts are state.
+        ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``) -- the scripts' three ``StepLR(step_size, gamma)``
         (train_wae_stage1.py:226-228, 334-336) on the device; all three optimizers follow it unless ``lr_mask`` says
         otherwise, and a margin / equilibrium / lambda_mse decay is a ValueError (a WAE step has none of them).
@@ -142,6 +143,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
                                      ("discriminator", self.opt_dis, self.wd)], 1)
         self._init_schedule(schedule)
         self._init_log(log)
+        self._init_checkpoints(checkpoints)
 
     # ---- parameters (the golden-fixture recipes of tests/golden/make_golden.py) --------------------------
     def load_recipe(self, seed: int, perturb: Optional[bool] = None):
@@ -156,14 +158,11 @@ class WaeStep(_LatentDiscPhase, _StepBase):
             self.cog.group.load_recipe(np.random.RandomState(seed + 100), True)
             self.wd.group.load_recipe(np.random.RandomState(seed + 200), True)
 
-    def state_dict(self):
-        sd = {}
-        sd.update(self.enc.group.state_dict("encoder."))
-        sd.update(self.dec.group.state_dict("decoder."))
-        sd.update(self.wd.group.state_dict("discriminator."))
+    def _state_groups(self):
+        nets = [("encoder.", self.enc), ("decoder.", self.dec), ("discriminator.", self.wd)]
         if self.stage > 1:
-            sd.update(self.img_enc.group.state_dict("teacher_net.encoder."))
-        return sd
+            nets.append(("teacher_net.encoder.", self.img_enc))
+        return nets
 
     # ---- the step --------------------------------------------------------------------------------------------
     def step(self, image: Optional[torch.Tensor] = None, z_fake_noise: Optional[torch.Tensor] = None,
@@ -338,8 +337,9 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
                  mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, recon_level: int = 3):
-        """``recon_level``: the script's ``--recon_level`` (wae_vgan_stage1.py:71,199), as in Stage1Step.
+                 schedule=None, log=None, recon_level: int = 3, checkpoints=None):
+        """``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step).
+        ``recon_level``: the script's ``--recon_level`` (wae_vgan_stage1.py:71,199), as in Stage1Step.
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
         (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step).
         ``schedule`` / ``log``: see Stage1Step.  By default the lr schedule covers what ``set_hyper(lr=)`` covers:
@@ -362,7 +362,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis),
                                      ("wae_discriminator", self.opt_wd, self.wd)], 2)
-        self._init_extras(schedule, log)         # (the base constructor ran with neither: ``optims`` was not complete)
+        self._init_extras(schedule, log, checkpoints)    # (the base constructor ran with none: ``optims`` was not complete)
 
     def _monitor_losses(self):
         return [self.scal[:len(LOG_KEYS)], self.wscal[:len(W_LOG_KEYS)]]
@@ -371,10 +371,17 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         super().load_recipe(seed, perturb)
         self.wd.group.load_recipe(np.random.RandomState(seed + 200), perturb)
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd.update(self.wd.group.state_dict("wae_discriminator."))
-        return sd
+    def _state_groups(self):
+        return super()._state_groups() + [("wae_discriminator.", self.wd)]
+
+    def _host_state(self):
+        """The iteration count behind ``torch14_zero_grad`` (it decides whether a step decays the decoder's RMSprop state
+        first); a recorded step has it baked in as > 0."""
+        return {"it": self._it}
+
+    def _restored(self, host):
+        super()._restored(host)
+        self._it = int(host.get("it", self._it))
 
     def step(self, x=None, eps=None, z_p=None, z_fake_noise=None):
         fed = self._fed(x)
