@@ -454,77 +454,76 @@ int permute_chw_launch(const float* s, float* d, int C, int HW, int to_engine, f
 }
 
 
+// The row of a device-resident table (rows in tile order, `tile_begin` = first block of a row) that blockIdx.x belongs
+// to.  Every wave counts for itself -- one ballot per 64 rows, no LDS, no barrier -- and the index is wave-uniform, so
+// the row's fields are read with scalar loads into SGPRs.
+template <typename Entry>
+__device__ __forceinline__ int table_row(const Entry* __restrict__ tab, int n) {
+    int cnt = 0;
+    for (int e0 = 0; e0 < n; e0 += 64) {
+        const int e = e0 + (int)(threadIdx.x & 63);
+        const bool ge = e < n && (int)blockIdx.x >= tab[e].tile_begin;
+        cnt += __popcll(__ballot(ge));
+    }
+    return __builtin_amdgcn_readfirstlane(cnt - 1);
+}
+
 // fp16 matrix transpose dst[c][r] = src[r][c] (r < R, c < C) in 64 x 64 tiles through LDS, 16-byte loads and stores.
 // The two GEMM orientations of a dense layer's weight are transposes of each other ([n][k] for the forward pass, [k][n]
 // for the data gradient, the (C,H,W) -> (H,W,C) permutation of the flatten already inside the column order): the second
 // copy is made from the first (2 + 2 bytes per element) instead of from the fp32 master (4 + 2).  Rows r >= R of src up
 // to Rbuf and columns up to lds exist and are zero (the pack kernels' padding contract), so whole 16-byte items are
 // read; dst's padding is never written.
-__global__ __launch_bounds__(256) void transpose_f16_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int R,
-                                                            int C, int Rbuf, int lds_, int ldd) {
-    __shared__ half_t t[64][72];
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+// A wave's store instruction covers whole 128-byte runs of destination rows: 8 lanes x 16 bytes per destination row, 8
+// rows per instruction (one 16-byte item per lane on 64 different rows before: no instruction wrote a whole line).  The
+// LDS pitch of 33 words (66 halves) puts the 8 source-row groups of such an instruction 8 banks apart; rows are then only
+// 4-byte aligned, so the tile is kept as words.
+constexpr int TR_PITCH = 33;
+__device__ __forceinline__ void transpose_tile(const half_t* __restrict__ src, half_t* __restrict__ dst, int r0, int c0, int R,
+                                               int C, int Rbuf, int width, int64_t lds_, int64_t ldd,
+                                               uint32_t (*t)[TR_PITCH]) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int e = threadIdx.x + 256 * k;          // 64 rows x 8 items
         const int r = e >> 3, ch = e & 7;
         h8 v = {};
-        if (r0 + r < Rbuf && c0 + ch * 8 + 8 <= lds_) v = *(const h8*)(src + (int64_t)(r0 + r) * lds_ + c0 + ch * 8);
-        *(h8*)&t[r][ch * 8] = v;
+        if (r0 + r < Rbuf && c0 + ch * 8 + 8 <= width) v = *(const h8*)(src + (int64_t)(r0 + r) * lds_ + c0 + ch * 8);
+        const u4 u = __builtin_bit_cast(u4, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[r][ch * 4 + j] = u[j];
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int e = threadIdx.x + 256 * k;          // 64 output rows (c) x 8 items of 8 source rows
-        const int c = e & 63, rh = e >> 6;
+        const int c = e >> 3, rh = e & 7;
         if (c0 + c < C && r0 + rh * 8 < R) {
-            h8 v;
+            typedef uint16_t us8 __attribute__((ext_vector_type(8)));
+            us8 v;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (r0 + rh * 8 + j < R) ? t[rh * 8 + j][c] : (half_t)0.f;
-            *(h8*)(dst + (int64_t)(c0 + c) * ldd + r0 + rh * 8) = v;
+            for (int j = 0; j < 8; ++j)
+                v[j] = (r0 + rh * 8 + j < R) ? (uint16_t)(t[rh * 8 + j][c >> 1] >> ((c & 1) * 16)) : (uint16_t)0;
+            *(us8*)(dst + (int64_t)(c0 + c) * ldd + r0 + rh * 8) = v;
         }
     }
+}
+__global__ __launch_bounds__(256) void transpose_f16_kernel(const half_t* __restrict__ src, half_t* __restrict__ dst, int R,
+                                                            int C, int Rbuf, int lds_, int ldd) {
+    __shared__ uint32_t t[64][TR_PITCH];
+    transpose_tile(src, dst, blockIdx.y * 64, blockIdx.x * 64, R, C, Rbuf, lds_, lds_, ldd, t);
 }
 // Batched form: every second-orientation fp16 copy of a sub-network in one launch, from a device-resident table.  A row
 // of the table is one 2-D transpose: a dense weight, or ONE TAP of one parity class of a stride-2 transposed convolution
 // (class block [ci][t' * Cop + co] = forward copy [co][t * Cip + ci]: the [co][ci] slice at column t * Cip of the source,
 // written at column t' * Cop of the class block).  `width` = source columns that may be read from src on (its row's end).
 __global__ __launch_bounds__(256) void transpose_f16_batch_kernel(const TransposeEntry* __restrict__ tab, int n) {
-    __shared__ half_t t[64][72];
-    __shared__ int sel;
-    if (threadIdx.x < 64) {
-        int cnt = 0;
-        for (int e = threadIdx.x; e < n; e += 64) cnt += (int)blockIdx.x >= tab[e].tile_begin ? 1 : 0;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s, 64);
-        if (threadIdx.x == 0) sel = cnt - 1;
-    }
-    __syncthreads();
-    const TransposeEntry& en = tab[sel];
+    __shared__ uint32_t t[64][TR_PITCH];
+    const TransposeEntry& en = tab[table_row(tab, n)];
     const int tile = blockIdx.x - en.tile_begin;
     const int ntc = (en.C + 63) / 64;
     const int r0 = (tile / ntc) * 64, c0 = (tile - (tile / ntc) * ntc) * 64;
-    const int R = en.R, C = en.C;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int e = threadIdx.x + 256 * k;
-        const int r = e >> 3, ch = e & 7;
-        h8 v = {};
-        if (r0 + r < en.Rbuf && c0 + ch * 8 + 8 <= en.width) v = *(const h8*)(en.src + (int64_t)(r0 + r) * en.lds + c0 + ch * 8);
-        *(h8*)&t[r][ch * 8] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int e = threadIdx.x + 256 * k;
-        const int c = e & 63, rh = e >> 6;
-        if (c0 + c < C && r0 + rh * 8 < R) {
-            h8 v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (r0 + rh * 8 + j < R) ? t[rh * 8 + j][c] : (half_t)0.f;
-            *(h8*)(en.dst + (int64_t)(c0 + c) * en.ldd + r0 + rh * 8) = v;
-        }
-    }
+    transpose_tile(en.src, en.dst, r0, c0, en.R, en.C, en.Rbuf, en.width, en.lds, en.ldd, t);
 }
 int transpose_batch_launch(const TransposeEntry* tab, int n, int total_tiles, hipStream_t st) {
     if (n < 1 || total_tiles < 1) return OK;
@@ -549,6 +548,14 @@ int transpose_f16_launch(const half_t* src, half_t* dst, int R, int C, int Rbuf,
 // The other orientation is still a pack launch.  1-D parameters (biases, BatchNorm gamma / beta) are kind-2 rows:
 // flat segments of the buffer whose gradients the backward pass accumulated in place; mode 2 clears those segments (the
 // start of a backward pass: instead of a memset of the whole gradient buffer).
+// Bytes per parameter, as the table asks for them: 16 (w and sq, read and written) + 2 where the row has an fp16 copy +
+// 4 per slab read (+ 4 per slab of a `clear` row); 22 for a one-slab tensor.  A row of kind 0 / 1 whose strides and base
+// pointers allow it (apply_entry_vec, recorded in ApplyEntry::pad_) moves all of that in 16-byte items in mode 1 (8-byte
+// items of the fp16 copy), with the w / sq loads of a tile issued before its slab sums meet at the first barrier; every
+// other row, and modes 0 / 3, take the scalar path.  Graph-replay time of the encoder's launch (18 M parameters, 420 MB):
+// 110 -> 76 us = 5.5 TB/s, 0.82 of what fmri_rmsprop_dev reaches on the same count (6.7 TB/s); the rest is the three
+// phases a tile still goes through (slab sums -> LDS -> update -> LDS -> fp16 copy), a tap's 256-byte and 128-byte
+// segments on the packed side, and five resident blocks per CU (92 VGPRs).  profiles/update_family_rate.md.
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float slab_sum(const float* q, int nslabs, int64_t slab_stride) {
     // (unpack_tile_kernel's order: four loads in flight)
@@ -577,22 +584,42 @@ __device__ __forceinline__ float rms_update(float g, float* w, float* sq, float 
     return nw;
 }
 
+// The 16-byte forms of the three helpers above, component by component the same float operations in the same order.
+__device__ __forceinline__ f4 slab_sum4(const float* q, int nslabs, int64_t slab_stride) {
+    f4 v0 = *(const f4*)q, v1 = {0.f, 0.f, 0.f, 0.f}, v2 = v1, v3 = v1;
+    int z = 1;
+    for (; z + 3 < nslabs; z += 4) {
+        v0 += *(const f4*)(q + z * slab_stride);
+        v1 += *(const f4*)(q + (z + 1) * slab_stride);
+        v2 += *(const f4*)(q + (z + 2) * slab_stride);
+        v3 += *(const f4*)(q + (z + 3) * slab_stride);
+    }
+    for (; z < nslabs; ++z) v0 += *(const f4*)(q + z * slab_stride);
+    return (v0 + v1) + (v2 + v3);
+}
+__device__ __forceinline__ void slab_clear4(float* q, int nslabs, int64_t slab_stride) {
+    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int z = 0; z < nslabs; ++z) *(f4*)(q + z * slab_stride) = zero;
+}
+// rms_update on values already in registers: `sq` is replaced by the new state, the new parameter is returned
+__device__ __forceinline__ float rms_step(float g, float w, float& sq, float gs, float lr, const ApplyOpt& o) {
+    float gg = g * gs;
+    if (o.clamp > 0.f) gg = fminf(fmaxf(gg, -o.clamp), o.clamp);
+    const float s = o.alpha * sq + (1.f - o.alpha) * gg * gg;
+    sq = s;
+    return w - lr * gg / (sqrtf(s) + o.eps);
+}
+// Bit 0 of ApplyEntry::pad_ (set by apply_entry_tiles): this row's strides and base pointers let mode 1 move it in
+// 16-byte items (8-byte items of the fp16 copy).
+constexpr int APPLY_VEC = 1;
+
 // STATS (fmri_apply_batch_stats): the true-scale gradient (before the clamp) and the new weight of every element this
 // thread updates go into `ga` / `pa` -- from the registers the update already holds, no extra loads
 template <bool STATS>
 __device__ __forceinline__ void apply_batch_body(const ApplyEntry* __restrict__ tab, int n, const ApplyOpt o,
                                                  StatAcc& ga, StatAcc& pa) {
-    __shared__ float t[64 * 65];
-    __shared__ int sel;
-    if (threadIdx.x < 64) {
-        int cnt = 0;
-        for (int e = threadIdx.x; e < n; e += 64) cnt += (int)blockIdx.x >= tab[e].tile_begin ? 1 : 0;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) cnt += __shfl_xor(cnt, s, 64);
-        if (threadIdx.x == 0) sel = cnt - 1;
-    }
-    __syncthreads();
-    const ApplyEntry& en = tab[sel];
+    __shared__ __attribute__((aligned(16))) float t[64 * 65];
+    const ApplyEntry& en = tab[table_row(tab, n)];
     const int tile = blockIdx.x - en.tile_begin;
     const bool update = o.mode == 1 || o.mode == 3;
     const bool from_grad = o.mode == 3;     // the gradient is read from the reference layout (summed over the ranks there)
@@ -620,6 +647,141 @@ __device__ __forceinline__ void apply_batch_body(const ApplyEntry* __restrict__ 
     }
     if (o.mode == 2) return;
     float* gsrc = const_cast<float*>(en.gsrc);
+    const bool vec = (en.pad_ & APPLY_VEC) && o.mode == 1;
+    if (en.kind == 1 && vec) {
+        // B % 4 == 0: an item of four elements never leaves its row; one item per thread
+        const int64_t total = (int64_t)en.TA * en.A * en.B;
+        const int64_t i = (int64_t)tile * APPLY_CHUNK + threadIdx.x * 4;
+        if (i >= total) return;
+        const int row = (int)(i / en.B), b = (int)(i - (int64_t)row * en.B);
+        const int ta = row / en.A, a = row - ta * en.A;
+        const int64_t off = a * en.sa + ta * en.sta + b;
+        f4 wv = {}, sv = {};
+        if (live) { wv = *(const f4*)(en.w + off); sv = *(const f4*)(en.sq + off); }
+        float* q = gsrc + (int64_t)row * en.ld + b;
+        const f4 v = slab_sum4(q, en.nslabs, en.slab_stride) * en.scale;
+        if (en.clear) slab_clear4(q, en.nslabs, en.slab_stride);
+        if (!live) return;
+        h4 hv;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float s = sv[c];
+            const float nw = rms_step(v[c], wv[c], s, gs, lr, o);
+            wv[c] = nw; sv[c] = s; hv[c] = (half_t)nw;
+            if (STATS) { stat_add_clamped(ga, v[c] * gs, o.clamp); stat_add(pa, nw); }
+        }
+        *(f4*)(en.sq + off) = sv;
+        *(f4*)(en.w + off) = wv;
+        if (en.pk) *(h4*)(en.pk + (int64_t)row * en.kpad + b) = hv;
+        return;
+    }
+    if (en.kind == 0 && vec) {
+        // sb == run: the tile's nb x run elements are ONE contiguous, 16-byte aligned run of w / sq.  Their loads are
+        // issued first, the slab sums go through LDS as in the scalar path, and the update reads both from registers.
+        const int bt = en.bt, sh = bt == 64 ? 6 : 5, run = en.run;
+        const int nbt = (en.B + bt - 1) / bt;
+        const int row = tile / nbt, b0 = (tile - row * nbt) * bt;
+        const int ta = row / en.A, a = row - ta * en.A;
+        const int stride = run | 1;
+        // LDS place of (bl, tap j).  run == 64 (the dense maps, where the parameters are): row bl rotated by 4 (bl / 4)
+        // words -- the transposing accesses (a lane owns four bl of one tap, 16 lanes a tap's 64 bl, a wave four taps)
+        // fall on 32 different banks, and four taps of one bl from a multiple of 4 on stay one aligned 16-byte item.
+        const bool r64 = run == 64;
+        auto li = [&](int bl, int j) { return r64 ? (bl << 6) + ((j + (bl & ~3)) & 63) : bl * stride + j; };
+        const int nb = min(bt, en.B - b0), nel = nb * run, nel4 = nel & ~3;
+        const int64_t base = a * en.sa + ta * en.sta + (int64_t)b0 * run;
+        float* wp = en.w + base;
+        float* sqp = en.sq + base;
+        f4 wv[4], sv[4];                                  // bt * run <= 4096: at most four items per thread
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int e = (threadIdx.x + 256 * k) * 4;
+                if (e < nel4) { wv[k] = *(const f4*)(wp + e); sv[k] = *(const f4*)(sqp + e); }
+            }
+        }
+        float* s = gsrc + (int64_t)row * en.ld + b0;
+        const int nit = run << (sh - 2);                  // items of four b: bt / 4 per tap
+        for (int it = threadIdx.x; it < nit; it += 256) {
+            const int tb = it >> (sh - 2), bl = (it & ((bt >> 2) - 1)) * 4;
+            float* q = s + tb * en.Bp + bl;
+            if (b0 + bl + 4 <= en.B) {
+                const f4 v = slab_sum4(q, en.nslabs, en.slab_stride);
+                if (en.clear) slab_clear4(q, en.nslabs, en.slab_stride);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) t[li(bl + c, tb)] = v[c];
+            } else {
+                for (int c = 0; c < 4 && b0 + bl + c < en.B; ++c) {   // the item that holds B: pad channels stay unread
+                    t[li(bl + c, tb)] = slab_sum(q + c, en.nslabs, en.slab_stride);
+                    if (en.clear) slab_clear(q + c, en.nslabs, en.slab_stride);
+                }
+            }
+        }
+        if (en.clear && b0 == 0)                          // the columns behind the taps (ld and run * Bp: multiples of 4)
+            for (int c = run * en.Bp + threadIdx.x * 4; c < en.ld; c += 1024)
+                slab_clear4(gsrc + (int64_t)row * en.ld + c, en.nslabs, en.slab_stride);
+        if (!live) return;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = (threadIdx.x + 256 * k) * 4;
+            if (e < nel4) {
+                f4 x;
+                int bl = r64 ? e >> 6 : e / run, j = e - bl * run;
+                if (r64) {
+                    x = *(const f4*)&t[li(bl, j)];
+                } else {
+                    int b2 = bl, j2 = j;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        x[c] = t[b2 * stride + j2];
+                        if (++j2 == run) { j2 = 0; ++b2; }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float v = x[c] * en.scale;
+                    float sc = sv[k][c];
+                    const float nw = rms_step(v, wv[k][c], sc, gs, lr, o);
+                    wv[k][c] = nw; sv[k][c] = sc;
+                    if (STATS) { stat_add_clamped(ga, v * gs, o.clamp); stat_add(pa, nw); }
+                }
+                if (r64) {
+                    *(f4*)&t[li(bl, j)] = wv[k];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        t[bl * stride + j] = wv[k][c];
+                        if (++j == run) { j = 0; ++bl; }
+                    }
+                }
+                *(f4*)(sqp + e) = sv[k];
+                *(f4*)(wp + e) = wv[k];
+            }
+        }
+        if ((int)threadIdx.x < nel - nel4) {              // a ragged tile of an odd run: up to three elements
+            const int e = nel4 + threadIdx.x, bl = e / run, j = e - bl * run;
+            const float v = t[li(bl, j)] * en.scale;
+            const float nw = rms_update(v, wp + e, sqp + e, gs, lr, o);
+            t[li(bl, j)] = nw;
+            if (STATS) { stat_add_clamped(ga, v * gs, o.clamp); stat_add(pa, nw); }
+        }
+        if (!en.pk) return;
+        __syncthreads();
+        half_t* d = en.pk + (int64_t)row * en.kpad + b0;
+        for (int it = threadIdx.x; it < nit; it += 256) {
+            const int tb = it >> (sh - 2), bl = (it & ((bt >> 2) - 1)) * 4;
+            if (b0 + bl + 4 <= en.B) {
+                h4 hv;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) hv[c] = (half_t)t[li(bl + c, tb)];
+                *(h4*)(d + tb * en.Bp + bl) = hv;
+            } else {
+                for (int c = 0; c < 4 && b0 + bl + c < en.B; ++c) d[tb * en.Bp + bl + c] = (half_t)t[li(bl + c, tb)];
+            }
+        }
+        return;
+    }
     if (en.kind == 1) {
         const int64_t total = (int64_t)en.TA * en.A * en.B;
         const int64_t i0 = (int64_t)tile * APPLY_CHUNK + threadIdx.x;
@@ -714,17 +876,29 @@ __global__ __launch_bounds__(256) void apply_batch_stats_kernel(const ApplyEntry
 
 // Completes a row of the table (kind, run, bt) from the tap geometry of its PackSpec and returns the number of blocks it
 // occupies; 0 = this tensor's layout map is not one the kernel knows (the caller keeps the separate launches).
+// Whether mode 1 may move a kind-0 / kind-1 row in 16-byte items: every item the vector path forms must start on a
+// 16-byte boundary of its buffer (8 bytes for the fp16 copy) and lie inside what the scalar path touches.  Bp is a
+// multiple of 8 by construction; a row that fails any condition keeps the scalar path.
+static bool apply_entry_vec(const ApplyEntry& e) {
+    const uintptr_t p = (uintptr_t)e.gsrc | (uintptr_t)e.w | (uintptr_t)e.sq;
+    if ((p & 15) || ((uintptr_t)e.pk & 7) || (e.pk && (e.kpad & 3))) return false;
+    if ((e.sa & 3) || (e.sta & 3) || (e.ld & 3) || (e.slab_stride & 3) || (e.Bp & 3)) return false;
+    return e.kind == 0 ? e.sb == e.run : (e.B & 3) == 0;
+}
 int apply_entry_tiles(ApplyEntry& e, int TH, int TW, int KW, int py, int px, int step, int64_t stb) {
+    e.pad_ = 0;
     if (e.kind == 2) return (int)((e.n + APPLY_CHUNK - 1) / APPLY_CHUNK);
     const int run = TH * TW;
     const int64_t rows = (int64_t)e.TA * e.A;
     if (run > 1 && run <= 64 && stb == 1 && py == 0 && px == 0 && step == 1 && TW == KW) {
         e.kind = 0; e.run = run; e.bt = e.B >= 64 ? 64 : 32;
+        e.pad_ = apply_entry_vec(e) ? APPLY_VEC : 0;
         const int64_t tiles = rows * ((e.B + e.bt - 1) / e.bt);
         return tiles < (1 << 24) ? (int)tiles : 0;
     }
     if (run == 1 && e.sb == 1) {
         e.kind = 1; e.run = 1; e.bt = 0;
+        e.pad_ = apply_entry_vec(e) ? APPLY_VEC : 0;
         const int64_t tiles = (rows * e.B + APPLY_CHUNK - 1) / APPLY_CHUNK;
         return tiles < (1 << 24) ? (int)tiles : 0;
     }
