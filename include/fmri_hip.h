@@ -874,6 +874,43 @@ int fmri_state_copy(const fmri_state_seg* segs_host, const fmri_state_seg* segs_
                     int64_t ring_bytes, int64_t slot_bytes, int dir, const int64_t* feed_state, int every, int capacity,
                     uint64_t fingerprint, const int64_t* log_counter, void* stream);
 
+/* ---- exponential moving average of the weights (csrc/ema.hip; fmri_hip/ema.py) -----------------------------------------
+ * Averaged weights ("shadows") of a fused step, kept on the device: per step and per element, in fp32 and in this order,
+ *     omd = 1.0f - d;  e = e + omd * (w - e)
+ * with w the live value, e its shadow and d the step's decay, derived by every block of the launch from the same 16-byte
+ * state block, which nothing in the launch writes (the step counter is advanced with fmri_counter_inc on &state->t,
+ * behind the last update launch of a step):
+ *     t < start:  d = 0 -- the shadow becomes a copy of the live value;
+ *     otherwise:  s = t - start,  d = warmup ? min(decay, (float)((1.0 + s) / (10.0 + s))) : decay  (quotient in double).
+ * A table lists the (live, shadow) pairs one launch covers; a chunk (FMRI_EMA_CHUNK floats of one segment) is what one
+ * 256-thread block moves: four 16-byte accesses per lane and side in flight when both bases of the segment are 16-byte
+ * aligned (plus a dword tail), dword by dword otherwise.  No byte outside [base, base + 4 n) of either side is touched.
+ * Plain vector loads and stores: no atomics, no allocation; enqueue-only and capturable. */
+#define FMRI_EMA_CHUNK 4096
+typedef struct fmri_ema_seg {
+    float* live;                                 /* device address of the tensor, a multiple of 4 */
+    float* shadow;                               /* device address of its average, a multiple of 4 */
+    int64_t n;                                   /* floats, >= 0 (0: the pointers are not looked at) */
+    int64_t chunk0;                              /* chunks of the segments in front of it (the prefix a block searches) */
+} fmri_ema_seg;                                  /* 32 bytes */
+typedef struct fmri_ema_state {
+    int32_t t;                                   /* steps averaged so far */
+    int32_t start;                               /* steps t < start copy */
+    float decay;                                 /* in [0, 1) */
+    int32_t warmup;                              /* 0 / 1 */
+} fmri_ema_state;                                /* 16 bytes */
+/* host only: the decay d of step t, from the expression the kernel evaluates. */
+float fmri_ema_decay_at(int32_t t, int32_t start, float decay, int32_t warmup);
+/* One launch over all segments of the table.  segs_host: the table in host memory, checked here on every call -- n >= 0,
+ * chunk0 the running chunk count, both addresses of a segment with n > 0 non-NULL multiples of 4 -- and segs_dev its copy
+ * in device memory, which the kernel reads; state_dev: the fmri_ema_state in device memory, a multiple of 4.  Grid:
+ * min(chunks, 2048) blocks, grid-stride; a table of empty segments launches nothing.  nseg < 0, a NULL table with
+ * nseg > 0, a NULL state or a table that fails the checks: FMRI_E_BADARG, nothing is launched. */
+int fmri_ema_update(const fmri_ema_seg* segs_host, const fmri_ema_seg* segs_dev, int nseg,
+                    const fmri_ema_state* state_dev, void* stream);
+/* live <-> shadow of every segment, moved as 32-bit words: bit for bit, NaN payloads included.  Checks as above. */
+int fmri_ema_swap(const fmri_ema_seg* segs_host, const fmri_ema_seg* segs_dev, int nseg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

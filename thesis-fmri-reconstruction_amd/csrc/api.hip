@@ -1294,6 +1294,24 @@ int fmri_state_copy(const fmri_state_seg* segs_host, const fmri_state_seg* segs_
     return state_copy_launch(segs_dev, nseg, chunks, ring, slot_bytes, dir, feed_state, every, capacity, fingerprint,
                              log_counter, S(stream));
 }
+float fmri_ema_decay_at(int32_t t, int32_t start, float decay, int32_t warmup) {
+    return ema_decay_at(t, start, decay, warmup);
+}
+static int ema_call(const fmri_ema_seg* segs_host, const fmri_ema_seg* segs_dev, int nseg, const void* state_dev, int op,
+                    void* stream) {
+    if (nseg < 0 || (nseg > 0 && (!segs_host || !segs_dev || ((uintptr_t)segs_dev & 7)))) return FMRI_E_BADARG;
+    if (op == 0 && (!state_dev || ((uintptr_t)state_dev & 3))) return FMRI_E_BADARG;
+    const int64_t chunks = ema_table_chunks(segs_host, nseg);
+    if (chunks < 0) return FMRI_E_BADARG;
+    return ema_launch(segs_dev, nseg, chunks, state_dev, op, S(stream));
+}
+int fmri_ema_update(const fmri_ema_seg* segs_host, const fmri_ema_seg* segs_dev, int nseg,
+                    const fmri_ema_state* state_dev, void* stream) {
+    return ema_call(segs_host, segs_dev, nseg, state_dev, 0, stream);
+}
+int fmri_ema_swap(const fmri_ema_seg* segs_host, const fmri_ema_seg* segs_dev, int nseg, void* stream) {
+    return ema_call(segs_host, segs_dev, nseg, nullptr, 1, stream);
+}
 int fmri_axpby_f16(const void* x, const void* y, void* out, int64_t n, float a, float b, const float* a_dev,
                    void* stream) {
     if (!x || !out || (n & 7)) return FMRI_E_BADARG;

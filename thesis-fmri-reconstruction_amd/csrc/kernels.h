@@ -292,6 +292,11 @@ int64_t state_table_chunks(const void* segs_host, int nseg, int64_t slot_bytes);
 int state_copy_launch(const void* segs_dev, int nseg, int64_t chunks, void* ring, int64_t slot_bytes, int dir,
                       const int64_t* feed_state, int every, int capacity, uint64_t fingerprint,
                       const int64_t* log_counter, hipStream_t st);
+// csrc/ema.hip (`segs`: fmri_ema_seg tables, `state`: an fmri_ema_state of include/fmri_hip.h; ema_table_chunks: the host
+// check of a table, its chunk count or E_BADARG; op 0 updates the shadows, 1 exchanges live and shadow)
+float ema_decay_at(int32_t t, int32_t start, float decay, int32_t warmup);
+int64_t ema_table_chunks(const void* segs_host, int nseg);
+int ema_launch(const void* segs_dev, int nseg, int64_t chunks, const void* state_dev, int op, hipStream_t st);
 int axpby_f16_launch(const half_t* x, const half_t* y, half_t* out, int64_t n, float a, float b, const float* pa,
                      const float* pb, hipStream_t st);
 int sumsq_launch(const float* x, int64_t n, float* acc, hipStream_t st);

@@ -90,15 +90,23 @@ class Evaluator:
     reconstructions and, with ``generate=g > 0`` (needs an ``rng``), of an eval-mode decoder forward of g rows of N(0, I)
     (``model(None, g)``).  ``dump`` (egress.ImageDump): ``run()`` also writes every reconstruction and every ingested
     image of the pass, normalised per image and resized, as ``evaluate(save=True)`` writes its files.  Without the three
-    a pass enqueues exactly what it did before them.
+    a pass enqueues exactly what it did before them.  ``weights``: ``"live"`` (default) the weights of the last step;
+    ``"ema"`` the step's averaged ones (a step built with ``ema=WeightEma(...)``, fmri_hip/ema.py) -- ``run()`` only,
+    ``train_batch()`` reads the training step's own tensors.  Two evaluators whose generators share a seed make a paired
+    comparison.
 
     With ``distributed=True`` steps every rank evaluates the whole set by itself: there is no collective in a pass."""
 
     def __init__(self, step, dataset: DeviceDataset, batch: int, rng: Optional[DeviceRng] = None,
                  mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), denorm: bool = False, capacity: int = 1024,
-                 identify: Optional[int] = None, grids=None, dump=None, generate: int = 0):
+                 identify: Optional[int] = None, grids=None, dump=None, generate: int = 0, weights: str = "live"):
         from .steps import CognitiveStep, Stage1Step
         from .wae_steps import WaeStep
+        if weights not in ("live", "ema"):
+            raise ValueError(f"Evaluator: weights must be 'live' or 'ema', got {weights!r}")
+        if weights == "ema" and getattr(step, "ema", None) is None:
+            raise ValueError("Evaluator: weights='ema' needs a step constructed with ema=WeightEma(...)")
+        self.weights = weights
         if isinstance(step, WaeStep):
             self.enc, self.uses_fmri, self.samples = (step.img_enc if step.stage == 1 else step.cog), step.stage > 1, False
         elif isinstance(step, CognitiveStep):
@@ -264,7 +272,15 @@ class Evaluator:
         self.grids.write("random", self._gen16)
 
     def run(self):
-        """One pass over the validation set in eval mode and one row in the ring; enqueues only."""
+        """One pass over the validation set in eval mode and one row in the ring; enqueues only.  ``weights="ema"``: the
+        whole pass runs inside ``step.ema.swapped()`` -- the same columns, grids and dumps from the averaged weights."""
+        if self.weights == "ema":
+            with self.step.ema.swapped():
+                self._run()
+        else:
+            self._run()
+
+    def _run(self):
         ops.require_gpu(self.ds.images)
         bns = [bn for net in (self.enc, self.dec) for bn in net.all_bns()]
         was = [bn.eval_mode for bn in bns]

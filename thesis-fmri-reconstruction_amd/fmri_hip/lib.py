@@ -113,6 +113,8 @@ _SIGS = {
     "fmri_trainlog_append": [_p, _p, _i, _p, _l, _p, _p],
     "fmri_state_nontemporal": [_i],
     "fmri_state_copy": [_p, _p, _i, _p, _l, _l, _i, _p, _i, _i, C.c_uint64, _p, _p],
+    "fmri_ema_update": [_p, _p, _i, _p, _p],
+    "fmri_ema_swap": [_p, _p, _i, _p],
     "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
     "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
     "fmri_sumsq": [_p, _l, _p, _p],
@@ -149,6 +151,11 @@ class StateSeg(C.Structure):
     _fields_ = [("live", C.c_void_p), ("offset", C.c_int64), ("bytes", C.c_int64), ("chunk0", C.c_int64)]
 
 
+class EmaSeg(C.Structure):
+    """``fmri_ema_seg`` of include/fmri_hip.h (one (live, shadow) pair of a weight-average table)."""
+    _fields_ = [("live", C.c_void_p), ("shadow", C.c_void_p), ("n", C.c_int64), ("chunk0", C.c_int64)]
+
+
 class Schedule(C.Structure):
     """``fmri_schedule`` of include/fmri_hip.h (the device-resident state of an epoch-end schedule)."""
     _fields_ = [("lr_base", C.c_double * 4), ("margin_base", C.c_double), ("equilibrium_base", C.c_double),
@@ -162,6 +169,7 @@ SCHED_MAX_LR = 4         # FMRI_SCHED_MAX_LR
 STATE_MAGIC = 0x31544154534d4621     # FMRI_STATE_MAGIC
 STATE_HEADER = 64        # FMRI_STATE_HEADER
 STATE_CHUNK = 16384      # FMRI_STATE_CHUNK
+EMA_CHUNK = 4096         # FMRI_EMA_CHUNK (floats)
 STAT_BYTES = 32          # sizeof(fmri_stat)
 STAT_MAX_SEGS = 8        # FMRI_STAT_MAX_SEGS
 
@@ -174,7 +182,7 @@ EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_
                              "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
                              "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
                              "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes", "fmri_images_u8_ws_bytes",
-                             "fmri_images_u8_out_bytes", "fmri_state_layout",
+                             "fmri_images_u8_out_bytes", "fmri_state_layout", "fmri_ema_decay_at",
                              "fmri_tensor_stats_ws_bytes", "fmri_feat_mse_wide_chunk", "fmri_feat_mse_wide_ws_floats"])
 
 _lib = None
@@ -223,6 +231,8 @@ def load():
     lib.fmri_images_u8_out_bytes.argtypes = [_i, _i, _i, _i, _i, _i, _i]
     lib.fmri_state_layout.restype = _l
     lib.fmri_state_layout.argtypes = [_p, _i, _p]
+    lib.fmri_ema_decay_at.restype = _f
+    lib.fmri_ema_decay_at.argtypes = [C.c_int32, C.c_int32, _f, C.c_int32]
     lib.fmri_tensor_stats_ws_bytes.restype = _i
     lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
     lib.fmri_feat_mse_wide_chunk.restype = _i

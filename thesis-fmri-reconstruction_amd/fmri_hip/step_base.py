@@ -39,6 +39,7 @@ class _Optim:
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=group.device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=group.device) if kind == "adam" else None
         self.stats = None        # (monitor.Monitor, device address of its record pair): set by a monitored step
+        self.ema = None          # zero-argument launch of the group's weight average (ema.WeightEma.attach), or None
         self.scheduled = False   # an attached schedule.EpochSchedule writes lr_dev (set_lr then raises)
 
     @property
@@ -52,6 +53,13 @@ class _Optim:
         self.lr_dev.fill_(float(lr))
 
     def step(self, flag: Optional[torch.Tensor] = None, clamp: float = 0.0, gdev: Optional[torch.Tensor] = None):
+        """The update, and directly behind it on the same stream -- whether or not ``flag`` let the update happen -- the
+        group's weight average (``ema=`` of the step classes)."""
+        self._update(flag, clamp, gdev)
+        if self.ema is not None:
+            self.ema()
+
+    def _update(self, flag, clamp, gdev):
         g = self.g
         mon, rec = self.stats if self.stats is not None else (None, None)
         if self.kind == "rmsprop" and ops.apply_group(g, self.s1, self.lr_dev, self.alpha, self.eps, flag, gdev, clamp,
@@ -242,6 +250,7 @@ class _StepBase(Monitored):
     schedule: Optional[EpochSchedule] = None
     log: Optional[TrainLog] = None
     checkpoints: Optional[StateRing] = None
+    ema = None                                   # fmri_hip.ema.WeightEma or None
     _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
@@ -288,6 +297,28 @@ class _StepBase(Monitored):
         cols, losses = self._log_columns()
         self._epoch_dev = torch.full((1,), -1, dtype=torch.int64, device=self.device)
         log.attach(self.device, list(cols) + [("epoch", self._epoch_dev, 0)] + lr_columns(self.optims), losses)
+
+    # ---- weight average (fmri_hip/ema.py) ------------------------------------------------------------------------------
+    def _trained(self) -> List[str]:
+        """Names (``OPTIM_NAMES``) of the optimizers the step runs every batch -- the networks that can have an average;
+        a subclass with frozen networks says which."""
+        return [n for n, _ in zip(OPTIM_NAMES, self.optims)]
+
+    def _init_ema(self, ema):
+        """``ema=`` of the step classes, after ``optims`` is complete and before ``_init_checkpoints`` (the ring sees the
+        shadows).  None: nothing is added -- the step issues the launches it always did."""
+        self.ema = ema
+        if ema is not None:
+            ema.attach(self)
+            self._pre_replay.append(ema.prime)
+
+    def ema_state_dict(self):
+        """``state_dict()`` with the averaged weights and BatchNorm statistics of the shadowed networks in place of the live
+        ones (everything else -- ``num_batches_tracked``, the other networks -- is the live value): loadable wherever
+        ``state_dict()`` is.  Device tensors, no sync."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dict(): the step was constructed without ema=WeightEma(...)")
+        return self.ema.state_dict()
 
     def _epoch_begin(self):
         """The launch in FRONT of the feed's draws: the feed's state still holds the epoch of the batch about to be drawn.
@@ -370,6 +401,8 @@ class _StepBase(Monitored):
         if self.log is not None:
             out["log"] = self.log.blk
             out["log_epoch"] = self._epoch_dev
+        if self.ema is not None:
+            out.update(self.ema.state_tensors())
         return out
 
     def _state_signature(self) -> List[str]:
@@ -382,11 +415,21 @@ class _StepBase(Monitored):
             sig.append(f"recon_level={self.dis.level}")
         sig.append("optims=" + ",".join(f"{n}:{o.kind}" for n, o in zip(OPTIM_NAMES, self.optims)))
         sig.append("log=" + ("none" if self.log is None else ",".join(self.log.names) + f"@{self.log.capacity}"))
+        if self.ema is not None:
+            sig.append(self.ema.signature())
         return sig
 
     def _host_state(self) -> dict:
         """Host-side counters a resumed run needs (TrainState.meta["host"]); none here."""
         return {}
+
+    def _host_meta(self) -> dict:
+        """``_host_state()`` and, with ``ema=``, where the state-dict entries sit in the shadows (WeightEma.state_dict_of
+        reads a saved state without a step)."""
+        host = dict(self._host_state())
+        if self.ema is not None:
+            host["ema"] = self.ema.layout()
+        return host
 
     def _restored(self, host: dict):
         """Host copies of restored device values (``restore`` has synchronised): learning rates, Adam's step count, the
@@ -412,7 +455,8 @@ class _StepBase(Monitored):
         keys = [pre + k for pre, n in self._state_groups() for k, _, _ in n.group.spec]
         ring.attach(self.device, segs, self._state_signature(), keys,
                     self.feed._state if self.feed is not None else None,
-                    self.log.counter if self.log is not None else None, self._host_state)
+                    self.log.counter if self.log is not None else None,
+                    self._host_state if self.ema is None else self._host_meta)
 
     def _state_ready(self, between_steps: bool = False):
         """In front of a snapshot launch: the optimizer updates of the eager two-stream mode run on the side stream, so the
@@ -454,6 +498,8 @@ class _StepBase(Monitored):
         ops.join_side()
         for bn in self._lazy_bns():
             bn._running_in()                     # a pending reload from the reference-order buffers would undo the restore
+        if self.ema is not None:
+            self.ema.mark_loaded()               # as would a pending copy of loaded weights into the shadows
         ring.scatter(blob)
         for n in self._state_nets():
             n.group.drop_pending()
@@ -464,7 +510,10 @@ class _StepBase(Monitored):
         torch.cuda.current_stream().synchronize()
 
     def _log_append(self):
-        """The last launch of a step: behind the gate, the loss all-reduce and every kernel that writes a logged value."""
+        """The last launch of a step: behind the gate, the loss all-reduce and every kernel that writes a logged value.  In
+        front of it, with ``ema=``, the tail of the weight average: the BatchNorm buffers' launch and the step counter."""
+        if self.ema is not None:
+            self.ema.finish()
         if self.log is not None:
             self.log.append()
 
@@ -490,6 +539,8 @@ class _StepBase(Monitored):
         (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
         generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
         the noise and the augmentation draws.  A schedule / log puts ONE launch in front of the feed's (``_epoch_begin``)."""
+        if self.ema is not None:
+            self.ema.prime()                     # host check: weights loaded from outside since the last step
         feed = self.feed
         if feed is None:
             if any(g is None for g in given):

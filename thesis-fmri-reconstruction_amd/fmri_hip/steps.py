@@ -200,11 +200,12 @@ class _GanStepBase(_StepBase):
         cols = [(k, self.scal, i) for i, k in enumerate(LOG_KEYS)]
         return cols + [("train_dis", self.flags, 0), ("train_dec", self.flags, 1)], LOG_KEYS
 
-    def _init_extras(self, schedule, log, checkpoints=None):
-        """``schedule=`` / ``log=`` / ``checkpoints=`` once ``optims`` is complete.  lr: encoder, decoder, discriminator,
-        as ``set_hyper``."""
+    def _init_extras(self, schedule, log, checkpoints=None, ema=None):
+        """``schedule=`` / ``log=`` / ``ema=`` / ``checkpoints=`` once ``optims`` is complete.  lr: encoder, decoder,
+        discriminator, as ``set_hyper``."""
         self._init_schedule(schedule, [i < 3 for i in range(len(self.optims))], self.hp, self.hp_dev)
         self._init_log(log)
+        self._init_ema(ema)
         self._init_checkpoints(checkpoints)
 
     def _state_tensors(self):
@@ -237,8 +238,12 @@ class Stage1Step(_GanStepBase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
                  monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None,
-                 recon_level: int = 3, checkpoints=None):
-        """``checkpoints``: a fmri_hip.state.StateRing; with its ``every`` set, one predicated launch behind
+                 recon_level: int = 3, checkpoints=None, ema=None):
+        """``ema``: a fmri_hip.ema.WeightEma; the step then keeps an exponential moving average of the weights and BatchNorm
+        statistics of the networks it names (default: the trained ones the eval forward uses) on the device -- one launch
+        behind every optimizer update, two at the end of the step, recorded steps included; ``ema_state_dict()`` reads it,
+        ``Evaluator(..., weights="ema")`` evaluates with it.  None: nothing is added.
+        ``checkpoints``: a fmri_hip.state.StateRing; with its ``every`` set, one predicated launch behind
         ``fmri_epoch_begin`` keeps the whole training state of the epochs the scripts save (``idx_epoch % every == 0``) in a
         device ring, recorded steps included; ``snapshot()`` takes the state now, ``ring.states()`` reads the ring with
         one sync and ``restore(state)`` continues a run bit for bit (fmri_hip/state.py).  None: nothing is added.
@@ -287,12 +292,16 @@ class Stage1Step(_GanStepBase):
         self.extra_mu_decoder_pass = False   # DualStage1Step (wae_steps.py)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
-        self._init_extras(schedule, log, checkpoints)
+        self._init_extras(schedule, log, checkpoints, ema)
 
     # ---- parameters -----------------------------------------------------------------------------
     def _subnets(self):
         """(state-dict prefix, network, slot of the device factor its gradients carry) per sub-network."""
         return (("encoder.", self.enc, S_NE), ("decoder.", self.dec, S_GDEC), ("discriminator.", self.dis, S_NA))
+
+    def _trained(self):
+        """'dcgan' never steps the encoder (``apply``)."""
+        return [n for n in super()._trained() if not (n == "encoder" and self.mode == "dcgan")]
 
     def load_recipe(self, seed: int, perturb: bool = False):
         rs = np.random.RandomState(seed)
@@ -532,6 +541,8 @@ class Stage1Step(_GanStepBase):
         fw_captured = self.fw                 # the tensors the recorded forward writes
 
         def run():
+            if self.ema is not None:
+                self.ema.prime()
             for n in nets:
                 refresh_net(n)               # no-ops for the sub-networks the last backward refreshed early
             graph.replay()
@@ -594,8 +605,10 @@ class CognitiveStep(_GanStepBase):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
-                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None):
-        """``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step); the frozen networks and the teacher are state too.
+                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None, ema=None):
+        """``ema``: a fmri_hip.ema.WeightEma (see Stage1Step): by default the cognitive encoder in Stage II, the decoder in
+        Stage III -- a frozen network has no average.
+        ``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step); the frozen networks and the teacher are state too.
         The discriminator keeps ``recon_level`` 3: the Stage-II / Stage-III scripts build theirs with the default
         (train_vgan_stage2.py:213, train_vgan_stage3.py:231), so there is no such option here.
         ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
@@ -634,7 +647,10 @@ class CognitiveStep(_GanStepBase):
         self.optims = [self.opt_enc, self.opt_dec, self.opt_dis]
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.cog), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis)], 1)
-        self._init_extras(schedule, log, checkpoints)
+        self._init_extras(schedule, log, checkpoints, ema)
+
+    def _trained(self):
+        return ["encoder", "discriminator"] if self.stage == 2 else ["decoder", "discriminator"]
 
     def load_recipe(self, seed: int, perturb: bool = False):
         """Teacher VaeGan weights from seed, cognitive encoder from seed+100 (the golden-fixture recipe)."""

@@ -105,8 +105,9 @@ class WaeStep(_LatentDiscPhase, _StepBase):
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, checkpoints=None):
-        """``checkpoints``: a fmri_hip.state.StateRing (see steps.Stage1Step); Adam's moments and step counts are state.
+                 schedule=None, log=None, checkpoints=None, ema=None):
+        """``ema``: a fmri_hip.ema.WeightEma (see steps.Stage1Step) over the networks this stage trains.
+        ``checkpoints``: a fmri_hip.state.StateRing (see steps.Stage1Step); Adam's moments and step counts are state.
         ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``) -- the scripts' three ``StepLR(step_size, gamma)``
         (train_wae_stage1.py:226-228, 334-336) on the device; all three optimizers follow it unless ``lr_mask`` says
@@ -143,7 +144,14 @@ class WaeStep(_LatentDiscPhase, _StepBase):
                                      ("discriminator", self.opt_dis, self.wd)], 1)
         self._init_schedule(schedule)
         self._init_log(log)
+        self._init_ema(ema)
         self._init_checkpoints(checkpoints)
+
+    def _trained(self):
+        """Stage II freezes the decoder, Stage III the cognitive encoder; the latent discriminator trains under the GAN
+        penalty only."""
+        on = {"encoder": self.stage != 3, "decoder": self.stage != 2, "discriminator": self.penalty == "gan"}
+        return [n for n in super()._trained() if on[n]]
 
     # ---- parameters (the golden-fixture recipes of tests/golden/make_golden.py) --------------------------
     def load_recipe(self, seed: int, perturb: Optional[bool] = None):
@@ -337,8 +345,9 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
                  mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, recon_level: int = 3, checkpoints=None):
-        """``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step).
+                 schedule=None, log=None, recon_level: int = 3, checkpoints=None, ema=None):
+        """``ema``: a fmri_hip.ema.WeightEma (see Stage1Step); ``"wae_discriminator"`` names the latent discriminator.
+        ``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step).
         ``recon_level``: the script's ``--recon_level`` (wae_vgan_stage1.py:71,199), as in Stage1Step.
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
         (see Stage1Step).  ``feed``: a fmri_hip.feed.DeviceFeed; ``step()`` then draws its batch itself (Stage1Step).
@@ -362,7 +371,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.dis),
                                      ("wae_discriminator", self.opt_wd, self.wd)], 2)
-        self._init_extras(schedule, log, checkpoints)    # (the base constructor ran with none: ``optims`` was not complete)
+        self._init_extras(schedule, log, checkpoints, ema)    # (the base constructor ran with none: ``optims`` was not complete)
 
     def _monitor_losses(self):
         return [self.scal[:len(LOG_KEYS)], self.wscal[:len(W_LOG_KEYS)]]
