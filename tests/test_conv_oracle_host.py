@@ -16,7 +16,7 @@ def _rel(got, ref):
     return float((got - ref).abs().max() / ref.abs().max())
 
 
-SIZES = [(9, 11), (13, 7), (16, 16), (25, 25)]
+SIZES = [(9, 11), (13, 7), (16, 16), (25, 25), (50, 50)]
 
 
 @pytest.mark.parametrize("chunk", [None, 1, 2])
@@ -85,7 +85,7 @@ def test_route_table_is_what_the_library_and_run_wgrad_give():
     from fmri_hip import lib, ops
     L = lib.load()
     assert (ops._WW_SLABS, ops._WW_SIDE_BLOCKS, ops._WW_BLOCKS, ops._WW_ON, ops._WN_ON) == (24, 160, 0, True, True)
-    assert set(T.ROUTES) == {name for name, _ in T.CASES} and len(T.CASES) == 22
+    assert set(T.ROUTES) == {name for name, _ in T.CASES} and len(T.CASES) == 44
     for name, case in T.CASES:
         kind, cin, cout, stride, H, op, N = case
         g = T.geometry(*case)
@@ -149,6 +149,16 @@ def test_route_table_covers_the_piece_edges():
     assert any(r[0][1] == 1 and r[0][2] > 1 for r in generic), "generic kernel, K splits in atomic mode"
     assert any(r[2][1] == 4 and r[2][3] == r[2][2] for r in generic), "generic kernel, slab mode 4, every slab stored"
     assert any(r[2][1] == 4 and 0 < r[2][3] < r[2][2] for r in generic), "slab mode 4, fewer slabs stored than allocated"
+    # ... at two different ratios at least (the K steps of the 100-px planes do not divide by the split count)
+    short = {(r[2][3], r[2][2]) for r in generic if r[2][1] == 4 and 0 < r[2][3] < r[2][2]}
+    assert len({stored / alloc for stored, alloc in short}) >= 2 and {(278, 312), (500, 512), (22, 24)} <= short, short
+    # the role-exchanged generic route with 64-row tiles (decoder.conv.3 at 64 input channels)
+    assert any(g["flip"] and g["A"] == 64 and r[0][0] == "generic" and r[0][2] > 1 and r[2][1] == 4
+               for _, g, r in routes), "generic kernel, role-exchanged, 64-row tiles"
+    # window-kernel pieces of fewer than 8 tiles on planes of partial tiles (a plane side that is no multiple of 8)
+    partial = [r for r in slab if T.geometry(*dict(T.CASES)[r[0]])["Yc"] % 8 and min(r[5]) < 8]
+    assert {r[1] for r in partial} == set(T.SETTINGS), "pieces of fewer than 8 tiles, partial tiles, every setting"
+    assert any(min(r[5]) == 2 for r in partial) and any(max(r[5]) == 5 for r in partial), "2 - 5 tiles per piece"
 
 
 def test_cases_are_the_full_size_list_plus_the_edges():
@@ -158,4 +168,64 @@ def test_cases_are_the_full_size_list_plus_the_edges():
     # the epilogue layers are the stride-1 / stride_gan first discriminator layer and the decoder's last layer
     for name, act in T.EPILOGUE.items():
         kind, cin, cout = dict(T.CASES)[name][:3]
-        assert (kind, cin, cout) == (("conv", 3, 32) if act == T.RELU else ("conv", 32, 3))
+        assert (kind, cin, cout) in ([("conv", 3, 32)] if act == T.RELU else [("conv", 32, 3), ("conv", 64, 3)])
+    tanh_layers = {n for n, act in T.EPILOGUE.items() if act == T.TANH}
+    assert tanh_layers == {"decoder.conv.3", "decoder.conv.3 @128", "decoder.conv.3 @100"}
+    assert {dict(T.CASES)[n][:3] for n in tanh_layers} == {("conv", 32, 3), ("conv", 64, 3)}
+    # the 100-px family: the eleven layers at the shipped batch and at the remainder batch, in that order
+    assert [n for n, _ in T.CASES[22:]] == [n for n, _ in T.PX100_CASES] and len(T.PX100_CASES) == 22
+    assert [c[6] for _, c in T.PX100_CASES] == [64] * 3 + [128] * 4 + [192] * 4 + [5] * 3 + [10] * 4 + [15] * 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# forward / data-gradient kernels of the 100-px family
+# ---------------------------------------------------------------------------------------------------------------------
+def _launches():
+    """(case name, kernel family, instantiation, epilogue or None, side of the plane the kernel tiles) of every launch
+    KERNELS states.  The window kernels of the stride-2 convolution (c5 / c5w) tile the output plane, those of the
+    transposed convolution (tc5 / tc5w / tc32) the parity-class grid, ceil(output side / 2); the generic kernel tiles
+    the flattened pixels of all images in 128."""
+    out = []
+    for name, case in T.PX100_CASES:
+        kind, cin, cout, stride, H, op, N = case
+        Ho = T.geometry(*case)["Ho"]
+        fwd_out, dgr_out = Ho, H                                       # output plane of the forward / the data gradient
+        for which, kname in enumerate(T.KERNELS[name]):
+            if kname is None:
+                continue
+            side = fwd_out if which < 2 else dgr_out
+            family = kname.split("::")[1].split("<")[0]
+            ep = T.EPILOGUE.get(name) if which == 1 else None
+            if family == "igemm_kernel":
+                out.append((name, family, kname, ep, N * side * side, 128))
+            elif family in ("igemm_c5_kernel", "igemm_c5w_kernel"):
+                out.append((name, family, kname, ep, side, 8))
+            else:
+                assert family in ("igemm_tc5_kernel", "igemm_tc5w_kernel", "igemm_tc32_kernel"), kname
+                out.append((name, family, kname, ep, (side + 1) // 2, 8))
+    return out
+
+
+def test_kernel_table_is_what_the_library_routes_to_and_covers_the_families():
+    """KERNELS, written out in the GPU module, equals what ops.igemm_route gives for the arguments ConvLayer hands over
+    (no GPU: the library's routing is host code); and the family as a whole meets every window kernel and the generic
+    kernel on a plane that is no multiple of its tile, the generic kernel also with the tanh epilogue."""
+    assert set(T.KERNELS) == {n for n, _ in T.PX100_CASES}
+    for name, case in T.PX100_CASES:
+        got = T.igemm_kernels(name, case)
+        assert got == T.KERNELS[name], (name, got, T.KERNELS[name])
+        print(f"[fullbatch-conv] kernels {name:32s} {got}")
+    launches = _launches()
+    # every tile edge of the window kernels is 8 or 16 (8 x 8, 8 x 16, 16 x 16): a side that is no multiple of 8 is a
+    # multiple of none of them; the generic kernel's last 128-pixel tile is partial when the pixel count is no multiple
+    ragged = {family for _, family, _, _, extent, tile in launches if extent % tile}
+    assert {"igemm_tc5_kernel", "igemm_tc5w_kernel", "igemm_tc32_kernel", "igemm_kernel"} <= ragged, ragged
+    assert ragged & {"igemm_c5_kernel", "igemm_c5w_kernel"}, ragged
+    assert any(family == "igemm_kernel" and ep == T.TANH for _, family, _, ep, _, _ in launches), \
+        "generic kernel with the tanh epilogue"
+    assert any(family == "igemm_kernel" and ep == T.RELU for _, family, _, ep, _, _ in launches)
+    # both tile widths of the wide window kernels, and the ReLU-mask form of igemm_tc32, on such planes
+    names = {kname for _, _, kname, _, extent, tile in launches if extent % tile}
+    assert {"fmri::igemm_c5w_kernel<16,0>", "fmri::igemm_c5w_kernel<8,0>", "fmri::igemm_tc32_kernel<true>"} <= names
+    assert any(k.startswith("fmri::igemm_tc5w_kernel<16,") for k in names)
+    assert any(k.startswith("fmri::igemm_tc5w_kernel<8,") for k in names)

@@ -14,6 +14,7 @@ The references never call the library under test and read nothing outside this f
 ``[fullbatch] <case> | <quantity> | err/bound = r``; profiles/fullbatch_ops_parity.md records those of one GPU run.
 """
 import math
+import time
 
 import numpy as np
 import pytest
@@ -127,7 +128,26 @@ DENSE_TABLE = [
     # fc.3 has 4 output tiles and 24 K steps -> 3 splits; fc.0 has exactly 512 tiles, which is not < 512 -> one pass
     ("discriminator.fc.0",      16384, 512,   (256, 64), None,      True,  NONE, 1536, 6,  1,  1,  24),
     ("discriminator.fc.3",      512,   1,     None,      None,      True,  NONE, 1536, 2,  1,  3,  24),
+    # the dense layers of the 100-px step (ArchConfig.px100: 13 x 13 and 7 x 7 feature planes, HW = 169 and 49 in the
+    # (C, HW) <-> (HW, C) permutation) at the reference's shipped batch of 64, M = 64 / 128 / 192: 31 and 62 splits over
+    # 676 K steps (no even division), 49 splits over 196 K steps
+    ("encoder.fc.0 @100",       43264, 1024,  (256, 169), None,     True,  NONE, 64,   31, 1,  1,  1),
+    ("decoder.fc.0 @100",       512,   43264, None,     (256, 169), False, NONE, 128,  1,  62, 1,  2),
+    ("discriminator.fc.0 @100", 12544, 256,   (256, 49), None,      True,  NONE, 192,  49, 1,  1,  3),
+    ("fused heads @100",        1024,  1024,  None,      None,      True,  NONE, 64,   4,  4,  1,  1),
+    ("discriminator.fc.3 @100", 256,   1,     None,      None,      True,  NONE, 192,  1,  1,  1,  3),
+    # ... and at the remainder batch of 5 (M = 5 / 10 / 15): the same splits over one partial row tile
+    ("encoder.fc.0 @100",       43264, 1024,  (256, 169), None,     True,  NONE, 5,    31, 1,  1,  1),
+    ("decoder.fc.0 @100",       512,   43264, None,     (256, 169), False, NONE, 10,   1,  62, 1,  1),
+    ("discriminator.fc.0 @100", 12544, 256,   (256, 49), None,      True,  NONE, 15,   49, 1,  1,  1),
 ]
+
+
+def _k_steps(case):
+    """(forward, data-gradient) K steps of 64 of a DENSE_TABLE row: the reduction lengths _dense_route hands to
+    ops._choose_splits."""
+    from fmri_hip.ops import ceil_to, pad8
+    return ceil_to(pad8(case[1]), 64) // 64, ceil_to(pad8(case[2]), 64) // 64
 # row sweep over the 128-row tile edge on one split-K layer (fused heads) and one single-pass layer (128 -> 512)
 DENSE_TABLE += [("fused heads", 1024, 256, None, None, True, NONE, m, 4, 1, 1, (m + 63) // 64) for m in SWEEP]
 DENSE_TABLE += [("latent-disc 128->512", 128, 512, None, None, True, RELU, m, 1, 2, 1, (m + 63) // 64) for m in SWEEP]
@@ -170,6 +190,12 @@ def test_dense_table_states_its_routes_and_covers_both():
         "fmri_reduce_slabs with bias + activation over two or more row tiles"
     assert any(c[10] == 1 and c[11] >= 4 for c in DENSE_TABLE), "one-pass weight gradient over several K steps"
     assert any(c[10] > 1 for c in DENSE_TABLE), "split weight gradient"
+    # a split count that does not divide the K steps (the splits then cover unequal K ranges), in either direction
+    assert any(c[8] > 1 and _k_steps(c)[0] % c[8] for c in DENSE_TABLE), "forward splits that do not divide the K steps"
+    assert any(c[9] > 1 and _k_steps(c)[1] % c[9] for c in DENSE_TABLE), "dgrad splits that do not divide the K steps"
+    assert (676 % 31, 676 % 62) == (25, 56) and any(c[8] == 31 for c in DENSE_TABLE) and any(c[9] == 62 for c in DENSE_TABLE)
+    # the feature permutation at plane sizes other than 64
+    assert {p[1] for c in DENSE_TABLE for p in (c[3], c[4]) if p} >= {64, 169, 49}
 
 
 def _perms(K, N, in_perm, out_perm):
@@ -208,6 +234,7 @@ def test_dense_at_engine_rows(name, K, N, in_perm, out_perm, bias, act, M, fwd, 
     from fmri_hip import ops
     from fmri_hip.ops import DenseLayer, pad8, rows_to_f16
     case = f"A {name} {K}->{N} M={M}"
+    t_start = time.time()
     torch.manual_seed(M * 7 + K + N)
     w = _h(torch.randn(N, K) / np.sqrt(K))
     b = torch.randn(N) * 0.1 if bias else None
@@ -273,6 +300,8 @@ def test_dense_at_engine_rows(name, K, N, in_perm, out_perm, bias, act, M, fwd, 
                 assert all(torch.equal(runs[0][k], runs[1][k]) for k in runs[0]), "deterministic mode: two runs differ"
     finally:
         ops.set_deterministic(was)
+    torch.cuda.synchronize()
+    print(f"[fullbatch] {case} | wall {time.time() - t_start:.1f} s", flush=True)
 
 
 @pytest.mark.parametrize("K,N,M,act", [(128, 512, 77, RELU), (512, 1, 768, NONE), (1024, 256, 129, NONE)])
@@ -400,6 +429,7 @@ def _run_bn_case(M, C, perm=None, hard=False, updates=1, x16=None, seed=None):
     cols = M <= ops._BN_COLS_ROWS
     case = f"B ({M}, {C})" + (" perm" if perm else "") + (" hard" if hard else "") + (" cols" if cols else " stream")
     torch.cuda.reset_peak_memory_stats()
+    t_start = time.time()
     if x16 is None:
         x16 = _bn_input(M, C, seed if seed is not None else M + C, hard)
     dya, dyb = _bn_cotangents(x16, 3 * M + C)
@@ -539,12 +569,19 @@ def _run_bn_case(M, C, perm=None, hard=False, updates=1, x16=None, seed=None):
             dz, rz = dx16[:, z].double(), refs[0][0][:, z]
             lim = 3e-3 * rz.pow(2).mean().sqrt() + 3e-3 * rz.abs()
             assert bool((dz == 0).all()) or bool(((dz - rz).abs() <= lim).all()), "all-zero channel: dx"
-    print(f"[fullbatch] {case} | peak device memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
+    torch.cuda.synchronize()
+    print(f"[fullbatch] {case} | wall {time.time() - t_start:.1f} s, peak device memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
 
 
-BN_COLS = [(256, 1024, None), (512, 16384, (256, 64)), (768, 512, None), (2048, 64, None)]
+BN_COLS = [(256, 1024, None), (512, 16384, (256, 64)), (768, 512, None), (2048, 64, None),
+           # the 100-px step at batch 64: encoder.fc.0, decoder.fc.0 (13 x 13 planes: HW = 169), discriminator.fc.0
+           (64, 1024, None), (128, 43264, (256, 169)), (192, 256, None)]
 BN_STREAM = [(256 * 32 * 32, 64), (768 * 32 * 32, 128), (512 * 16 * 16, 256), (512 * 64 * 64, 32),
-             (512 * 64 * 64 - 5, 32)]
+             (512 * 64 * 64 - 5, 32),
+             # the row counts N H W of the 100-px planes at batch 64, none a power of two: 64 x 50 x 50, 64 x 25 x 25,
+             # 64 x 13 x 13, 192 x 7 x 7, 128 x 100 x 100
+             (160000, 64), (40000, 128), (10816, 256), (9408, 256), (1280000, 64)]
 
 
 @pytest.mark.parametrize("M,C,perm", BN_COLS)
