@@ -143,22 +143,50 @@ int fmri_wgrad(const void* P, const void* Q, float* out, const void* zero16, int
 int fmri_wgrad_if(const int* gate, const void* P, const void* Q, float* out, const void* zero16, int N, int Yc, int Xc,
                   int A, int Hq, int Wq, int Bc, int k, int stride, int pad, int flip, int apad, int ba_tile, int ldo,
                   int splits, int atomic, void* stream);
-/* atomic = 0: one split, plain stores.  1: atomic adds into a pre-zeroed out.  2: split z stores its partial result
- * to out + z*apad*ldo (stride-2, 128-row, 32-channel-block geometries only -- csrc/wgrad_win.hip -- else
- * FMRI_E_UNSUPPORTED).  For that kernel `splits` is the block budget per (128-row, 32-channel) group over the 4
- * parity planes; the number of slabs it writes is fmri_wgrad_slabs().
- * atomic = 3: 5x5 stride-1 layers with A = 32, Bc = 8 only (csrc/wgrad_narrow.hip, else FMRI_E_UNSUPPORTED): out
- * holds `splits` pre-zeroed slabs of apad*ldo floats that the blocks add into round-robin; fmri_unpack_grad sums
- * them (`splits` = the number of blocks the kernel is launched with, fmri_wgrad_narrow_blocks(): one slab per block,
- * every element added exactly once onto zero -- bit-reproducible).
- * atomic = 4: per-split slabs of the generic kernel (csrc/wgrad.hip): out holds `splits` ZERO-FILLED slabs of apad*ldo
- * floats, split z stores its partial result to slab z with plain stores (the kernel may use fewer splits than asked
- * for; the remaining slabs stay zero); fmri_unpack_grad sums them in slab order -- bit-reproducible.
- * flip = 0: Q pixel = m*stride + tap - pad.  flip = 1 (stride 1 only): Q pixel = m + pad - tap, i.e. the roles of
- * the two activations are exchanged so that the GATHERED operand is the one with fewer channels. */
+/* flip = 0: Q pixel = m*stride + tap - pad.  flip = 1 (stride 1 only): Q pixel = m + pad - tap, i.e. the roles of
+ * the two activations are exchanged so that the GATHERED operand is the one with fewer channels.
+ *
+ * `atomic` is one of the five modes below; it fixes what `out` is and what `splits` counts.  A caller does not work the
+ * pair out itself: fmri_wgrad_route plans it for a geometry, and the dispatch of fmri_wgrad_if runs exactly what the plan
+ * names.  Three kernels stand behind the modes: the window-resident kernel (csrc/wgrad_win.hip: 5x5, pad 2, stride 2,
+ * 128-row tiles, Bc a multiple of 32, operands within 2^30 elements), the narrow kernel (csrc/wgrad_narrow.hip: 5x5,
+ * pad 2, stride 1, A = apad = 32, Bc = 8, equal planes, P within 2^31 elements) and the generic kernel (csrc/wgrad.hip). */
+#define FMRI_WGRAD_STORE 0         /* out [apad][ldo], plain stores; splits = 1.  Generic kernel. */
+#define FMRI_WGRAD_ATOMIC 1        /* out [apad][ldo], PRE-ZEROED, atomic adds.  Window kernel where the geometry fits it:
+                                    * splits = block budget per (128-row, 32-channel) group over the 4 parity planes.
+                                    * Else the generic kernel: splits = K splits. */
+#define FMRI_WGRAD_PLANE_SLABS 2   /* window kernel only (else FMRI_E_UNSUPPORTED): splits = the same block budget; K piece
+                                    * z of a parity plane stores to out + z*apad*ldo.  fmri_wgrad_slabs() slabs, every one
+                                    * written in full. */
+#define FMRI_WGRAD_NARROW_SLABS 3  /* narrow kernel only (else FMRI_E_UNSUPPORTED): out holds `splits` PRE-ZEROED slabs that
+                                    * the blocks add into round-robin; column k*k*Bc of row a holds sum_m P[m][a].  With
+                                    * splits = fmri_wgrad_narrow_blocks(), the blocks launched, every element is added
+                                    * once, onto zero: bit-reproducible. */
+#define FMRI_WGRAD_KSPLIT_SLABS 4  /* generic kernel: out holds `splits` ZERO-FILLED slabs, K split z stores slab z with
+                                    * plain stores.  The kernel may use fewer splits than asked for (the plan's `stored`);
+                                    * the other slabs stay zero.  Summed in slab order: bit-reproducible. */
+/* fmri_unpack_grad / fmri_apply_batch sum the slabs of modes 2 - 4. */
 int fmri_wgrad_slabs(int N, int Yc, int Xc, int k, int pad, int splits);
-/* number of blocks fmri_wgrad(..., atomic = 3) launches for this geometry */
+/* number of blocks fmri_wgrad(..., FMRI_WGRAD_NARROW_SLABS) launches for this geometry */
 int fmri_wgrad_narrow_blocks(int N, int Yc, int Xc);
+/* What to launch for a geometry, and into what: the counterpart of fmri_igemm_route and the ONLY statement of the
+ * weight-gradient routing.  Pure host code -- no GPU is touched, it runs on a machine without one.  The geometry
+ * arguments are those of fmri_wgrad_if up to ldo.  The caller's policy: win_blocks, the window kernel's block budget for
+ * the whole launch (per group it is win_blocks / groups, at least 4); slab_limit, the most K pieces the window kernel
+ * still writes as slabs before it turns to atomics; deterministic != 0 asks for a slab mode wherever partial sums meet.
+ * Returns what fmri_wgrad_if returns for the planned call (the geometry is validated the same way). */
+typedef struct {
+    int32_t atomic;      /* the FMRI_WGRAD_* mode to pass to fmri_wgrad_if */
+    int32_t splits;      /* the `splits` argument to pass */
+    int32_t slabs;       /* 0: out is one [apad][ldo] matrix; n: out is [n][apad][ldo] */
+    int32_t zeroed;      /* out must hold zeros at the launch */
+    int32_t stored;      /* slabs the launch writes (< slabs possible in FMRI_WGRAD_KSPLIT_SLABS); 0 when slabs is 0 */
+    int32_t colsum;      /* narrow kernel: the spare column holds the bias gradient's sums */
+    int32_t pieces[4];   /* window kernel: K pieces of parity plane py*2 + px; else 0 */
+    char kernel[64];     /* the instantiation the dispatch reached under the probe, e.g. "fmri::wgrad_kernel<64,1,4>" */
+} fmri_wgrad_plan;
+int fmri_wgrad_route(int N, int Yc, int Xc, int A, int Hq, int Wq, int Bc, int k, int stride, int pad, int flip, int apad,
+                     int ba_tile, int ldo, int win_blocks, int slab_limit, int deterministic, fmri_wgrad_plan* plan);
 
 /* ---- deterministic-reduction mode (process-wide; initial value: environment FMRI_DETERMINISTIC=1).  When on, the
  * loss / norm kernels that end in an atomic add onto a device scalar (fmri_latent_fwd, fmri_feat_mse, fmri_pixel_sq,

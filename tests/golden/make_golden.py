@@ -879,7 +879,18 @@ def case_ingest(name):
     print(name, "written")
 
 
+def case_wgrad_routes():
+    """tests/golden/wgrad_routes.json: what ops.run_wgrad hands to fmri_wgrad_if and asks of the allocator over the sweep
+    of tests/test_conv_oracle_host.py (CPU only; needs the built library, not the reference).  The committed file was
+    recorded at the last commit whose run_wgrad held the routing conditions itself; only when asked for by name."""
+    sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "thesis-fmri-reconstruction_amd")]
+    import test_conv_oracle_host as H
+    print("wgrad_routes written:", H.write_routes_json(), "geometries")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["wgrad_routes"]:
+        sys.exit(case_wgrad_routes())
     torch.set_num_threads(8)
     which = [a for a in sys.argv[1:] if not a.startswith("--")] or ["all"]
     # --f64: the same cases with the reference modules, the recipe weights and the inputs in DOUBLE precision, written as

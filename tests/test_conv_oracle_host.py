@@ -1,6 +1,9 @@
 """Host side of tests/test_fullbatch_conv_gpu.py, no GPU needed: the float64 slicing-and-matmul reference
 (tests/conv_oracle.py) against torch's float64 convolutions and autograd on the CPU, and the weight-gradient route table
 of the GPU module against the library's own host functions, with the conditions the table as a whole has to cover."""
+import json
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -80,18 +83,21 @@ def test_plane_pieces_restatement_agrees_with_the_library():
 
 
 def test_route_table_is_what_the_library_and_run_wgrad_give():
-    """ROUTES, written out in the GPU module, equals the restated conditions of ops.run_wgrad; the slab counts behind
-    it are the library's (fmri_wgrad_slabs, fmri_wgrad_narrow_blocks); the constants the restatement uses are ops'."""
+    """ROUTES, written out in the GPU module, is what the code that runs decides: ops.wgrad_plan (fmri_wgrad_route, the
+    plan run_wgrad launches) per case and setting; the slab counts behind it are the library's (fmri_wgrad_slabs,
+    fmri_wgrad_narrow_blocks); the policy constants are ops' defaults.  (With a kernel family switched off its rows fail.)"""
     from fmri_hip import lib, ops
     L = lib.load()
-    assert (ops._WW_SLABS, ops._WW_SIDE_BLOCKS, ops._WW_BLOCKS, ops._WW_ON, ops._WN_ON) == (24, 160, 0, True, True)
+    assert (ops._WW_SLABS, ops._WW_SIDE_BLOCKS, ops._WW_BLOCKS) == (24, 160, 0)
     assert set(T.ROUTES) == {name for name, _ in T.CASES} and len(T.CASES) == 44
     for name, case in T.CASES:
         kind, cin, cout, stride, H, op, N = case
         g = T.geometry(*case)
         for si, setting in enumerate(T.SETTINGS):
-            route = T.wgrad_route(case, setting)
+            plan = T.case_plan(case, setting)
+            route = T.plan_route(plan)
             assert T.ROUTES[name][si] == route, (name, setting, T.ROUTES[name][si], route)
+            assert 0 <= plan.stored <= plan.slabs and plan.colsum == (route[0] == "narrow"), (name, setting, plan)
             kern, mode, splits, detail = route
             print(f"[fullbatch-conv] route {name:28s} {setting:16s} {kern:8s} atomic={mode} splits={splits:3d} {detail}")
             if kern == "win":
@@ -159,6 +165,98 @@ def test_route_table_covers_the_piece_edges():
     partial = [r for r in slab if T.geometry(*dict(T.CASES)[r[0]])["Yc"] % 8 and min(r[5]) < 8]
     assert {r[1] for r in partial} == set(T.SETTINGS), "pieces of fewer than 8 tiles, partial tiles, every setting"
     assert any(min(r[5]) == 2 for r in partial) and any(max(r[5]) == 5 for r in partial), "2 - 5 tiles per piece"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the recorded sweep: what run_wgrad decided, per geometry and setting, at the commit before it asked the library's plan
+# ---------------------------------------------------------------------------------------------------------------------
+ROUTES_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_routes.json")
+SWEEP_BATCHES = (1, 2, 3, 4, 5, 8, 16, 32, 64, 100, 128, 255, 256, 257, 512)
+SETTING_FLAGS = ((True, False), (False, False), (True, True))       # (side stream, deterministic) of T.SETTINGS
+ROUTE_KERNELS = ["fmri::wgrad_win_kernel", "fmri::wgrad_narrow_kernel", "fmri::wgrad_kernel"]
+
+
+def sweep_geometries():
+    """(N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip) as ConvLayer._wgrad / DenseLayer._wgrad hand them to run_wgrad:
+    the FULL_SIZE, PX100_LAYERS and DENSE_TABLE layers at SWEEP_BATCHES samples times the layer's images per sample (255,
+    256 and 257 straddle the narrow kernel's 32 768 tiles, the dense rows the generic kernel's 512 output tiles)."""
+    import test_fullbatch_ops_gpu as D
+    from fmri_hip.ops import pad8
+    layers = [(case[:6], case[6] // (256 if i < 11 else 128)) for i, (_, case) in enumerate(T.CASES[:19])]
+    layers += [(row[1:7], row[7]) for row in T.PX100_LAYERS]
+    per_sample = lambda name: 3 if name.startswith("discriminator") else 2 if name.startswith(("decoder", "latent")) else 1
+    dense = [(c[1], c[2], per_sample(c[0])) for c in D.DENSE_TABLE]
+    out = []
+    for B in SWEEP_BATCHES:
+        for shape, per in layers:
+            g = T.geometry(*shape, B * per)
+            out.append((B * per, g["Yc"], g["Yc"], g["A"], g["Hq"], g["Hq"], g["Bc"], T.K5, g["stride"], T.PAD, g["flip"]))
+        out += [(B * per, 1, 1, pad8(N), 1, 1, pad8(K), 1, 1, 0, 0) for K, N, per in dense]
+    return list(dict.fromkeys(out))
+
+
+def route_by_run_wgrad(geo, side, det):
+    """[kernel-name prefix, atomic, splits, buffer shape, zeroed] of one ops.run_wgrad call on the CPU: lib.call,
+    lib.note and ops._grad_buffer are recorders for its duration, the operands one-element tensors."""
+    from fmri_hip import lib, ops
+    seen, one = {}, torch.zeros(1, dtype=torch.float16)
+    saved = (lib.call, lib.note, lib.PROFILE, ops._grad_buffer, ops._SIDE["on"], ops._DET["on"])
+
+    def buffer(hold, shape, zeroed, device):
+        seen["buffer"] = [list(shape), bool(zeroed)]
+        return one
+
+    lib.call = lambda name, *a: seen.update(call=(name, a))
+    lib.note = lambda **kw: seen.update(kernel=kw["kernel"])
+    lib.PROFILE, ops._grad_buffer, ops._SIDE["on"], ops._DET["on"] = [], buffer, side, det
+    try:
+        ops.run_wgrad(one, one, *geo)
+    finally:
+        lib.call, lib.note, lib.PROFILE, ops._grad_buffer, ops._SIDE["on"], ops._DET["on"] = saved
+    name, a = seen["call"]
+    assert name == "fmri_wgrad_if" and tuple(a[5:16]) == tuple(geo), (name, a)
+    return [seen["kernel"].split("<")[0], a[20], a[19]] + seen["buffer"]
+
+
+def route_by_plan(geo, side, det):
+    """The same five values from ops.wgrad_plan."""
+    from fmri_hip import ops
+    p = ops.wgrad_plan(*geo, side=side, det=det)
+    apad, ldo = ops.ceil_to(geo[3], ops.tile_for(geo[3])), ops.ceil_to(geo[7] * geo[7] * geo[6], 128)
+    return [p.kernel.split("<")[0], p.atomic, p.splits, ([p.slabs] if p.slabs else []) + [apad, ldo], p.zeroed]
+
+
+def write_routes_json(route=route_by_run_wgrad):
+    """tests/golden/make_golden.py: one compact row per geometry -- the eleven run_wgrad arguments, then per setting
+    [index into ``kernels``, atomic, splits, buffer shape, zeroed (0 / 1)]."""
+    rows = []
+    for geo in sweep_geometries():
+        per = [route(geo, side, det) for side, det in SETTING_FLAGS]
+        rows.append(list(geo) + [[ROUTE_KERNELS.index(r[0]), r[1], r[2], r[3], int(r[4])] for r in per])
+    head = json.dumps({"settings": list(T.SETTINGS), "kernels": ROUTE_KERNELS}, separators=(",", ":"))
+    with open(ROUTES_JSON, "w") as f:
+        f.write(head[:-1] + ',"rows":[\n' + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]}\n")
+    return len(rows)
+
+
+def test_recorded_routes_replay_through_the_plan_and_through_run_wgrad():
+    """Every row of tests/golden/wgrad_routes.json -- kernel, ``atomic``, ``splits``, buffer shape, zeroed, recorded off
+    run_wgrad before the routing moved into fmri_wgrad_route -- is what ops.wgrad_plan states and what run_wgrad hands
+    to its launch today, for the whole sweep and the three settings."""
+    assert os.path.getsize(ROUTES_JSON) < 100 * 1024
+    with open(ROUTES_JSON) as f:
+        doc = json.load(f)
+    assert doc["settings"] == list(T.SETTINGS) and doc["kernels"] == ROUTE_KERNELS
+    assert [tuple(r[:11]) for r in doc["rows"]] == sweep_geometries()
+    families = set()
+    for row in doc["rows"]:
+        geo = tuple(row[:11])
+        for (side, det), (kern, atomic, splits, shape, zeroed) in zip(SETTING_FLAGS, row[11:]):
+            recorded = [ROUTE_KERNELS[kern], atomic, splits, shape, bool(zeroed)]
+            assert route_by_plan(geo, side, det) == recorded, (geo, side, det)
+            assert route_by_run_wgrad(geo, side, det) == recorded, (geo, side, det)
+            families.add((kern, atomic))
+    assert families == {(0, 1), (0, 2), (1, 3), (2, 0), (2, 1), (2, 4)}, families
 
 
 def test_cases_are_the_full_size_list_plus_the_edges():

@@ -3,10 +3,11 @@ element of the weight gradient, against the float64 slicing-and-matmul reference
 
 tests/test_kernels_gpu.py compares these kernels element by element at 2 - 9 images; at the real sizes it looks at three
 images and ties the weight gradient down with one scalar.  What the weight-gradient code does depends on the size
-(ops.run_wgrad, wgrad_plane_pieces in csrc/api.hip): ROUTES below states, for each case and each of the three launch
-settings (side stream on / off, deterministic mode), the kernel, the ``atomic`` mode, the ``splits`` argument and the K
-pieces per parity plane; tests/test_conv_oracle_host.py holds that table against the library's host functions and
-asserts what the table as a whole has to cover, and every case here reads the same off its own fmri_wgrad_if launch.
+(fmri_wgrad_route in csrc/api.hip, asked through ops.wgrad_plan): ROUTES below states, for each case and each of the
+three launch settings (side stream on / off, deterministic mode), the kernel, the ``atomic`` mode, the ``splits`` argument
+and the K pieces per parity plane, as literal values; tests/test_conv_oracle_host.py holds that table against the
+library's plan and asserts what the table as a whole has to cover, and every case here holds its own fmri_wgrad_if
+launch and buffer request against both the table and the plan.
 
 Cases: the 19 FULL_SIZE layers of tests/test_kernels_gpu.py plus EDGE_CASES, cheap shapes that meet the piece-edge
 conditions (unequal plane pieces, planes clamped to the tile count, a last piece of one tile, fewer stored slabs than
@@ -278,36 +279,23 @@ def planned_pieces(ntiles, splits, k=K5, pad=PAD):
     return tuple(max(int(total * c / sum(cost) + 0.5), 1) for c in cost)
 
 
-def wgrad_route(case, setting, ww_slabs=24, side_blocks=160):
-    """(kernel, atomic, splits, detail) of ROUTES from the conditions of ops.run_wgrad, restated (ops has no function
-    to ask; every case also reads kernel, mode and splits off its own launch)."""
-    kind, cin, cout, stride, H, op, N = case
+FAMILY = {"fmri::wgrad_win_kernel": "win", "fmri::wgrad_narrow_kernel": "narrow", "fmri::wgrad_kernel": "generic"}
+
+
+def plan_route(plan):
+    """(kernel, atomic, splits, detail) of ROUTES out of an ops.WgradPlan (fmri_wgrad_route: the library's own statement
+    of the routing, host code only)."""
+    kern = FAMILY[plan.kernel.split("<")[0]]
+    detail = {"win": plan.pieces, "narrow": plan.slabs, "generic": plan.stored}[kern]
+    return (kern, plan.atomic, plan.splits, detail)
+
+
+def case_plan(case, setting):
+    """ops.wgrad_plan for the arguments ConvLayer._wgrad hands to run_wgrad for this case, under a launch setting."""
+    from fmri_hip.ops import wgrad_plan
     g = geometry(*case)
-    A, Bc, Yc = g["A"], g["Bc"], g["Yc"]
-    det = setting == "deterministic"
-    ba = 128 if A >= 128 else (64 if A >= 64 else 32)
-    apad = (A + ba - 1) // ba * ba
-    ldo = (25 * Bc + 127) // 128 * 128
-    ntiles = N * ((Yc + 7) // 8) ** 2
-    if g["stride"] == 2 and not g["flip"] and ba == 128 and Bc % 32 == 0 and Yc * Yc > 1:
-        groups = (Bc // 32) * (apad // 128)
-        budget = side_blocks if setting == "side stream on" else 256
-        splits = max(4, budget // groups)
-        pieces = plane_pieces(ntiles, splits)[1]
-        slabs = max(pieces) <= ww_slabs or det
-        return ("win", 2 if slabs else 1, splits, pieces)
-    if g["stride"] == 1 and A == 32 and Bc == 8 and ntiles >= 32768:
-        nslabs = max(1, min((ntiles + 31) // 32, 768)) if det else 4
-        return ("narrow", 3, nslabs, nslabs)
-    tiles = (ldo // 128) * (apad // ba)
-    steps = (N * Yc * Yc + 63) // 64
-    splits = 1
-    if tiles < 512 and steps >= 16:
-        splits = max(min(steps // 8, (1024 + tiles - 1) // tiles), 1)
-    if splits > 1 and det:
-        per = (steps + splits - 1) // splits
-        return ("generic", 4, splits, (steps + per - 1) // per)
-    return ("generic", 1 if splits > 1 else 0, splits, 0)
+    return wgrad_plan(case[6], g["Yc"], g["Yc"], g["A"], g["Hq"], g["Hq"], g["Bc"], K5, g["stride"], PAD, g["flip"],
+                      side=setting != "side stream off", det=setting == "deterministic")
 
 
 def routes_of(name, case):
@@ -439,19 +427,6 @@ def _igemm_name(a, act_y=False):
     """Kernel instantiation behind a recorded fmri_igemm_ep call (asked of the library: fmri_igemm_route)."""
     from fmri_hip.ops import igemm_route
     return igemm_route(*a[5:18], bool(a[18]), a[19], a[21], a[22], has_bias=bool(a[3]), want_act_y=act_y)
-
-
-def _wgrad_kernel_of(a):
-    """Kernel a recorded fmri_wgrad_if call is dispatched to, from its arguments (the dispatch of fmri_wgrad_if in
-    csrc/api.hip: the window kernel takes stride 2, 128-row tiles, 32-channel column blocks in modes 1 and 2; mode 3
-    is the narrow kernel's; everything else is the generic kernel)."""
-    N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, apad, ba, ldo, splits, mode = a[5:21]
-    if stride == 2 and not flip and mode in (1, 2) and ba == 128 and Bc % 32 == 0 and Yc * Xc > 1:
-        return "win"
-    if mode == 3:
-        return "narrow"
-    assert mode != 2
-    return "generic"
 
 
 def _nan16(*shape):
@@ -681,11 +656,15 @@ def test_conv_layer_every_element(name, case):
                 a = spy.args_of("fmri_wgrad_if")
                 assert len(a) == 1, len(a)
                 kern, mode, splits, detail = expected[si]
-                seen = (_wgrad_kernel_of(a[0]), a[0][20], a[0][19])
-                assert seen == (kern, mode, splits), (label, setting, seen, expected[si])
+                # the library's plan for the geometry of this very launch: it is the table's row, and what was launched
+                plan = ops.wgrad_plan(*a[0][5:16], side=ops._SIDE["on"], det=ops.deterministic())
+                assert plan_route(plan) == expected[si] == plan_route(case_plan(case, setting)), (label, setting, plan)
+                seen = (FAMILY[plan.kernel.split("<")[0]], a[0][20], a[0][19])
+                assert seen == (kern, mode, splits) == (kern, plan.atomic, plan.splits), (label, setting, seen, expected[si])
                 # the buffer the launch was given: slabs as the route says, NaN-filled unless the kernel adds into it
                 shape, zeroed = nb.requests[0]
                 slabs_alloc = shape[0] if len(shape) == 3 else 0
+                assert (slabs_alloc, zeroed) == (plan.slabs, plan.zeroed), (shape, zeroed, plan)
                 if kern == "win":
                     assert (slabs_alloc, zeroed) == ((max(detail), False) if mode == 2 else (0, True)), (shape, zeroed)
                 elif kern == "narrow":

@@ -107,7 +107,7 @@ SWEEP = (1, 63, 64, 127, 128, 129, 200, 257)
 
 # name, K, N, in_perm, out_perm, bias, activation, rows M, then the route this case takes, stated from
 # ops._choose_splits (forward, data gradient: 1 = one pass with the bias / activation / fp16 store in the contraction's
-# epilogue, > 1 = fp32 slabs + fmri_reduce_slabs) and from the generic branch of ops.run_wgrad (weight gradient:
+# epilogue, > 1 = fp32 slabs + fmri_reduce_slabs) and from the generic branch of the library's weight-gradient plan (ops.wgrad_plan:
 # splits > 1 needs tiles < 512 and ceil(M / 64) >= 16 K steps), and the K steps of the weight gradient.
 DENSE_TABLE = [
     # name                      K      N      in_perm    out_perm   bias   act   M     fwd dgrad wgrad ksteps
@@ -155,25 +155,20 @@ DENSE_TABLE += [("latent-disc 128->512", 128, 512, None, None, True, RELU, m, 1,
 
 def _dense_route(M, K, N):
     """(forward splits, data-gradient splits, weight-gradient splits, weight-gradient K steps) from ops._choose_splits
-    with DenseLayer._gemm's block / K-step counts, and from the conditions of run_wgrad's generic branch."""
-    from fmri_hip.ops import _choose_splits, ceil_to, pad8, tile_for
+    with DenseLayer._gemm's block / K-step counts, and from ops.wgrad_plan for the geometry DenseLayer._wgrad hands to
+    run_wgrad (a 1 x 1 plane per row, one tap)."""
+    from fmri_hip.ops import _choose_splits, ceil_to, pad8, tile_for, wgrad_plan
     kp, np_ = pad8(K), pad8(N)
     t_out, t_in = min(64, tile_for(N)), min(64, tile_for(K))
     rows = (M + 127) // 128
     fwd = _choose_splits(rows * (ceil_to(N, t_out) // t_out), ceil_to(kp, 64) // 64)
     dgr = _choose_splits(rows * (ceil_to(K, t_in) // t_in), ceil_to(np_, 64) // 64)
-    ba = tile_for(np_)
-    tiles = (ceil_to(kp, 128) // 128) * (ceil_to(np_, ba) // ba)
-    steps = (M + 63) // 64
-    # restated from the generic branch of ops.run_wgrad (``if tiles < 512 and steps >= 16: splits = min(steps // 8,
-    # ceil(1024 / tiles))``): ops has no function to ask.  Every case also reads the split count and mode off its own
-    # fmri_wgrad_if launch, so a change of that branch fails the cases it moves even if this copy were left behind.
-    wgr = max(min(steps // 8, (1024 + tiles - 1) // tiles), 1) if (tiles < 512 and steps >= 16) else 1
-    return fwd, dgr, wgr, steps
+    wgr = wgrad_plan(M, 1, 1, np_, 1, 1, kp, 1, 1, 0).splits
+    return fwd, dgr, wgr, (M + 63) // 64
 
 
 def test_dense_table_states_its_routes_and_covers_both():
-    """The routes written into DENSE_TABLE are what ops._choose_splits / run_wgrad's conditions give today, and the
+    """The routes written into DENSE_TABLE are what ops._choose_splits / ops.wgrad_plan give today, and the
     table as a whole holds every route: forward and data gradient in one pass and through fmri_reduce_slabs (the
     latter with bias + activation over two or more 128-row tiles), weight gradient in one pass over several K steps
     and split.  A routing change that moves a case fails here (and in the case itself, which observes the launch)."""

@@ -792,33 +792,76 @@ int fmri_wgrad(const void* P, const void* Q, float* out, const void* zero16, int
                          splits, atomic, stream);
 }
 
-// one fmri_wgrad_if call after validation
+// One fmri_wgrad_if call.  A kernel family's geometry test (wgrad_win_fits, wgrad_narrow_fits) reads the sizes only: the
+// dispatch of fmri_wgrad_if and the plan of fmri_wgrad_route ask the same one, so the plan cannot choose a kernel the
+// dispatch would not run.
 struct WgradReq {
     const int* gate; const half_t *P, *Q, *zero; float* out;
     int N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, apad, ba_tile, ldo, splits, atomic;
     hipStream_t st;
 };
-// stride-2 sampling, >= 128 rows, 32-channel column blocks, pre-zeroed fp32 output (atomic accumulation):
-// window-resident kernel (csrc/wgrad_win.hip).  FMRI_WGRAD_WIN=off disables.  False: not this kernel's call.
-static bool wgrad_win_args(const WgradReq& q, WgradWinArgs& w) {
-    static const bool off = family_off("FMRI_WGRAD_WIN");
+static int wgrad_check(const WgradReq& q) {
+    if (!q.P || !q.Q || !q.out || !q.zero) return FMRI_E_BADARG;
+    if (q.flip && q.stride != 1) return FMRI_E_UNSUPPORTED;
+    if (q.N < 1 || q.A < 8 || (q.A & 7) || q.Bc < 8 || (q.Bc & 7) || q.k < 1 || q.splits < 1) return FMRI_E_BADARG;
+    if (q.ba_tile != 32 && q.ba_tile != 64 && q.ba_tile != 128) return FMRI_E_UNSUPPORTED;
+    if (q.apad % q.ba_tile || q.apad < q.A) return FMRI_E_BADARG;
+    if (q.ldo % 128 || q.ldo < q.k * q.k * q.Bc) return FMRI_E_BADARG;
+    if (q.splits > 1 && q.atomic == FMRI_WGRAD_STORE) return FMRI_E_BADARG;
+    if (q.atomic < FMRI_WGRAD_STORE || q.atomic > FMRI_WGRAD_KSPLIT_SLABS) return FMRI_E_BADARG;
     const int64_t M = (int64_t)q.N * q.Yc * q.Xc;
-    if (off || q.stride != 2 || q.flip || (q.atomic != 1 && q.atomic != 2) || q.ba_tile != 128 || (q.Bc & 31) ||
-        q.Yc * q.Xc <= 1 || (int64_t)q.N * q.Hq * q.Wq * q.Bc >= 0x7fffffffLL || M * q.A >= 0x7fffffffLL)
+    if (M < 1 || M > 0x7fffff00LL) return FMRI_E_BADARG;
+    return FMRI_OK;
+}
+static int wgrad_tiles8(const WgradReq& q) { return q.N * ((q.Yc + 7) / 8) * ((q.Xc + 7) / 8); }
+// taps of parity `par` of a k-tap window with padding `pad` under stride 2: their number, *tmin = the first one's source
+// offset in the parity plane
+static int wgrad_parity_taps(int k, int pad, int par, int* tmin) {
+    int cnt = 0, emin = 0;
+    for (int t = 0; t < k; ++t)
+        if (((t - pad) & 1) == par) { if (!cnt) emin = t - pad; ++cnt; }
+    *tmin = (emin - par) / 2;      // exact: emin and par have the same parity
+    return cnt;
+}
+// 5x5 pad-2 stride-2 sampling (2 or 3 taps per parity), 128-row tiles, 32-channel column blocks, 32-bit buffer offsets:
+// window-resident kernel (csrc/wgrad_win.hip).  FMRI_WGRAD_WIN=off disables.
+static bool wgrad_win_fits(const WgradReq& q) {
+    static const bool off = family_off("FMRI_WGRAD_WIN");
+    if (off || q.stride != 2 || q.flip || q.k != 5 || q.pad != 2 || q.ba_tile != 128 || (q.Bc & 31) || q.Yc * q.Xc <= 1 ||
+        (int64_t)q.N * q.Hq * q.Wq * q.Bc * 2 >= 0x80000000LL || (int64_t)q.N * q.Yc * q.Xc * q.A * 2 >= 0x80000000LL)
         return false;
     for (int par = 0; par < 2; ++par) {
-        int cnt = 0, emin = 0;
-        for (int t = 0; t < q.k; ++t)
-            if (((t - q.pad) & 1) == par) { if (!cnt) emin = t - q.pad; ++cnt; }
+        int tmin;
+        const int cnt = wgrad_parity_taps(q.k, q.pad, par, &tmin);
         if (cnt < 2 || cnt > 3) return false;
-        w.nsy[par] = w.nsx[par] = cnt;
-        w.tmin[par] = (emin - par) / 2;      // exact: emin and par have the same parity
     }
+    return true;
+}
+// 5x5 stride-1 layers between 32 and 3(8) channels, P within 2^31 elements: wave-private window kernel
+// (csrc/wgrad_narrow.hip).  FMRI_WGRAD_NARROW=off disables.
+static bool wgrad_narrow_fits(const WgradReq& q) {
+    static const bool off = family_off("FMRI_WGRAD_NARROW");
+    return !off && q.stride == 1 && q.k == 5 && q.pad == 2 && q.A == 32 && q.Bc == 8 && q.apad == 32 && q.Yc == q.Hq &&
+           q.Xc == q.Wq && (int64_t)q.N * q.Yc * q.Xc * 32 < 0x7fffffffLL;
+}
+// K steps of 64 rows per split of the generic kernel; *used = the splits that get any (<= splits)
+static int wgrad_ksplit_steps(const WgradReq& q, int splits, int* used) {
+    const int steps = (int)(((int64_t)q.N * q.Yc * q.Xc + 63) / 64);
+    if (splits > steps) splits = steps;
+    const int per = (steps + splits - 1) / splits;
+    *used = (steps + per - 1) / per;
+    return per;
+}
+
+// window-resident kernel, pre-zeroed fp32 output (FMRI_WGRAD_ATOMIC) or plane-piece slabs (FMRI_WGRAD_PLANE_SLABS)
+static int wgrad_win(const WgradReq& q) {
+    WgradWinArgs w;
+    for (int par = 0; par < 2; ++par) w.nsy[par] = w.nsx[par] = wgrad_parity_taps(q.k, q.pad, par, &w.tmin[par]);
     w.gate = q.gate; w.P = q.P; w.Q = q.Q; w.out = q.out; w.zero = q.zero;
     w.N = q.N; w.Yc = q.Yc; w.Xc = q.Xc; w.A = q.A; w.Hq = q.Hq; w.Wq = q.Wq; w.Bc = q.Bc; w.pad = q.pad; w.TW = q.k;
     w.ldo = q.ldo; w.a_tiles = q.apad / 128;
-    w.slab_stride = q.atomic == 2 ? (int64_t)q.apad * q.ldo : 0;
-    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = q.N * w.tiles_y * w.tiles_x;
+    w.slab_stride = q.atomic == FMRI_WGRAD_PLANE_SLABS ? (int64_t)q.apad * q.ldo : 0;
+    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = wgrad_tiles8(q);
     // `splits` = blocks per (row block, column block) over the 4 planes; K pieces per plane: wgrad_plane_pieces()
     int tps4[4];
     const int smax = wgrad_plane_pieces(q.N, q.Yc, q.Xc, q.k, q.pad, q.splits, tps4);  // = fmri_wgrad_slabs(): in slab mode
@@ -829,7 +872,7 @@ static bool wgrad_win_args(const WgradReq& q, WgradWinArgs& w) {
     w.splits = smax;
     w.fdTPI = make_fastdiv((uint32_t)(w.tiles_y * w.tiles_x));
     w.fdTX = make_fastdiv((uint32_t)w.tiles_x);
-    return true;
+    return wgrad_win_launch(w, q.apad, q.st);
 }
 // generic weight-gradient kernel (csrc/wgrad.hip)
 static int wgrad_generic(const WgradReq& q) {
@@ -839,14 +882,11 @@ static int wgrad_generic(const WgradReq& q) {
     a.s = q.stride; a.T = q.k * q.k; a.TW = q.k;
     a.dy0 = q.flip ? q.pad : -q.pad; a.dx0 = a.dy0; a.dstep = q.flip ? -1 : 1;
     a.M = (int)((int64_t)q.N * q.Yc * q.Xc); a.ldo = q.ldo;
-    const int steps = (a.M + 63) / 64;
-    const int splits = q.splits > steps ? steps : q.splits;
-    a.steps_per_split = (steps + splits - 1) / splits;
-    a.splits = (steps + a.steps_per_split - 1) / a.steps_per_split;
-    // atomic == 4: per-split slabs of the generic kernel -- the caller allocated `splits` (as passed in) slabs of
-    // apad x ldo; the kernel writes every element of the first a.splits (<= splits) of them with plain stores, the
-    // rest stay as the caller left them (zero-filled)
-    a.atomic = q.atomic == 4 ? 2 : q.atomic;
+    // FMRI_WGRAD_KSPLIT_SLABS: the caller allocated `splits` (as passed in) slabs of apad x ldo; the kernel writes every
+    // element of the first a.splits (<= splits) of them with plain stores, the rest stay as the caller left them
+    // (zero-filled)
+    a.steps_per_split = wgrad_ksplit_steps(q, q.splits, &a.splits);
+    a.atomic = q.atomic == FMRI_WGRAD_KSPLIT_SLABS ? 2 : q.atomic;
     a.slab_stride = (int64_t)q.apad * q.ldo;
     a.ncol_chunks = a.T * q.Bc / 8;
     a.fdX = make_fastdiv((uint32_t)q.Xc);
@@ -855,19 +895,13 @@ static int wgrad_generic(const WgradReq& q) {
     a.fdBc8 = make_fastdiv((uint32_t)(q.Bc / 8));
     return wgrad_launch(a, q.apad, q.ba_tile, q.st);
 }
-// 5x5 stride-1 layers between 32 and 3(8) channels, pre-zeroed output: wave-private window kernel
-// (csrc/wgrad_narrow.hip), the only one with the slabs of atomic = 3.  FMRI_WGRAD_NARROW=off disables.
+// wave-private window kernel, `splits` pre-zeroed slabs (FMRI_WGRAD_NARROW_SLABS)
 static int wgrad_narrow(const WgradReq& q) {
-    static const bool off = family_off("FMRI_WGRAD_NARROW");
-    if (off || !(q.stride == 1 && q.k == 5 && q.pad == 2 && q.A == 32 && q.Bc == 8 && q.apad == 32 && q.Yc == q.Hq &&
-                 q.Xc == q.Wq))
-        return FMRI_E_UNSUPPORTED;
-    if ((int64_t)q.N * q.Yc * q.Xc * 32 >= 0x7fffffffLL) return wgrad_generic(q);      // P beyond 2^31 elements
     WgradNarrowArgs w;
     w.gate = q.gate; w.P = q.P; w.Q = q.Q; w.out = q.out; w.zero = q.zero;
     w.N = q.N; w.H = q.Yc; w.W = q.Xc; w.ldo = q.ldo; w.flip = q.flip;
-    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = q.N * w.tiles_y * w.tiles_x;
-    w.nslabs = q.splits < 1 ? 1 : q.splits; w.pad0 = 0;     // the caller allocated `splits` zeroed slabs of apad x ldo
+    w.tiles_y = (q.Yc + 7) / 8; w.tiles_x = (q.Xc + 7) / 8; w.ntiles = wgrad_tiles8(q);
+    w.nslabs = q.splits; w.pad0 = 0;                       // the caller allocated `splits` zeroed slabs of apad x ldo
     w.slab_stride = (int64_t)q.apad * q.ldo;
     return wgrad_narrow_launch(w, wgrad_narrow_blocks(q.N, q.Yc, q.Xc), q.st);
 }
@@ -875,23 +909,72 @@ static int wgrad_narrow(const WgradReq& q) {
 int fmri_wgrad_if(const int* gate, const void* P, const void* Q, float* out, const void* zero16, int N, int Yc, int Xc,
                   int A, int Hq, int Wq, int Bc, int k, int stride, int pad, int flip, int apad, int ba_tile, int ldo,
                   int splits, int atomic, void* stream) {
-    if (!P || !Q || !out || !zero16) return FMRI_E_BADARG;
-    if (flip && stride != 1) return FMRI_E_UNSUPPORTED;
-    if (N < 1 || A < 8 || (A & 7) || Bc < 8 || (Bc & 7) || splits < 1) return FMRI_E_BADARG;
-    if (ba_tile != 32 && ba_tile != 64 && ba_tile != 128) return FMRI_E_UNSUPPORTED;
-    if (apad % ba_tile || apad < A) return FMRI_E_BADARG;
-    if (ldo % 128 || ldo < k * k * Bc) return FMRI_E_BADARG;
-    if (splits > 1 && !atomic) return FMRI_E_BADARG;
-    if (atomic < 0 || atomic > 4) return FMRI_E_BADARG;
-    const int64_t M = (int64_t)N * Yc * Xc;
-    if (M < 1 || M > 0x7fffff00LL) return FMRI_E_BADARG;
     const WgradReq q = {gate, (const half_t*)P, (const half_t*)Q, (const half_t*)zero16, out, N, Yc, Xc, A, Hq, Wq, Bc, k,
                         stride, pad, flip, apad, ba_tile, ldo, splits, atomic, S(stream)};
-    WgradWinArgs w;
-    if (wgrad_win_args(q, w)) return wgrad_win_launch(w, apad, q.st);      // its code is final, E_UNSUPPORTED too
-    if (atomic == 3) return wgrad_narrow(q);
-    if (atomic == 2) return FMRI_E_UNSUPPORTED;      // plane-piece slabs exist only in the window-resident kernel
+    const int e = wgrad_check(q);
+    if (e != FMRI_OK) return e;
+    // the slab modes belong to one kernel each: a geometry that kernel does not fit is refused, not sent to another one
+    if ((atomic == FMRI_WGRAD_ATOMIC || atomic == FMRI_WGRAD_PLANE_SLABS) && wgrad_win_fits(q)) return wgrad_win(q);
+    if (atomic == FMRI_WGRAD_NARROW_SLABS) return wgrad_narrow_fits(q) ? wgrad_narrow(q) : FMRI_E_UNSUPPORTED;
+    if (atomic == FMRI_WGRAD_PLANE_SLABS) return FMRI_E_UNSUPPORTED;
     return wgrad_generic(q);
+}
+
+int fmri_wgrad_route(int N, int Yc, int Xc, int A, int Hq, int Wq, int Bc, int k, int stride, int pad, int flip, int apad,
+                     int ba_tile, int ldo, int win_blocks, int slab_limit, int deterministic, fmri_wgrad_plan* plan) {
+    if (!plan) return FMRI_E_BADARG;
+    memset(plan, 0, sizeof(*plan));
+    // as in fmri_igemm_route: the pointers are non-NULL dummies that are never dereferenced, the launcher stops at
+    // route_probe()
+    const half_t* const dummy = (const half_t*)(uintptr_t)64;
+    WgradReq q = {nullptr, dummy, dummy, dummy, (float*)(uintptr_t)64, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, apad,
+                  ba_tile, ldo, 1, FMRI_WGRAD_STORE, nullptr};
+    const int e = wgrad_check(q);
+    if (e != FMRI_OK) return e;
+    fmri_wgrad_plan& p = *plan;
+    if (wgrad_win_fits(q)) {
+        // blocks = 32-channel column blocks x 128-row blocks x 4 parity planes x K pieces over the 8 x 8 pixel tiles:
+        // the budget per (row block, column block) group over the 4 planes; few pieces: one slab each, else atomics
+        const int groups = (Bc / 32) * (apad / 128), ntiles = wgrad_tiles8(q);
+        q.splits = win_blocks / groups < 4 ? 4 : win_blocks / groups;
+        int tps[4];
+        const int smax = wgrad_plane_pieces(N, Yc, Xc, k, pad, q.splits, tps);
+        for (int pl = 0; pl < 4; ++pl) p.pieces[pl] = (ntiles + tps[pl] - 1) / tps[pl];
+        const bool slabs = smax <= slab_limit || deterministic;
+        q.atomic = slabs ? FMRI_WGRAD_PLANE_SLABS : FMRI_WGRAD_ATOMIC;
+        p.slabs = p.stored = slabs ? smax : 0;
+        p.zeroed = !slabs;
+    } else if (wgrad_narrow_fits(q) && wgrad_tiles8(q) >= 32768) {
+        // the kernel needs >= ~16 tiles per wave to amortise its block reduction: measured 1.9x on the 3B-image
+        // discriminator layer, a loss on the B-image decoder layer.  Blocks add into slab (block index % 4), a quarter
+        // of the same-address atomics; deterministic: one slab per block, every element added once, onto zero
+        q.atomic = FMRI_WGRAD_NARROW_SLABS;
+        q.splits = deterministic ? wgrad_narrow_blocks(N, Yc, Xc) : 4;
+        p.slabs = p.stored = q.splits;
+        p.zeroed = p.colsum = 1;
+    } else {
+        // generic kernel: K splits while the output tiles alone do not fill the GPU; atomics, or one slab per split
+        const int tiles = (ldo / 128) * (apad / ba_tile), steps = (int)(((int64_t)N * Yc * Xc + 63) / 64);
+        if (tiles < 512 && steps >= 16) {
+            const int by_steps = steps / 8, by_tiles = (1024 + tiles - 1) / tiles;
+            q.splits = by_steps < by_tiles ? by_steps : by_tiles;      // (steps >= 16: at least 2)
+        }
+        if (q.splits > 1) {
+            q.atomic = deterministic ? FMRI_WGRAD_KSPLIT_SLABS : FMRI_WGRAD_ATOMIC;
+            p.zeroed = 1;
+            if (deterministic) { p.slabs = q.splits; wgrad_ksplit_steps(q, q.splits, &p.stored); }
+        }
+    }
+    p.atomic = q.atomic;
+    p.splits = q.splits;
+    t_probe_name[0] = 0;
+    t_probe_on = true;
+    const int r = fmri_wgrad_if(q.gate, q.P, q.Q, q.out, q.zero, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, apad,
+                                ba_tile, ldo, q.splits, q.atomic, nullptr);
+    t_probe_on = false;
+    if (r != FMRI_OK) return r;
+    snprintf(p.kernel, sizeof(p.kernel), "%s", t_probe_name);
+    return FMRI_OK;
 }
 
 int fmri_nchw_to_nhwc(const float* src, void* dst, int N, int C, int HW, int Cp, void* stream) {

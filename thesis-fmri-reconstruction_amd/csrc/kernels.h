@@ -228,9 +228,10 @@ int colsum_rows_launch(const half_t* x, int M, int C, float* sums2C, float* ws, 
 int colsum_acc_launch(const void* src, int is_f16, int M, int C, int64_t ld_row, int64_t ld_col, float scale, float* dst,
                       hipStream_t st);
 
-// api.hip: routing probe (fmri_igemm_route).  Every igemm launch function calls route_probe() with the name of the kernel
-// instantiation it is about to launch, after its own support checks and before any HIP call; while a probe is active on
-// the calling thread the name is recorded and `true` returned: the launcher then returns OK without touching the GPU.
+// api.hip: routing probe (fmri_igemm_route, fmri_wgrad_route).  Every igemm and wgrad launch function calls route_probe()
+// with the name of the kernel instantiation it is about to launch, after its own support checks and before any HIP call;
+// while a probe is active on the calling thread the name is recorded and `true` returned: the launcher then returns OK
+// without touching the GPU.
 bool route_probe(const char* fmt, ...);
 
 // loss.hip: process-wide deterministic-reduction switch (fmri_set_deterministic)

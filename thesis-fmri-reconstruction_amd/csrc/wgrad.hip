@@ -177,6 +177,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
 int wgrad_launch(const WgradArgs& a, int apad, int ba_tile, hipStream_t st) {
     dim3 grid(a.ldo / 128, apad / ba_tile, a.splits);
     const int lds = 2 * 2 * 64 * 256;
+    if (ba_tile != 128 && ba_tile != 64 && ba_tile != 32) return E_UNSUPPORTED;
+    if (route_probe("fmri::wgrad_kernel<%d,%d,%d>", ba_tile, ba_tile == 128 ? 2 : 1, ba_tile == 128 ? 2 : 4)) return OK;
     switch (ba_tile) {
         case 128: hipLaunchKernelGGL((wgrad_kernel<128, 2, 2>), grid, dim3(256), lds, st, a); break;
         case 64: hipLaunchKernelGGL((wgrad_kernel<64, 1, 4>), grid, dim3(256), lds, st, a); break;

@@ -163,6 +163,7 @@ __global__ __launch_bounds__(256, 3) void wgrad_narrow_kernel(const WgradNarrowA
 
 int wgrad_narrow_launch(const WgradNarrowArgs& a, int nblocks, hipStream_t st) {
     const int lds = 4 * 2 * (64 * 32 + 4 * 1024);       // 48 KB: three blocks per CU
+    if (route_probe("fmri::wgrad_narrow_kernel")) return OK;
     hipLaunchKernelGGL(wgrad_narrow_kernel, dim3(nblocks), dim3(256), lds, st, a);
     return hipGetLastError() == hipSuccess ? OK : E_LAUNCH;
 }

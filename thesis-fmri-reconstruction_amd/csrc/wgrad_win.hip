@@ -287,6 +287,7 @@ int wgrad_win_launch(const WgradWinArgs& a, int apad, hipStream_t st) {
         return E_UNSUPPORTED;
     dim3 grid((a.Bc / 32) * a.a_tiles * (a.plane_pieces[0] + a.plane_pieces[1] + a.plane_pieces[2] + a.plane_pieces[3]));
     const int lds = 3 * (64 * 256 + 7 * 1024);
+    if (route_probe("fmri::wgrad_win_kernel<%s>", a.slab_stride != 0 ? "true" : "false")) return OK;
     // raising the dynamic-LDS limit is idempotent; every call sets it (no library-global state)
     if (hipFuncSetAttribute((const void*)wgrad_win_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return E_LAUNCH;
     if (hipFuncSetAttribute((const void*)wgrad_win_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return E_LAUNCH;

@@ -52,6 +52,7 @@ _SIGS = {
                          C.c_char_p, _i],
     "fmri_wgrad_slabs": [_i, _i, _i, _i, _i, _i],
     "fmri_wgrad_narrow_blocks": [_i, _i, _i],
+    "fmri_wgrad_route": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],       # _p: WgradPlan*
     "fmri_set_deterministic": [_i],
     "fmri_get_deterministic": [],
     "fmri_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -138,6 +139,12 @@ class Epilogue(C.Structure):
                 ("bn_mean", C.c_void_p * 4), ("bn_rstd", C.c_void_p * 4), ("bn_x_img0", C.c_int32 * 4),
                 ("bn_relu", C.c_int32), ("reserved", C.c_int32), ("act_y", C.c_void_p),
                 ("aff_scale", C.c_void_p), ("aff_shift", C.c_void_p), ("aff_relu", C.c_int32), ("reserved2", C.c_int32)]
+
+
+class WgradPlan(C.Structure):
+    """``fmri_wgrad_plan`` of include/fmri_hip.h (what fmri_wgrad_route plans for a weight-gradient geometry)."""
+    _fields_ = [("atomic", C.c_int32), ("splits", C.c_int32), ("slabs", C.c_int32), ("zeroed", C.c_int32),
+                ("stored", C.c_int32), ("colsum", C.c_int32), ("pieces", C.c_int32 * 4), ("kernel", C.c_char * 64)]
 
 
 class StatSeg(C.Structure):

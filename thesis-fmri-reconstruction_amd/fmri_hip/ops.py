@@ -292,10 +292,9 @@ _EPI_BWD = os.environ.get("FMRI_EPI_BWD") == "on"
 # gradient out of the narrow weight-gradient kernel's spare column: on/off
 _EPI_ACT = os.environ.get("FMRI_EPI_ACT") != "off"
 
-# window-resident wgrad kernel: on/off, resident-block target (2 per CU), largest split count still written as slabs
-_WW_ON = os.environ.get("FMRI_WGRAD_WIN") != "off"
-_WN_ON = os.environ.get("FMRI_WGRAD_NARROW") != "off"
-# block budget per tile group (FMRI_WW_BLOCKS overrides): one 8-wave block per CU (256) when the kernel has the GPU to
+# window-resident wgrad kernel: the policy handed to the library's plan (``wgrad_plan``; the kernel families' off
+# switches are the library's alone).
+# Block budget of a launch (FMRI_WW_BLOCKS overrides): one 8-wave block per CU (256) when the kernel has the GPU to
 # itself; 160 when it runs on the side stream beside the main stream's kernels -- its blocks hold a CU (144 KB of LDS) for
 # their whole K range, and a main-stream kernel that finds no free CU waits for one: leaving ~96 CUs to the main stream
 # measured 6.39-6.41 ms per step against 6.48-6.50 (two boxes, two repeats each; 224 / 192: no gain, 128: 6.40-6.42,
@@ -404,6 +403,34 @@ def join_side(device=None):
     _SIDE["pending"].clear()
 
 
+class WgradPlan(NamedTuple):
+    """``fmri_wgrad_plan`` of include/fmri_hip.h: what ``run_wgrad`` launches for a geometry, and into what."""
+    kernel: str                      # the instantiation the library's dispatch reaches, e.g. "fmri::wgrad_win_kernel<true>"
+    atomic: int                      # the FMRI_WGRAD_* mode handed to fmri_wgrad_if
+    splits: int                      # ... and its ``splits`` argument
+    slabs: int                       # 0: one [apad][ldo] matrix; n: [n][apad][ldo]
+    zeroed: bool                     # the buffer must hold zeros at the launch
+    stored: int                      # slabs the launch writes (generic slab mode may write fewer than ``slabs``)
+    colsum: bool                     # narrow kernel: the spare column behind the taps holds the bias gradient's sums
+    pieces: tuple                    # window kernel: K pieces per parity plane, else zeros
+
+
+def wgrad_plan(N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, side=None, det=None) -> WgradPlan:
+    """The route of a weight gradient -- asked of the library itself (fmri_wgrad_route: host code only, works without a
+    GPU), the single statement of the routing rules.  ``side`` / ``det``: the side-stream and deterministic settings to
+    plan for (default: the current ones)."""
+    side = _SIDE["on"] if side is None else side
+    det = _DET["on"] if det is None else det
+    ba = tile_for(A)
+    budget = _WW_BLOCKS or (_WW_SIDE_BLOCKS if side and not det else 256)
+    plan = lib.WgradPlan()
+    code = lib.load().fmri_wgrad_route(N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip, ceil_to(A, ba), ba,
+                                       ceil_to(k * k * Bc, 128), budget, _WW_SLABS, 1 if det else 0, ctypes.byref(plan))
+    lib.check(code, "fmri_wgrad_route")
+    return WgradPlan(plan.kernel.decode(), plan.atomic, plan.splits, plan.slabs, bool(plan.zeroed), plan.stored,
+                     bool(plan.colsum), tuple(plan.pieces))
+
+
 def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0, hold=None, gate=None):
     """Returns the packed fp32 gradient [apad][ldo] (or its slabs) as a ``WgradOut``.  ``hold``: see ``_grad_buffer``.
     ``flops``: algorithmic FLOPs of the layer's weight gradient (for the profiling hook of lib.call; 0 = 2 * rows * A *
@@ -411,58 +438,16 @@ def run_wgrad(P, Q, N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip=0, flops=0.0,
     ba = tile_for(A)
     apad = ceil_to(A, ba)
     ldo = ceil_to(k * k * Bc, 128)
+    plan = wgrad_plan(N, Yc, Xc, A, Hq, Wq, Bc, k, stride, pad, flip)
+    # slabs: partial sums that unpack_grad / fmri_apply_batch add up in slab order -- all ``plan.slabs`` of them, so the
+    # ones the generic kernel leaves unwritten (plan.stored < plan.slabs) are zero-filled, like a buffer that is added into
+    out = _wgrad_out(hold, (plan.slabs, apad, ldo) if plan.slabs else (apad, ldo), plan.zeroed, P.device, ldo,
+                     colsum=plan.colsum)
     if lib.PROFILE is not None:
-        fl = flops or 2.0 * N * Yc * Xc * A * Bc * k * k
-        nb = 2.0 * N * Yc * Xc * A + 2.0 * N * Hq * Wq * Bc + 4.0 * apad * ldo
-        note = lambda kern: lib.note(kernel=kern, flops=fl, bytes=nb)
-    else:
-        note = lambda kern: None
-    if (stride == 2 and not flip and ba == 128 and Bc % 32 == 0 and Yc * Xc > 1 and k == 5 and pad == 2 and _WW_ON
-            and 2 * N * Yc * Xc * A < 2 ** 31 and 2 * N * Hq * Wq * Bc < 2 ** 31):       # 32-bit buffer offsets
-        # window-resident kernel (csrc/wgrad_win.hip): blocks = 32-channel column blocks x 128-row blocks x 4 parity
-        # planes x splits over the 8x8 pixel tiles; every split stores its own slab, unpack_grad sums them
-        groups = (Bc // 32) * (apad // 128)
-        budget = _WW_BLOCKS or (_WW_SIDE_BLOCKS if (_SIDE["on"] and not _DET["on"]) else 256)
-        splits = max(4, budget // groups)                               # block budget per group over the 4 planes
-        nslabs = lib.load().fmri_wgrad_slabs(N, Yc, Xc, k, pad, splits)
-        slabs = nslabs <= _WW_SLABS or _DET["on"]                       # few splits: per-split slabs, else atomics
-        out = _wgrad_out(hold, (nslabs, apad, ldo) if slabs else (apad, ldo), not slabs, P.device, ldo)
-        note("fmri::wgrad_win_kernel")
-        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
-                 stride, pad, flip, apad, ba, ldo, splits, 2 if slabs else 1)
-        return out
-    if (stride == 1 and k == 5 and pad == 2 and A == 32 and Bc == 8 and Yc == Hq and Xc == Wq and _WN_ON
-            and N * ((Yc + 7) // 8) * ((Xc + 7) // 8) >= 32768):
-        # wave-private window kernel (csrc/wgrad_narrow.hip): atomic accumulation into zeroed 32 x ldo slab(s).  It
-        # needs >= ~16 tiles per wave to amortise its block reduction: measured 1.9x on the 3B-image discriminator
-        # layer, a loss on the B-image decoder layer
-        nslabs = 4                   # blocks add into slab (block index % 4): a quarter of the same-address atomics
-        if _DET["on"]:               # one slab per block: every element is added once, onto zero
-            nslabs = lib.load().fmri_wgrad_narrow_blocks(N, Yc, Xc)
-        # (colsum: column 200 of every slab row a holds sum_m P[m][a])
-        out = _wgrad_out(hold, (nslabs, apad, ldo), True, P.device, ldo, colsum=True)
-        note("fmri::wgrad_narrow_kernel")
-        lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
-                 stride, pad, flip, apad, ba, ldo, nslabs, 3)
-        return out
-    tiles = (ldo // 128) * (apad // ba)
-    steps = (N * Yc * Xc + 63) // 64
-    splits = 1
-    if tiles < 512 and steps >= 16:
-        splits = min(steps // 8, (1024 + tiles - 1) // tiles)
-        splits = max(splits, 1)
-    mode = 1 if splits > 1 else 0
-    if splits > 1 and _DET["on"]:
-        mode = 4                     # per-split slabs (plain stores), summed in slab order by unpack_grad
-        # zero-filled: the library re-derives the split count from the K steps (ceil(steps / ceil(steps / splits)), which
-        # can be smaller than ``splits`` -- e.g. 18 of 19 at the 100-px encoder conv.0 with 4 images) and stores only that
-        # many slabs, while unpack_grad / fmri_apply_batch sum all of them
-        out = _wgrad_out(hold, (splits, apad, ldo), True, P.device, ldo)
-    else:
-        out = _wgrad_out(hold, (apad, ldo), splits > 1, P.device, ldo)
-    note("fmri::wgrad_kernel")
+        lib.note(kernel=plan.kernel, flops=flops or 2.0 * N * Yc * Xc * A * Bc * k * k,
+                 bytes=2.0 * N * Yc * Xc * A + 2.0 * N * Hq * Wq * Bc + 4.0 * apad * ldo)
     lib.call("fmri_wgrad_if", _P(gate), _P(P), _P(Q), _P(out.buf), _P(zero_page(P.device)), N, Yc, Xc, A, Hq, Wq, Bc, k,
-             stride, pad, flip, apad, ba, ldo, splits, mode)
+             stride, pad, flip, apad, ba, ldo, plan.splits, plan.atomic)
     return out
 
 
