@@ -628,6 +628,51 @@ int fmri_rng_u32_at(const int64_t* state, int32_t* out, int64_t n, int64_t start
  * Both: enqueue-only, no allocation, no global state.  (seed, epoch, cursor) reproduces a run. */
 int fmri_sampler_indices(const int64_t* state, int N, int B, int64_t row0, int32_t* idx_out, void* stream);
 int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream);
+/* ---- differentiable augmentation of the discriminator's inputs (csrc/diffaug.hip; fmri_hip/augment.py) -----------------
+ * Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training" (NeurIPS 2020), policy colour + translation
+ * + cutout: every image the discriminator sees, real or generated, goes through one random transform T_p, and the
+ * generator's gradient is taken through it.  The reference has no counterpart; the contract is the formula below.
+ *
+ * Images: fp16 NHWC8 [N][H][W][8], square (H == W <= 128), real channels 0..2, 16-byte aligned.  table: fp32 [2B][8],
+ * 16-byte aligned, one row p = [b, s, c, ty, tx, cy, cx, cut] per image (integers as exact floats).  Image i of the call
+ * is image img0 + i (0 <= img0, img0 + N <= 3B) of the steps' [orig | pred | sampled] layout of B images each: orig b
+ * and pred b use row b (they are compared feature by feature), sampled b uses row B + b.
+ *
+ * fmri_diffaug_fwd: dst = T_p(src), in this order on the values of the fp16 elements:
+ *     u = x + b;   m = mean of u over the pixel's 3 channels,  v = (u - m) s + m;
+ *     M = mean of v over the image's 3 H W real elements,      w = (v - M) c + M;
+ *     o[y][x] = w[y + ty][x + tx] if that pixel lies inside the image, else 0;
+ *     o[y][x] = 0 for y in rows and x in cols, rows = { clamp(cy - cut / 2 + i, 0, H - 1) : 0 <= i < cut } (integer
+ *     division), cols likewise from cx; cut <= 0 cuts nothing;
+ *     one rounding to fp16; lanes 3..7 of every output pixel are zeros.
+ *   A stage whose parameter is neutral (b = 0, s = 1, c = 1) is skipped: the row [0,1,1,0,0,0,0,0] copies the real
+ *   channels bit for bit.
+ * fmri_diffaug_bwd: the adjoint of T_p's linear part on up to two cotangent streams of the same images in one launch
+ *   (g_b / dst_b NULL: one):  mask g by the cutout window;  g1[y][x] = g[y - ty][x - tx] inside the image, else 0;
+ *     g2 = c g1 + (1 - c) mean(g1 over the image's 3 H W elements);
+ *     g3 = s g2 + (1 - s) (mean of g2 over the pixel's 3 channels);
+ *   stored as fp16, finite values beyond +-65504 saturate (NaN stays NaN), lanes 3..7 zeros.
+ * Both evaluate the colour stages and their sums in fp64 (the affine maps cancel near zero, where fp32 arithmetic misses
+ * the fp16 rounding of the exact value by many ulps) and round once; sums run in a fixed order and there are no atomics:
+ * the bits are a function of the inputs alone, with fmri_set_deterministic on or off.  src and dst may not overlap.
+ * fmri_diffaug_params: table rows r < rows (fp32 [rows][8]) for the GLOBAL rows row0 + r of stream sid at the state's
+ *   offset (fmri_rng_normal for the state; the offset is not moved; a row consumes 2 blocks).  With w0..w7 the elements
+ *   8 (row0 + r) .. + 7 of the stream in the layout of fmri_rng_u32 and u(w) = (w >> 8) 2^-24:
+ *     b = u(w0) - 0.5,  s = 2 u(w1),  c = u(w2) + 0.5                                   (policy_mask & 1: colour)
+ *       (fp32 holds every value exactly but c from 1 on, where it is the fp32 sum rounded to nearest even)
+ *     ty = -sh + ((w3 (2 sh + 1)) >> 32),  tx likewise from w4                          (policy_mask & 2: translation)
+ *     cy = (w5 (H - cut mod 2 + 1)) >> 32,  cx likewise from w6,  column 7 = cut        (policy_mask & 4: cutout)
+ *   w7 is unused; a policy that is off writes the neutral values of its columns (cut = 0).  Rank k of a data-parallel
+ *   run passes row0 = k * B and gets its rows of the draw at the global batch.
+ * Errors, before anything is launched or dereferenced: H != W or H > 128: FMRI_E_UNSUPPORTED; a NULL or misaligned
+ * pointer, overlapping src / dst, N, H, B < 1, an image range outside [0, 3B), sh or cut outside [0, H], row0 < 0 or
+ * > 2^40, sid < 0: FMRI_E_BADARG.  Enqueue-only, no allocation, no global state. */
+int fmri_diffaug_params(const int64_t* state, float* table, int rows, int64_t row0, int sid, int H, int sh, int cut,
+                        int policy_mask, void* stream);
+int fmri_diffaug_fwd(const void* src16, void* dst16, int N, int H, int W, const float* table, int B, int img0,
+                     void* stream);
+int fmri_diffaug_bwd(const void* g_a, void* dst_a, const void* g_b, void* dst_b, int N, int H, int W, const float* table,
+                     int B, int img0, void* stream);
 /* starting cotangents of the two back-propagated streams, fp16, multiplied by gscale * (*norm) (norm: device float) */
 int fmri_gan_head_bwd(const float* logit, int ldl, int B, void* dlogit, int ldg, float gscale, const float* norm,
                       void* stream);

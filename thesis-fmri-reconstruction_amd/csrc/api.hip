@@ -1337,6 +1337,45 @@ int fmri_sampler_advance(int64_t* state, int N, int B_global, void* stream) {
     if (N < B_global) return FMRI_E_UNSUPPORTED;
     return sampler_advance_launch(state, N, B_global, S(stream));
 }
+int fmri_diffaug_params(const int64_t* state, float* table, int rows, int64_t row0, int sid, int H, int sh, int cut,
+                        int policy_mask, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !table || ((uintptr_t)table & 15) || rows < 1 || row0 < 0 ||
+        row0 > (1ll << 40) || sid < 0 || H < 1 || sh < 0 || sh > H || cut < 0 || cut > H || (policy_mask & ~7))
+        return FMRI_E_BADARG;
+    if (H > 128) return FMRI_E_UNSUPPORTED;
+    return diffaug_params_launch(state, table, rows, row0, sid, H, sh, cut, policy_mask, S(stream));
+}
+// the checks fmri_diffaug_fwd / fmri_diffaug_bwd share, for one (input, output) pair of [N][H][W][8] fp16 tensors
+static int diffaug_check(const void* src, const void* dst, int N, int H, int W, const float* table, int B, int img0) {
+    if (!src || ((uintptr_t)src & 15) || !dst || ((uintptr_t)dst & 15) || !table || ((uintptr_t)table & 15) || N < 1 ||
+        H < 1 || W < 1 || B < 1 || img0 < 0 || (int64_t)img0 + N > 3ll * B)
+        return FMRI_E_BADARG;
+    if (H != W || H > 128) return FMRI_E_UNSUPPORTED;
+    const uintptr_t bytes = (uintptr_t)N * H * W * 16, s = (uintptr_t)src, d = (uintptr_t)dst;
+    if (s < d + bytes && d < s + bytes) return FMRI_E_BADARG;
+    return FMRI_OK;
+}
+int fmri_diffaug_fwd(const void* src16, void* dst16, int N, int H, int W, const float* table, int B, int img0,
+                     void* stream) {
+    const int rc = diffaug_check(src16, dst16, N, H, W, table, B, img0);
+    if (rc != FMRI_OK) return rc;
+    return diffaug_fwd_launch((const half_t*)src16, (half_t*)dst16, N, H, table, B, img0, S(stream));
+}
+int fmri_diffaug_bwd(const void* g_a, void* dst_a, const void* g_b, void* dst_b, int N, int H, int W, const float* table,
+                     int B, int img0, void* stream) {
+    int rc = diffaug_check(g_a, dst_a, N, H, W, table, B, img0);
+    if (rc != FMRI_OK) return rc;
+    if ((g_b == nullptr) != (dst_b == nullptr)) return FMRI_E_BADARG;
+    if (g_b) {
+        rc = diffaug_check(g_b, dst_b, N, H, W, table, B, img0);
+        if (rc == FMRI_OK) rc = diffaug_check(g_a, dst_b, N, H, W, table, B, img0);      // no output over an input
+        if (rc == FMRI_OK) rc = diffaug_check(g_b, dst_a, N, H, W, table, B, img0);
+        if (rc == FMRI_OK) rc = diffaug_check(dst_a, dst_b, N, H, W, table, B, img0);
+        if (rc != FMRI_OK) return rc;
+    }
+    return diffaug_bwd_launch((const half_t*)g_a, (half_t*)dst_a, (const half_t*)g_b, (half_t*)dst_b, N, H, table, B,
+                              img0, S(stream));
+}
 int fmri_schedule_seek_host(fmri_schedule* s, int64_t epoch, float* out7) {
     if (!s || s->lr_step < 1 || epoch < 0) return FMRI_E_BADARG;
     return schedule_seek_host(s, epoch, out7);

@@ -279,6 +279,12 @@ int rng_u32_launch(const int64_t* state, int32_t* out, int64_t n, int64_t start,
 int rng_advance_launch(int64_t* state, int64_t nblocks, hipStream_t st);
 int sampler_indices_launch(const int64_t* state, int N, int B, int64_t row0, int32_t* idx, hipStream_t st);
 int sampler_advance_launch(int64_t* state, int64_t N, int64_t B_global, hipStream_t st);
+// csrc/diffaug.hip (square images of H x H pixels; `img0`: the first image's index in the [orig | pred | sampled] layout)
+int diffaug_params_launch(const int64_t* state, float* table, int rows, int64_t row0, int sid, int H, int sh, int cut,
+                          int policy, hipStream_t st);
+int diffaug_fwd_launch(const half_t* src, half_t* dst, int N, int H, const float* table, int B, int img0, hipStream_t st);
+int diffaug_bwd_launch(const half_t* ga, half_t* da, const half_t* gb, half_t* db, int N, int H, const float* table, int B,
+                       int img0, hipStream_t st);
 // csrc/schedule.hip (`sched`: an fmri_schedule of include/fmri_hip.h)
 int epoch_begin_launch(const int64_t* feed_state, void* sched, float* lr0, float* lr1, float* lr2, float* lr3, float* hp3,
                        int64_t* epoch_out, hipStream_t st);

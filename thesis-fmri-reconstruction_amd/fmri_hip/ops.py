@@ -1562,6 +1562,57 @@ def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float, out: O
     return out
 
 
+def _aug_image_check(t: torch.Tensor, what: str):
+    if t.dtype != torch.float16 or t.dim() != 4 or t.shape[3] != 8 or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous fp16 [N,H,W,8] tensor is needed")
+
+
+def diffaug_params(state: torch.Tensor, table: torch.Tensor, row0: int, sid: int, H: int, sh: int, cut: int,
+                   policy_mask: int):
+    """Rows of a differentiable-augmentation table (fp32 [rows, 8], a contiguous slice is fine): global rows
+    ``row0 ..`` of stream ``sid`` at the generator state's offset (csrc/diffaug.hip; include/fmri_hip.h
+    fmri_diffaug_params).  Does not move the offset."""
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise ValueError("diffaug_params: table must be a contiguous fp32 [rows, 8] tensor")
+    lib.call("fmri_diffaug_params", _P(state), _P(table), table.shape[0], int(row0), int(sid), int(H), int(sh), int(cut),
+             int(policy_mask))
+    return table
+
+
+def diffaug_fwd(x16: torch.Tensor, table: torch.Tensor, B: int, img0: int = 0, out: Optional[torch.Tensor] = None):
+    """T_p of every image of ``x16`` (fp16 [N,H,W,8]; images img0 .. img0 + N of the [orig | pred | sampled] layout of B
+    each) under its row of ``table`` (fp32 [2B, 8]) into a new tensor (include/fmri_hip.h fmri_diffaug_fwd)."""
+    _aug_image_check(x16, "diffaug_fwd")
+    N, H, W, _ = x16.shape
+    if out is None:
+        out = torch.empty_like(x16)
+    lib.note(bytes=2.0 * x16.numel() * 2)
+    lib.call("fmri_diffaug_fwd", _P(x16), _P(out), N, H, W, _P(table), int(B), int(img0))
+    return out
+
+
+def diffaug_bwd(g_a: Optional[torch.Tensor], g_b: Optional[torch.Tensor], table: torch.Tensor, B: int, img0: int,
+                out=None):
+    """The adjoint of T_p's linear part on one or two cotangent streams of the same images (fp16 [N,H,W,8] each, either
+    may be None) in ONE launch; returns new tensors -- or those of the pair ``out`` -- in the same positions
+    (include/fmri_hip.h fmri_diffaug_bwd)."""
+    gs = [g for g in (g_a, g_b) if g is not None]
+    if not gs:
+        return None, None
+    for g in gs:
+        _aug_image_check(g, "diffaug_bwd")
+    if len(gs) == 2 and gs[0].shape != gs[1].shape:
+        raise ValueError("diffaug_bwd: the two streams must cover the same images")
+    N, H, W, _ = gs[0].shape
+    outs = [torch.empty_like(g) for g in gs] if out is None else [o for o, g in zip(out, (g_a, g_b)) if g is not None]
+    second = (gs[1], outs[1]) if len(gs) == 2 else (None, None)
+    lib.note(bytes=2.0 * len(gs) * gs[0].numel() * 2)
+    lib.call("fmri_diffaug_bwd", _P(gs[0]), _P(outs[0]), _P(second[0]), _P(second[1]), N, H, W, _P(table), int(B),
+             int(img0))
+    it = iter(outs)
+    return tuple(next(it) if g is not None else None for g in (g_a, g_b))
+
+
 def ingest_u8(images_u8: torch.Tensor, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), flip: Optional[torch.Tensor] = None,
               shift: Optional[torch.Tensor] = None, want16: bool = True, want32: bool = False):
     """uint8 [N,H,W,C] (C = 1 or 3, device) -> (fp16 NHWC8 engine input or None, fp32 NCHW or None): per-image

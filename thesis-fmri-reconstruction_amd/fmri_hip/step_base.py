@@ -9,6 +9,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import lib, ops
+from .augment import _check_table, blocks as aug_blocks
 from .monitor import Monitored
 from .nets import refresh_net
 from .rng import DeviceRng, StepNoise
@@ -251,6 +252,10 @@ class _StepBase(Monitored):
     log: Optional[TrainLog] = None
     checkpoints: Optional[StateRing] = None
     ema = None                                   # fmri_hip.ema.WeightEma or None
+    augment = None                               # fmri_hip.augment.DiffAugment or None
+    _aug_req = None                              # (caller's table or None, B, H) of the forward pass being issued
+    _aug_buf: Optional[torch.Tensor] = None      # the persistent table a step draws into
+    _last_aug: Optional[torch.Tensor] = None
     _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
@@ -269,6 +274,55 @@ class _StepBase(Monitored):
         self._last_noise: Dict[str, torch.Tensor] = {}
         self.feed = feed             # fmri_hip.feed.DeviceFeed or None
         self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
+
+    # ---- differentiable augmentation of the discriminator's inputs (fmri_hip/augment.py) ------------------------------
+    def _init_augment(self, augment):
+        """``augment=`` of the step classes that have an image discriminator.  None: nothing is added -- the step issues
+        the launches it always did."""
+        self.augment = augment
+
+    def _aug_begin(self, aug, B: int, H: int):
+        """In front of ``_resolve_noise``: what the forward pass about to be issued wants for its table -- ``aug`` as it
+        is, or, left out, a draw by the step's generator at the offset of the noise draws."""
+        if self.augment is None:
+            if aug is not None:
+                raise ValueError(f"{type(self).__name__}: aug= given, but the step was constructed without "
+                                 "augment=DiffAugment(...)")
+            return
+        self._aug_req = (aug, B, H)
+
+    def _aug_resolve(self) -> int:
+        """The table of the pending request into ``_last_aug``; returns the blocks of the generator the step's ONE advance
+        has to cover for it (0 for a table the caller passed)."""
+        req, self._aug_req = self._aug_req, None
+        if req is None:
+            return 0
+        aug, B, H = req
+        if aug is not None:
+            _check_table(aug, B)
+            self._last_aug = aug
+            return 0
+        if self.rng is None:
+            raise ValueError(f"{type(self).__name__}: aug not given and the step has no rng (pass the table, or "
+                             "construct the step with rng=DeviceRng(seed, device))")
+        dd = self.dd
+        rank = dd.dist.get_rank() if dd.on else 0
+        if self._aug_buf is None or self._aug_buf.shape[0] != 2 * B:
+            self._aug_buf = torch.empty(2 * B, 8, dtype=torch.float32, device=self.device)
+        self._last_aug = self.augment.table(self.rng, B, H, row0=rank * B, out=self._aug_buf)
+        return aug_blocks(B * dd.world)
+
+    def last_augment(self) -> Optional[torch.Tensor]:
+        """The fp32 [2B, 8] augmentation table the last step used (the step's own buffer where it drew it: clone what
+        has to outlive the next step); None for a step without ``augment=``."""
+        return self._last_aug
+
+    def _aug_adjoint(self, dimg_a, dimg_b, rows: slice):
+        """The image cotangents ``DiscriminatorNet.backward`` returned for images ``rows`` of the 3B layout, taken back
+        through the transform of the last forward pass -- both streams in one launch; as they are without ``augment=``."""
+        if self.augment is None or (dimg_a is None and dimg_b is None):
+            return dimg_a, dimg_b
+        return self.augment.adjoint((dimg_a, dimg_b), self.fw["aug"], self.fw["B"], rows)
 
     def _init_schedule(self, schedule: Optional[EpochSchedule], default_mask=None, hp=None, hp_dev=None):
         """``schedule=`` of the step classes (fmri_hip/schedule.py), after ``optims`` is complete.  ``default_mask``: which
@@ -417,6 +471,8 @@ class _StepBase(Monitored):
         sig.append("log=" + ("none" if self.log is None else ",".join(self.log.names) + f"@{self.log.capacity}"))
         if self.ema is not None:
             sig.append(self.ema.signature())
+        if self.augment is not None:
+            sig.append(f"augment={self.augment!r}")
         return sig
 
     def _host_state(self) -> dict:
@@ -556,10 +612,12 @@ class _StepBase(Monitored):
         self._feed_blocks = feed.rng_blocks() if shared else 0
         return x, fm, feed.fmri16
 
-    def _feed_advance(self):
-        """The shared generator's advance for a step that drew no noise after its feed drew augmentation."""
-        if self._feed_blocks:
-            self.rng.advance(self._feed_blocks)
+    def _feed_advance(self, at_least: int = 0):
+        """The shared generator's advance for a step that drew no noise after its feed drew augmentation, or after it
+        drew its own augmentation table (``at_least`` blocks)."""
+        n = max(self._feed_blocks, int(at_least))
+        if n:
+            self.rng.advance(n)
             self._feed_blocks = 0
 
     def _resolve_noise(self, B: int, wanted):
@@ -567,11 +625,13 @@ class _StepBase(Monitored):
         the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
         [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
         draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
-        the same generator in this step, if that is larger.  Returns the tensors in the order asked for."""
+        the same generator in this step, or of the augmentation table the step draws (``_aug_begin``), if that is larger.
+        Returns the tensors in the order asked for."""
         missing = [name for name, _, t in wanted if t is None]
         if missing and self._noise is None:
             raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
                              "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
+        aug_drawn = self._aug_resolve()          # at the offset of the noise draws: nothing has advanced yet
         Z = self.cfg.latent_dim
         dd = self.dd
         rank = dd.dist.get_rank() if dd.on else 0
@@ -581,10 +641,10 @@ class _StepBase(Monitored):
         for name, sid, t in wanted:
             out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
         if missing:
-            self._noise.end(B * dd.world, Z, at_least=self._feed_blocks)
+            self._noise.end(B * dd.world, Z, at_least=max(self._feed_blocks, aug_drawn))
             self._feed_blocks = 0
         else:
-            self._feed_advance()
+            self._feed_advance(aug_drawn)
         self._last_noise = out
         return list(out.values())
 

@@ -120,6 +120,16 @@ class _GanStepBase(_StepBase):
                 setattr(hp, name, float(v))
         self.hp_dev.copy_(torch.tensor([hp.lambda_mse, hp.equilibrium, hp.margin, hp.beta], dtype=torch.float32))
 
+    def _discriminate(self, disc_in, B):
+        """The discriminator's forward pass on the 3B images ``[orig | pred | sampled]`` -- with ``augment=`` on their
+        transforms under the table of this pass (``disc_in`` itself stays what it is for the pixel term and the
+        views).  Returns (feat, logit32, ctx, what ``fw`` notes about the augmentation)."""
+        if self.augment is None:
+            return (*self.dis.forward(disc_in), {})
+        table = self._last_aug
+        disc_aug = self.augment.forward(disc_in, table, B)
+        return (*self.dis.forward(disc_aug), dict(disc_aug=disc_aug, aug=table))
+
     def _gan_losses(self, feat, logit32, B, x16, xt16, H, W):
         """BCE / feature-mse / pixel terms of VaeGan.loss into the scalar block (+ all-reduce)."""
         dev = feat.device
@@ -238,8 +248,16 @@ class Stage1Step(_GanStepBase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  distributed: bool = False, sync_bn: bool = True, mode: str = "vae-gan", gate_skip: bool = True,
                  monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None,
-                 recon_level: int = 3, checkpoints=None, ema=None):
-        """``ema``: a fmri_hip.ema.WeightEma; the step then keeps an exponential moving average of the weights and BatchNorm
+                 recon_level: int = 3, checkpoints=None, ema=None, augment=None):
+        """``augment``: a fmri_hip.augment.DiffAugment; every image the discriminator sees -- orig, pred and sampled -- then
+        goes through one random colour / translation / cutout transform (one launch in front of the discriminator's
+        forward pass), and the image cotangents that come back out of the discriminator go through its adjoint (one
+        launch) before anything reads them.  The pixel ``nle`` term, ``outputs()``, the evaluator and the grids keep the
+        un-augmented images.  The per-image parameters follow the noise convention: a table passed as
+        ``step(..., aug=table)`` is used as it is; left out, it is drawn by the step's ``rng`` at the offset of the noise
+        draws (ValueError without one), recorded steps draw a fresh one at every replay; ``last_augment()`` reads it.
+        None: nothing is added.
+        ``ema``: a fmri_hip.ema.WeightEma; the step then keeps an exponential moving average of the weights and BatchNorm
         statistics of the networks it names (default: the trained ones the eval forward uses) on the device -- one launch
         behind every optimizer update, two at the end of the step, recorded steps included; ``ema_state_dict()`` reads it,
         ``Evaluator(..., weights="ema")`` evaluates with it.  None: nothing is added.
@@ -282,6 +300,7 @@ class Stage1Step(_GanStepBase):
         self._init_common(device, hp, scales, distributed, sync_bn, (self.enc, self.dec, self.dis))
         self._pre_replay = [self.dec.fc_bn._running_in]      # reloads after an outside write of the buffers only
         self._init_rng(rng, feed)
+        self._init_augment(augment)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.enc.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -316,10 +335,12 @@ class Stage1Step(_GanStepBase):
             n.group.load_state_dict(sd, pre)
 
     # ---- the step ---------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, z_p: Optional[torch.Tensor] = None):
+    def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, z_p: Optional[torch.Tensor] = None,
+                aug: Optional[torch.Tensor] = None):
         require_gpu(x)
         cfg = self.cfg
         B, _, H, W = x.shape
+        self._aug_begin(aug, B, H)
         eps, z_p = self._resolve_noise(B, [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)])
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = x.device
@@ -339,10 +360,10 @@ class Stage1Step(_GanStepBase):
         if G == 3:
             lib.call("fmri_latent_fwd", _P(head32), None, B, Z, zp, _P(z16[2 * B:]), None, None, 0)
         _, dctx = self.dec.forward(z16, G, out=dec_out[B:], zscale=self.zs)
-        feat, logit32, sctx = self.dis.forward(disc_in)
+        feat, logit32, sctx, seen = self._discriminate(disc_in, B)
         prob, F = self._gan_losses(feat, logit32, B, disc_in[:B], disc_in[B:2 * B], H, W)
         self.fw = dict(B=B, H=H, W=W, F=F, disc_in=disc_in, head32=head32, eps=eps, ectx=ectx, dctx=dctx, sctx=sctx,
-                       feat=feat, logit32=logit32, prob=prob)
+                       feat=feat, logit32=logit32, prob=prob, **seen)
         return self.fw
 
     def gate(self, B_global: int):
@@ -378,6 +399,7 @@ class Stage1Step(_GanStepBase):
         self._applied_early = early
         dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B),
                                            join=dp and not early, **stacked)
+        dimg_a, dimg_b = self._aug_adjoint(dimg_a, dimg_b, slice(B, 3 * B))
         if early:
             ops.side_run(dev, lambda: self._reduce_apply(self.opt_dis, self.dis, self.flags[0:1], S_NA))
         else:
@@ -445,6 +467,7 @@ class Stage1Step(_GanStepBase):
         x16, xt16 = d_in[:B], d_in[B:2 * B]
         if self.mode == "dcgan":
             dimg_a, _ = self.dis.backward(fw["sctx"], dlogit16, sc.a, None, sc.b, True, slice(B, 3 * B), join=dp)
+            dimg_a, _ = self._aug_adjoint(dimg_a, None, slice(B, 3 * B))
             self.dd.all_reduce_async(self.dis.group.grad)
             # stored = dec * nA * (lambda * d nle - (1-lambda) * A), d nle / d x_tilde = x_tilde - x
             dnle = axpby(xt16, x16, 1.0, -1.0)
@@ -505,7 +528,7 @@ class Stage1Step(_GanStepBase):
         self.opt_dec.step(self.flags[1:2], gdev=self._slot(S_GDEC))
         self.opt_dis.step(self.flags[0:1], gdev=self._slot(S_NA))
 
-    def capture_forward(self, x, eps=None, z_p=None, warmup: int = 2):
+    def capture_forward(self, x, eps=None, z_p=None, warmup: int = 2, aug=None):
         """Hybrid launch mode (one GPU): the forward pass + gate -- a dependent chain with nothing to overlap -- is
         recorded into a HIP graph, the backward pass and the updates stay eagerly issued launches on two streams
         (``ops.side_run``).  Halves the Python work per step, which is what decides whether a slow host can keep the
@@ -521,7 +544,7 @@ class Stage1Step(_GanStepBase):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                self.step(x, eps, z_p)
+                self.step(x, eps, z_p, aug)
             ops.join_side()
             for n in nets:
                 refresh_net(n)               # so that the recorded forward contains no refresh launches
@@ -532,7 +555,7 @@ class Stage1Step(_GanStepBase):
         self._defer_loss_reduce = not gate_in_graph      # the forward's only collective (sum of the loss scalars)
         try:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self.forward(x, eps, z_p)
+                self.forward(x, eps, z_p, aug)
                 if gate_in_graph:
                     self.gate(B)
         finally:
@@ -557,13 +580,14 @@ class Stage1Step(_GanStepBase):
         self._fwd_graph = graph
         return run
 
-    def step(self, x=None, eps=None, z_p=None):
+    def step(self, x=None, eps=None, z_p=None, aug=None):
         """One full training step; returns the device scalar block (see LOG_KEYS) without syncing.  ``eps`` / ``z_p``
-        left out: drawn by the step's ``rng`` (ValueError without one).  ``x`` left out: the step's ``feed`` draws it."""
+        left out: drawn by the step's ``rng`` (ValueError without one).  ``x`` left out: the step's ``feed`` draws it.
+        ``aug`` (steps with ``augment=``): the fp32 [2B, 8] table of this step's transforms; left out, the ``rng`` draws it."""
         fed = self._fed(x)
         if fed is not None:
             x = fed[0]
-        fw = self.forward(x, eps, z_p)
+        fw = self.forward(x, eps, z_p, aug)
         self.gate(fw["B"] * self.dd.world)
         self.backward(early_apply=True)
         self.apply()
@@ -605,8 +629,11 @@ class CognitiveStep(_GanStepBase):
     def __init__(self, cfg: ArchConfig, n_voxels: int, device, stage: int, hp: Optional[GanHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
-                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None, ema=None):
-        """``ema``: a fmri_hip.ema.WeightEma (see Stage1Step): by default the cognitive encoder in Stage II, the decoder in
+                 rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None, ema=None,
+                 augment=None):
+        """``augment``: a fmri_hip.augment.DiffAugment (see Stage1Step); in Stage II, mode 'vae-gan', the "real" image that
+        shares its transform with x_tilde is the teacher's reconstruction.
+        ``ema``: a fmri_hip.ema.WeightEma (see Stage1Step): by default the cognitive encoder in Stage II, the decoder in
         Stage III -- a frozen network has no average.
         ``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step); the frozen networks and the teacher are state too.
         The discriminator keeps ``recon_level`` 3: the Stage-II / Stage-III scripts build theirs with the default
@@ -639,6 +666,7 @@ class CognitiveStep(_GanStepBase):
         if feed is not None and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
             raise ValueError("CognitiveStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
         self._init_rng(rng, feed)
+        self._init_augment(augment)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -694,12 +722,13 @@ class CognitiveStep(_GanStepBase):
 
     def forward(self, fmri: torch.Tensor, image: torch.Tensor, eps: Optional[torch.Tensor] = None,
                 z_p: Optional[torch.Tensor] = None, eps_teacher: Optional[torch.Tensor] = None,
-                fmri16: Optional[torch.Tensor] = None):
+                fmri16: Optional[torch.Tensor] = None, aug: Optional[torch.Tensor] = None):
         """``fmri16``: the fp16 [B, pad8(V)] rows of ``fmri`` where the caller already has them (a feed's gather pass
         writes both); otherwise they are made here."""
         require_gpu(fmri)
         cfg = self.cfg
         B, _, H, W = image.shape
+        self._aug_begin(aug, B, H)
         wanted = [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)]
         if self.teacher_enc is not None:
             wanted.append(("eps_teacher", SID_EPS_TEACHER, eps_teacher))
@@ -734,10 +763,10 @@ class CognitiveStep(_GanStepBase):
             lib.call("fmri_rows_f32_to_f16", _P(z_p.contiguous().float()), _P(z16[B:]), B, Z, zp, 1.0)
             _, dctx = self.dec.forward(z16, 2, out=disc_in[B:], zscale=self.zs)
             g_tilde, g_p = 0, 1
-        feat, logit32, sctx = self.dis.forward(disc_in)
+        feat, logit32, sctx, seen = self._discriminate(disc_in, B)
         prob, F = self._gan_losses(feat, logit32, B, disc_in[:B], disc_in[B:2 * B], H, W)
         self.fw = dict(B=B, H=H, W=W, F=F, disc_in=disc_in, head32=head32, eps=eps, cctx=cctx, dctx=dctx, sctx=sctx,
-                       feat=feat, logit32=logit32, prob=prob, g_tilde=g_tilde, g_p=g_p)
+                       feat=feat, logit32=logit32, prob=prob, g_tilde=g_tilde, g_p=g_p, **seen)
         return self.fw
 
     def gate(self, B_global: int):
@@ -763,6 +792,7 @@ class CognitiveStep(_GanStepBase):
             ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
             _, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 2 * B),
                                           img_streams=(False, True), **stacked)
+            _, dimg_b = self._aug_adjoint(None, dimg_b, slice(B, 2 * B))
             self._reduce_async(self.dis.group)                  # under the decoder / cognitive-encoder backward
             entries = [dict(g=fw["g_tilde"], scale=sc.b, train=False, need_dz=True)]
             dz = self.dec.backward(fw["dctx"], dimg_b, entries)[0]
@@ -775,6 +805,7 @@ class CognitiveStep(_GanStepBase):
             ops.begin_grads(self.dis.group, fuse, gate=self._gate_flag(0))
             dimg_a, dimg_b = self.dis.backward(fw["sctx"], dlogit16, sc.a, dfeat16, sc.b, True, slice(B, 3 * B),
                                                **stacked)
+            dimg_a, dimg_b = self._aug_adjoint(dimg_a, dimg_b, slice(B, 3 * B))
             self._reduce_async(self.dis.group)                  # under the decoder backward
             cot = axpby(dimg_b, dimg_a, sc.dec / sc.b, -sc.dec / sc.a, a_dev=self._slot(S_C1), b_dev=self._slot(S_C2))
             entries = [dict(g=0, scale=sc.dec, train=True), dict(g=1, scale=sc.dec, train=True)]
@@ -826,12 +857,12 @@ class CognitiveStep(_GanStepBase):
             self.opt_dec.step(self.flags[1:2], clamp=1.0, gdev=self._slot(S_GDEC))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))
 
-    def step(self, fmri=None, image=None, eps=None, z_p=None, eps_teacher=None):
+    def step(self, fmri=None, image=None, eps=None, z_p=None, eps_teacher=None, aug=None):
         fed = self._fed(fmri, image)
         fmri16 = None
         if fed is not None:
             image, fmri, fmri16 = fed
-        fw = self.forward(fmri, image, eps, z_p, eps_teacher, fmri16=fmri16)
+        fw = self.forward(fmri, image, eps, z_p, eps_teacher, fmri16=fmri16, aug=aug)
         self.gate(fw["B"] * self.dd.world)
         self.backward(fuse=True)
         self.apply()

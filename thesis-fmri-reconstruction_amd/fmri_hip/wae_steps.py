@@ -345,8 +345,9 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
     def __init__(self, cfg: ArchConfig, device, hp: Optional[GanHyper] = None, scales: Optional[Scales] = None,
                  lam: float = 1.0, distributed: bool = False, sync_bn: bool = True, torch14_zero_grad: bool = True,
                  mode: str = "vae-gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, recon_level: int = 3, checkpoints=None, ema=None):
-        """``ema``: a fmri_hip.ema.WeightEma (see Stage1Step); ``"wae_discriminator"`` names the latent discriminator.
+                 schedule=None, log=None, recon_level: int = 3, checkpoints=None, ema=None, augment=None):
+        """``augment``: a fmri_hip.augment.DiffAugment in front of the IMAGE discriminator (see Stage1Step).
+        ``ema``: a fmri_hip.ema.WeightEma (see Stage1Step); ``"wae_discriminator"`` names the latent discriminator.
         ``checkpoints``: a fmri_hip.state.StateRing (see Stage1Step).
         ``recon_level``: the script's ``--recon_level`` (wae_vgan_stage1.py:71,199), as in Stage1Step.
         ``rng``: a fmri_hip.rng.DeviceRng; ``step(x)`` then draws ``eps``, ``z_p`` and ``z_fake_noise`` on the device
@@ -357,7 +358,7 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         there the image discriminator's rate never decays and the latent discriminator's does:
         ``EpochSchedule(..., lr_mask=(True, True, False, True))`` reproduces that literally."""
         super().__init__(cfg, device, hp, scales, distributed, sync_bn, mode=mode, rng=rng, feed=feed,
-                         recon_level=recon_level)
+                         recon_level=recon_level, augment=augment)
         hp = self.hp
         self.lam = lam
         self.torch14 = torch14_zero_grad
@@ -392,14 +393,15 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         super()._restored(host)
         self._it = int(host.get("it", self._it))
 
-    def step(self, x=None, eps=None, z_p=None, z_fake_noise=None):
+    def step(self, x=None, eps=None, z_p=None, z_fake_noise=None, aug=None):
         fed = self._fed(x)
         if fed is not None:
             x = fed[0]
+        self._aug_begin(aug, x.shape[0], x.shape[2])     # drawn with the noise: the one advance covers it
         eps, z_p, z_fake_noise = self._resolve_noise(x.shape[0], [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
                                                                   ("z_fake_noise", SID_ZFAKE, z_fake_noise)])
         noise = self._last_noise
-        fw = self.forward(x, eps, z_p)
+        fw = self.forward(x, eps, z_p, self._last_aug if self.augment is not None else None)
         self._last_noise = noise             # (forward records its two)
         self.gate(fw["B"] * self.dd.world)
         B, Z = fw["B"], self.cfg.latent_dim
