@@ -673,6 +673,42 @@ int fmri_diffaug_fwd(const void* src16, void* dst16, int N, int H, int W, const 
                      void* stream);
 int fmri_diffaug_bwd(const void* g_a, void* dst_a, const void* g_b, void* dst_b, int N, int H, int W, const float* table,
                      int B, int img0, void* stream);
+/* ---- augmentation of the fMRI rows of the Stage-II / Stage-III steps (csrc/voxaug.hip; fmri_hip/voxaug.py) -------------
+ * Trial noise, voxel dropout, a masked span of voxels (an "ROI") and gain jitter on the rows the cognitive encoder reads.
+ * The reference has no counterpart; the contract is the formula below.  Batch row b, global row r = row0 + b (a rank k of
+ * a data-parallel run passes row0 = k * B), voxel c < V, state [seed, offset] as for fmri_rng_normal:
+ *
+ *     y[b][c] = 0                                             if s_b <= c < s_b + L_b        (span mask)
+ *             = 0                                             if dropped(b, c)
+ *             = k_b * fma(sigma_b, n[r][c], g_b * x[b][c])    otherwise
+ *
+ *   in fp32 -- the product g x rounded, then the fma (left out where sigma_b == 0), then the product with k_b rounded --
+ *   and then ONE rounding to fp16, the conversion of fmri_rows_f32_to_f16.  dst16 is fp16 [B][pad8(V)], columns V ..
+ *   pad8(V) zero; dst32 (may be NULL) takes the fp32 value before that last rounding, [B][V].
+ *   n[r][c]       element r V + c of stream sid_noise in the layout of fmri_rng_normal with cols = V: word (r V + c) % 4
+ *                 of block offset + (r V + c) / 4, through the same Box-Muller -- bit for bit what
+ *                 fmri_rng_normal(state, out, B, V, V, row0, sid_noise, 1) writes to out[b][c] at the same offset.
+ *   dropped(b,c)  word (r V + c) % 4 of block offset + (r V + c) / 4 of stream sid_drop  <  (uint32)((double)p_b 2^32):
+ *                 a comparison of integers.
+ *   One step consumes (B_global V + 3) / 4 blocks, the two element streams alike.
+ * table: fp32 [B][8], 16-byte aligned, row b = [g, sigma, p, k, s, L, 0, 0] (s, L integers as exact floats: V < 2^24).
+ *   The neutral row [1, 0, 0, 1, 0, 0, 0, 0] gives bit for bit the rows of fmri_rows_f32_to_f16 at scale 1 (a negative
+ *   zero included); a row with sigma == 0 / p == 0 evaluates no block of the noise / dropout stream.
+ * fmri_voxaug_params: table rows b < rows from ONE Philox block per global row: block offset + row0 + b of stream
+ *   sid_row, words w0 .. w3:
+ *     the row is augmented iff prob >= 1 or w3 < (uint32)((double)prob 2^32); otherwise it is the neutral row;
+ *     g = fma(gain, z0(w0, w1), 1), z0 the first Box-Muller output of the pair;  sigma and p as passed;
+ *     k = 1 / (1 - p) in fp32 where rescale != 0 (inverted dropout), else 1 -- computed here, fmri_voxaug_apply reads it;
+ *     s = (w2 (V - span_len + 1)) >> 32,  L = span_len.
+ *   The offset is not moved; the row stream consumes B_global blocks.
+ * Errors, before anything is launched or dereferenced: a NULL or misaligned pointer (state 8, table and dst16 16, src32
+ * and dst32 4 bytes), dst32 overlapping src32, rows, B, V < 1, V >= 2^24, row0 < 0 or > 2^40, a negative stream id,
+ * sid_noise == sid_drop, span_len outside [0, V], gain or sigma < 0, p outside [0, 1), prob outside [0, 1]:
+ * FMRI_E_BADARG; B V > 2^31 - 1: FMRI_E_UNSUPPORTED.  Enqueue-only, no allocation, no global state. */
+int fmri_voxaug_params(const int64_t* state, float* table, int rows, int64_t row0, int sid_row, int V, float gain,
+                       float sigma, float p, int rescale, int span_len, float prob, void* stream);
+int fmri_voxaug_apply(const float* src32, int V, int B, const float* table, const int64_t* state, int64_t row0,
+                      int sid_noise, int sid_drop, void* dst16, float* dst32, void* stream);
 /* starting cotangents of the two back-propagated streams, fp16, multiplied by gscale * (*norm) (norm: device float) */
 int fmri_gan_head_bwd(const float* logit, int ldl, int B, void* dlogit, int ldg, float gscale, const float* norm,
                       void* stream);

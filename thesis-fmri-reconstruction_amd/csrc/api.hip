@@ -1376,6 +1376,26 @@ int fmri_diffaug_bwd(const void* g_a, void* dst_a, const void* g_b, void* dst_b,
     return diffaug_bwd_launch((const half_t*)g_a, (half_t*)dst_a, (const half_t*)g_b, (half_t*)dst_b, N, H, table, B,
                               img0, S(stream));
 }
+int fmri_voxaug_params(const int64_t* state, float* table, int rows, int64_t row0, int sid_row, int V, float gain,
+                       float sigma, float p, int rescale, int span_len, float prob, void* stream) {
+    if (!state || ((uintptr_t)state & 7) || !table || ((uintptr_t)table & 15) || rows < 1 || row0 < 0 ||
+        row0 > (1ll << 40) || sid_row < 0 || V < 1 || V >= (1 << 24) || span_len < 0 || span_len > V || !(gain >= 0.f) ||
+        !(sigma >= 0.f) || !(p >= 0.f && p < 1.f) || !(prob >= 0.f && prob <= 1.f))
+        return FMRI_E_BADARG;
+    return voxaug_params_launch(state, table, rows, row0, sid_row, V, gain, sigma, p, rescale ? 1 : 0, span_len, prob,
+                                S(stream));
+}
+int fmri_voxaug_apply(const float* src32, int V, int B, const float* table, const int64_t* state, int64_t row0,
+                      int sid_noise, int sid_drop, void* dst16, float* dst32, void* stream) {
+    if (!src32 || ((uintptr_t)src32 & 3) || !table || ((uintptr_t)table & 15) || !state || ((uintptr_t)state & 7) ||
+        !dst16 || ((uintptr_t)dst16 & 15) || ((uintptr_t)dst32 & 3) || V < 1 || V >= (1 << 24) || B < 1 || row0 < 0 ||
+        row0 > (1ll << 40) || sid_noise < 0 || sid_drop < 0 || sid_noise == sid_drop)
+        return FMRI_E_BADARG;
+    if ((int64_t)B * V > INT32_MAX) return FMRI_E_UNSUPPORTED;
+    const uintptr_t bytes = (uintptr_t)B * V * 4, s = (uintptr_t)src32, d = (uintptr_t)dst32;
+    if (dst32 && s < d + bytes && d < s + bytes) return FMRI_E_BADARG;               // no fp32 result over its input
+    return voxaug_apply_launch(src32, V, B, table, state, row0, sid_noise, sid_drop, (half_t*)dst16, dst32, S(stream));
+}
 int fmri_schedule_seek_host(fmri_schedule* s, int64_t epoch, float* out7) {
     if (!s || s->lr_step < 1 || epoch < 0) return FMRI_E_BADARG;
     return schedule_seek_host(s, epoch, out7);

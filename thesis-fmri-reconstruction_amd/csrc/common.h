@@ -422,6 +422,17 @@ __device__ __forceinline__ h4 bn_bwd_mask4(const f4& v, const h4& xr, const f4& 
     return hv;
 }
 
+// (half_t)(a * b) as the two roundings it is written as: the product rounded to fp32, then the cast.  Left as one
+// expression hipcc selects v_fma_mixlo_f16 (a * b + 0, also under -ffp-contract=off), which rounds the exact product to
+// fp16 ONCE and adds +0: a negative zero comes out as +0, and where the two roundings do not commute the bits differ from
+// the cast of the fp32 product that numpy and torch give (1.5 * 2^-24 at scale 1/3: 2^-24 instead of 0;
+// tests/test_glue_kernels_gpu.py::test_row_conversions).  The empty asm keeps the two operations apart.
+__device__ __forceinline__ half_t mul_then_f16(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return (half_t)p;
+}
+
 __device__ __forceinline__ float act_apply(float v, int act) {
     if (act == ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == ACT_TANH) return tanhf(v);

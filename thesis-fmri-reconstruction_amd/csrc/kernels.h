@@ -285,6 +285,11 @@ int diffaug_params_launch(const int64_t* state, float* table, int rows, int64_t 
 int diffaug_fwd_launch(const half_t* src, half_t* dst, int N, int H, const float* table, int B, int img0, hipStream_t st);
 int diffaug_bwd_launch(const half_t* ga, half_t* da, const half_t* gb, half_t* db, int N, int H, const float* table, int B,
                        int img0, hipStream_t st);
+// csrc/voxaug.hip (fMRI rows fp32 [B][V] -> fp16 [B][pad8(V)]; `table`: fp32 [B][8], include/fmri_hip.h fmri_voxaug_apply)
+int voxaug_params_launch(const int64_t* state, float* table, int rows, int64_t row0, int sid, int V, float gain, float sigma,
+                         float p, int rescale, int span_len, float prob, hipStream_t st);
+int voxaug_apply_launch(const float* src, int V, int B, const float* table, const int64_t* state, int64_t row0,
+                        int sid_noise, int sid_drop, half_t* dst16, float* dst32, hipStream_t st);
 // csrc/schedule.hip (`sched`: an fmri_schedule of include/fmri_hip.h)
 int epoch_begin_launch(const int64_t* feed_state, void* sched, float* lr0, float* lr1, float* lr2, float* lr3, float* hp3,
                        int64_t* epoch_out, hipStream_t st);

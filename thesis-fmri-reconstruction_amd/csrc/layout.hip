@@ -253,17 +253,6 @@ __global__ void nhwc_to_nchw_kernel(const half_t* __restrict__ src, float* __res
     }
 }
 
-// (half_t)(a * b) as the two roundings it is written as: the product rounded to fp32, then the cast.  Left as one
-// expression hipcc selects v_fma_mixlo_f16 (a * b + 0, also under -ffp-contract=off), which rounds the exact product to
-// fp16 ONCE and adds +0: a negative zero comes out as +0, and where the two roundings do not commute the bits differ from
-// the cast of the fp32 product that numpy and torch give (1.5 * 2^-24 at scale 1/3: 2^-24 instead of 0;
-// tests/test_glue_kernels_gpu.py::test_row_conversions).  The empty asm keeps the two operations apart.
-__device__ __forceinline__ half_t mul_then_f16(float a, float b) {
-    float p = a * b;
-    asm volatile("" : "+v"(p));
-    return (half_t)p;
-}
-
 // rows fp32 [M][C] -> fp16 [M][Cp] (zero padded), scaled
 __global__ void rows_f32_to_f16_kernel(const float* __restrict__ src, half_t* __restrict__ dst, int M, int C, int Cp,
                                        float scale) {

@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., SC 2011; the Random123 constants) and the counter layout of the engine's draws: what
-// rng.hip and the kernels that draw inside a launch of their own (nway.hip) share.
+// rng.hip and the kernels that draw inside a launch of their own (nway.hip, diffaug.hip, voxaug.hip) share.
 #pragma once
 #include "kernels.h"
 
@@ -33,6 +33,36 @@ __device__ __forceinline__ u32x4 rng_block(const int64_t* __restrict__ state, ui
     const uint64_t seed = (uint64_t)state[0];
     const uint64_t ctr = (uint64_t)state[1] + blk;
     return philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), sid, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// ---- the normal draw: what rng_normal_kernel and the kernels that draw normals inside a launch of their own share ----
+// u = (k + 0.5) * 2^-24 with k = w >> 8 is no fp32 number for k >= 2^23 (25 significant bits), and near u = 1 the half
+// step it would be rounded by moves sqrt(-2 ln u) by far more than an ulp.  1 - u = ((2^24 - 1 - k) + 0.5) * 2^-24 IS one
+// there, so the upper half of the interval goes through its complement: ln u = log1p(-(1 - u)), and the angle 2 pi u is
+// taken as -2 pi (1 - u) (cos is even, sin odd).  Both halves evaluate the same real-valued map.
+__device__ __forceinline__ float neg2_log_u(uint32_t w) {
+    const uint32_t k = w >> 8;
+    if (k < (1u << 23)) return -2.f * logf(((float)k + 0.5f) * 0x1p-24f);
+    return -2.f * log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f));
+}
+
+__device__ __forceinline__ void sincos_2pi_u(uint32_t w, float& s, float& c) {
+    const uint32_t k = w >> 8;
+    const float two_pi = 6.28318530717958647692f;
+    if (k < (1u << 23)) {
+        sincosf(two_pi * (((float)k + 0.5f) * 0x1p-24f), &s, &c);
+    } else {
+        sincosf(two_pi * (((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f), &s, &c);
+        s = -s;
+    }
+}
+
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float scale, float& z0, float& z1) {
+    const float r = scale * sqrtf(neg2_log_u(wa));
+    float s, c;
+    sincos_2pi_u(wb, s, c);
+    z0 = r * c;
+    z1 = r * s;
 }
 
 }  // namespace fmri

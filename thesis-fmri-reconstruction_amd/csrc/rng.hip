@@ -22,35 +22,6 @@ namespace fmri {
 
 namespace {
 
-// u = (k + 0.5) * 2^-24 with k = w >> 8 is no fp32 number for k >= 2^23 (25 significant bits), and near u = 1 the half
-// step it would be rounded by moves sqrt(-2 ln u) by far more than an ulp.  1 - u = ((2^24 - 1 - k) + 0.5) * 2^-24 IS one
-// there, so the upper half of the interval goes through its complement: ln u = log1p(-(1 - u)), and the angle 2 pi u is
-// taken as -2 pi (1 - u) (cos is even, sin odd).  Both halves evaluate the same real-valued map.
-__device__ __forceinline__ float neg2_log_u(uint32_t w) {
-    const uint32_t k = w >> 8;
-    if (k < (1u << 23)) return -2.f * logf(((float)k + 0.5f) * 0x1p-24f);
-    return -2.f * log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f));
-}
-
-__device__ __forceinline__ void sincos_2pi_u(uint32_t w, float& s, float& c) {
-    const uint32_t k = w >> 8;
-    const float two_pi = 6.28318530717958647692f;
-    if (k < (1u << 23)) {
-        sincosf(two_pi * (((float)k + 0.5f) * 0x1p-24f), &s, &c);
-    } else {
-        sincosf(two_pi * (((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f), &s, &c);
-        s = -s;
-    }
-}
-
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float scale, float& z0, float& z1) {
-    const float r = scale * sqrtf(neg2_log_u(wa));
-    float s, c;
-    sincos_2pi_u(wb, s, c);
-    z0 = r * c;
-    z1 = r * s;
-}
-
 // e0 = row0 * cols: first global element of the caller's rows; n = rows * cols (< 2^31); b0 = e0 / 4
 __global__ __launch_bounds__(256) void rng_normal_kernel(const int64_t* __restrict__ state, float* __restrict__ out,
                                                          uint64_t e0, uint32_t n, uint64_t b0, uint32_t nblk,

@@ -1,7 +1,7 @@
 """fmri_hip: the gfx950 engine.  The sub-modules are imported by name (``fmri_hip.steps``, ``fmri_hip.build`` ...); the
 public classes below are resolved on first use, so that ``import fmri_hip.build`` needs neither torch nor the library."""
 
-_LAZY = {"DiffAugment": "augment"}
+_LAZY = {"DiffAugment": "augment", "VoxelAugment": "voxaug"}
 
 
 def __getattr__(name):

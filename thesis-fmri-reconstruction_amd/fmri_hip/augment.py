@@ -17,10 +17,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
-from .rng import DeviceRng
+from .rng import SID_DAUG, SID_DAUG_P, DeviceRng
 
-SID_DAUG = 12          # rows of the [orig | pred] images
-SID_DAUG_P = 13        # rows of the sampled images
 POLICIES = {"color": 1, "translation": 2, "cutout": 4}
 NEUTRAL = (0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
 

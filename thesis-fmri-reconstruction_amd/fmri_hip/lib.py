@@ -112,6 +112,8 @@ _SIGS = {
     "fmri_diffaug_params": [_p, _p, _i, _l, _i, _i, _i, _i, _i, _p],
     "fmri_diffaug_fwd": [_p, _p, _i, _i, _i, _p, _i, _i, _p],
     "fmri_diffaug_bwd": [_p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p],
+    "fmri_voxaug_params": [_p, _p, _i, _l, _i, _i, _f, _f, _f, _i, _i, _f, _p],
+    "fmri_voxaug_apply": [_p, _i, _i, _p, _p, _l, _i, _i, _p, _p, _p],
     "fmri_schedule_seek_host": [_p, _l, _p],
     "fmri_epoch_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _p],
     "fmri_trainlog_append": [_p, _p, _i, _p, _l, _p, _p],

@@ -1613,6 +1613,38 @@ def diffaug_bwd(g_a: Optional[torch.Tensor], g_b: Optional[torch.Tensor], table:
     return tuple(next(it) if g is not None else None for g in (g_a, g_b))
 
 
+def voxaug_params(state: torch.Tensor, table: torch.Tensor, row0: int, sid_row: int, V: int, gain: float, sigma: float,
+                  p: float, rescale: bool, span_len: int, prob: float):
+    """Rows of an fMRI-augmentation table (fp32 [rows, 8]): global rows ``row0 ..`` of stream ``sid_row`` at the generator
+    state's offset (csrc/voxaug.hip; include/fmri_hip.h fmri_voxaug_params).  Does not move the offset."""
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise ValueError("voxaug_params: table must be a contiguous fp32 [rows, 8] tensor")
+    lib.call("fmri_voxaug_params", _P(state), _P(table), table.shape[0], int(row0), int(sid_row), int(V), float(gain),
+             float(sigma), float(p), int(bool(rescale)), int(span_len), float(prob))
+    return table
+
+
+def voxaug_apply(x32: torch.Tensor, table: torch.Tensor, state: torch.Tensor, row0: int, sid_noise: int, sid_drop: int,
+                 out16: Optional[torch.Tensor] = None, out32: Optional[torch.Tensor] = None):
+    """The augmented fp16 rows [B, pad8(V)] of ``x32`` (contiguous fp32 [B, V]) under ``table`` (fp32 [B, 8]), the element
+    draws at the generator state's offset for global rows ``row0 ..``; ``out32``: also the fp32 result [B, V]
+    (include/fmri_hip.h fmri_voxaug_apply).  Does not move the offset."""
+    require_gpu(x32)
+    if x32.dtype != torch.float32 or x32.dim() != 2 or not x32.is_contiguous():
+        raise ValueError("voxaug_apply: a contiguous fp32 [B, V] tensor is needed")
+    B, V = x32.shape
+    if out16 is None:
+        out16 = torch.empty(B, pad8(V), dtype=torch.float16, device=x32.device)
+    if out16.dtype != torch.float16 or tuple(out16.shape) != (B, pad8(V)) or not out16.is_contiguous():
+        raise ValueError(f"voxaug_apply: out16 must be a contiguous fp16 [{B}, {pad8(V)}] tensor")
+    if out32 is not None and (out32.dtype != torch.float32 or out32.shape != x32.shape or not out32.is_contiguous()):
+        raise ValueError(f"voxaug_apply: out32 must be a contiguous fp32 [{B}, {V}] tensor")
+    lib.note(bytes=x32.numel() * 4.0 + out16.numel() * 2.0 + (x32.numel() * 4.0 if out32 is not None else 0.0))
+    lib.call("fmri_voxaug_apply", _P(x32), V, B, _P(table), _P(state), int(row0), int(sid_noise), int(sid_drop),
+             _P(out16), _P(out32))
+    return out16
+
+
 def ingest_u8(images_u8: torch.Tensor, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), flip: Optional[torch.Tensor] = None,
               shift: Optional[torch.Tensor] = None, want16: bool = True, want32: bool = False):
     """uint8 [N,H,W,C] (C = 1 or 3, device) -> (fp16 NHWC8 engine input or None, fp32 NCHW or None): per-image

@@ -26,7 +26,12 @@ SID_FLIP = 8           # per-image horizontal flip
 SID_SHIFT = 9          # per-image (rows, cols) shift
 SID_DISTRACT = 10      # distractors of n-way identification (fmri_nway_scores)
 SID_GENERATE = 11      # decoder input of the evaluator's `random` grid (fmri_hip/evaluate.py generate=)
+SID_DAUG = 12          # DiffAugment rows of the [orig | pred] images (fmri_hip/augment.py)
+SID_DAUG_P = 13        # DiffAugment rows of the sampled images
+SID_VNOISE = 14        # VoxelAugment trial noise, one normal per (global row, voxel) (fmri_hip/voxaug.py)
+SID_VDROP = 15         # VoxelAugment voxel dropout, one raw word per (global row, voxel)
 SID_PERM = 16          # the epoch sampler's round function (fmri_sampler_indices; a counter layout of its own)
+SID_VROW = 17          # VoxelAugment row parameters, one Philox block per global row
 
 _I64 = (1 << 64) - 1
 

@@ -10,6 +10,7 @@ import torch
 
 from . import lib, ops
 from .augment import _check_table, blocks as aug_blocks
+from .voxaug import _check_table as _check_vox_table, blocks as vox_blocks
 from .monitor import Monitored
 from .nets import refresh_net
 from .rng import DeviceRng, StepNoise
@@ -256,6 +257,12 @@ class _StepBase(Monitored):
     _aug_req = None                              # (caller's table or None, B, H) of the forward pass being issued
     _aug_buf: Optional[torch.Tensor] = None      # the persistent table a step draws into
     _last_aug: Optional[torch.Tensor] = None
+    fmri_augment = None                          # fmri_hip.voxaug.VoxelAugment or None
+    _vox_req = None                              # (caller's table or None, fp32 fMRI rows) of the step being issued
+    _vox_tab: Optional[torch.Tensor] = None      # the persistent table a step draws into
+    _vox16: Optional[torch.Tensor] = None        # the persistent fp16 rows the encoder reads
+    _last_vox: Optional[torch.Tensor] = None
+    _last_fmri16: Optional[torch.Tensor] = None
     _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
@@ -323,6 +330,60 @@ class _StepBase(Monitored):
         if self.augment is None or (dimg_a is None and dimg_b is None):
             return dimg_a, dimg_b
         return self.augment.adjoint((dimg_a, dimg_b), self.fw["aug"], self.fw["B"], rows)
+
+    # ---- augmentation of the fMRI rows (fmri_hip/voxaug.py) -----------------------------------------------------------
+    def _init_fmri_augment(self, fmri_augment):
+        """``fmri_augment=`` of the step classes that have a cognitive encoder, after ``_init_rng``.  None: nothing is
+        added -- the step issues the launches it always did."""
+        if fmri_augment is not None and self.rng is None:
+            raise ValueError(f"{type(self).__name__}: fmri_augment= needs rng=DeviceRng(seed, device): noise and dropout "
+                             "are drawn per element by the step's generator, under a table the caller passes too")
+        self.fmri_augment = fmri_augment
+
+    def _vox_begin(self, fmri_aug, fmri: torch.Tensor):
+        """In front of ``_resolve_noise`` / ``_feed_advance``: what the step about to be issued wants for the rows its
+        encoder reads -- ``fmri`` (fp32 [B, V]) under the table ``fmri_aug``, or, left out, under a draw by the step's
+        generator at the offset of the noise draws."""
+        if self.fmri_augment is None:
+            if fmri_aug is not None:
+                raise ValueError(f"{type(self).__name__}: fmri_aug= given, but the step was constructed without "
+                                 "fmri_augment=VoxelAugment(...)")
+            return
+        self._vox_req = (fmri_aug, fmri)
+
+    def _vox_resolve(self) -> int:
+        """The two launches of the pending request -- the table (unless the caller passed it) into ``_last_vox``, the
+        augmented fp16 rows into ``_last_fmri16`` -- at the offset of the noise draws; returns the blocks of the generator
+        the step's ONE advance has to cover for them."""
+        req, self._vox_req = self._vox_req, None
+        if req is None:
+            return 0
+        table, fmri = req
+        fmri = fmri.contiguous().float()
+        B, V = fmri.shape
+        dd = self.dd
+        row0 = (dd.dist.get_rank() if dd.on else 0) * B
+        if table is None:
+            if self._vox_tab is None or self._vox_tab.shape[0] != B:
+                self._vox_tab = torch.empty(B, 8, dtype=torch.float32, device=self.device)
+            table = self.fmri_augment.table(self.rng, B, V, row0=row0, out=self._vox_tab)
+        else:
+            _check_vox_table(table, B)
+        if self._vox16 is None or self._vox16.shape[0] != B:
+            self._vox16 = torch.empty(B, ops.pad8(V), dtype=torch.float16, device=self.device)
+        self._last_vox = table
+        self._last_fmri16 = self.fmri_augment.apply(fmri, table, self.rng, row0=row0, out16=self._vox16)
+        return vox_blocks(B * dd.world, V)
+
+    def last_fmri_augment(self) -> Optional[torch.Tensor]:
+        """The fp32 [B, 8] table of the fMRI rows' augmentation the last step used (the step's own buffer where it drew
+        it: clone what has to outlive the next step); None for a step without ``fmri_augment=``."""
+        return self._last_vox
+
+    def last_fmri16(self) -> Optional[torch.Tensor]:
+        """The fp16 [B, pad8(V)] rows the cognitive encoder read in the last step (the step's own buffer); None for a step
+        without ``fmri_augment=``."""
+        return self._last_fmri16
 
     def _init_schedule(self, schedule: Optional[EpochSchedule], default_mask=None, hp=None, hp_dev=None):
         """``schedule=`` of the step classes (fmri_hip/schedule.py), after ``optims`` is complete.  ``default_mask``: which
@@ -473,6 +534,8 @@ class _StepBase(Monitored):
             sig.append(self.ema.signature())
         if self.augment is not None:
             sig.append(f"augment={self.augment!r}")
+        if self.fmri_augment is not None:
+            sig.append(f"fmri_augment={self.fmri_augment!r}")
         return sig
 
     def _host_state(self) -> dict:
@@ -614,8 +677,8 @@ class _StepBase(Monitored):
 
     def _feed_advance(self, at_least: int = 0):
         """The shared generator's advance for a step that drew no noise after its feed drew augmentation, or after it
-        drew its own augmentation table (``at_least`` blocks)."""
-        n = max(self._feed_blocks, int(at_least))
+        drew its own augmentation table (``at_least`` blocks) or augmented its fMRI rows (``_vox_begin``)."""
+        n = max(self._feed_blocks, int(at_least), self._vox_resolve())
         if n:
             self.rng.advance(n)
             self._feed_blocks = 0
@@ -625,13 +688,15 @@ class _StepBase(Monitored):
         the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
         [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
         draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
-        the same generator in this step, or of the augmentation table the step draws (``_aug_begin``), if that is larger.
+        the same generator in this step, or of the augmentation table the step draws (``_aug_begin``), or of the element
+        draws of its fMRI augmentation (``_vox_begin``), if that is larger.
         Returns the tensors in the order asked for."""
         missing = [name for name, _, t in wanted if t is None]
         if missing and self._noise is None:
             raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
                              "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
-        aug_drawn = self._aug_resolve()          # at the offset of the noise draws: nothing has advanced yet
+        # at the offset of the noise draws: nothing has advanced yet
+        aug_drawn = max(self._aug_resolve(), self._vox_resolve())
         Z = self.cfg.latent_dim
         dd = self.dd
         rank = dd.dist.get_rank() if dd.on else 0

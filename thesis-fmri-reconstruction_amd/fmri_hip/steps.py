@@ -630,8 +630,14 @@ class CognitiveStep(_GanStepBase):
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  gate_skip: bool = True, mode: str = "vae-gan", monitor: bool = False,
                  rng: Optional[DeviceRng] = None, feed=None, schedule=None, log=None, checkpoints=None, ema=None,
-                 augment=None):
-        """``augment``: a fmri_hip.augment.DiffAugment (see Stage1Step); in Stage II, mode 'vae-gan', the "real" image that
+                 augment=None, fmri_augment=None):
+        """``fmri_augment``: a fmri_hip.voxaug.VoxelAugment (needs ``rng``); the rows the cognitive encoder reads are then
+        the fMRI rows under trial noise, voxel dropout, a masked span and gain jitter -- two launches (the per-row table,
+        the transform) in place of the fp32 -> fp16 conversion, drawn at the offset of the noise draws, fresh at every
+        replay of a recorded step.  ``step(..., fmri_aug=table)`` pins the per-row parameters (fp32 [B, 8]);
+        ``last_fmri_augment()`` / ``last_fmri16()`` read the table and the rows.  A feed's ``fmri`` / ``fmri16``, the
+        teacher, the images and the evaluator keep the clean rows.  None: nothing is added.
+        ``augment``: a fmri_hip.augment.DiffAugment (see Stage1Step); in Stage II, mode 'vae-gan', the "real" image that
         shares its transform with x_tilde is the teacher's reconstruction.
         ``ema``: a fmri_hip.ema.WeightEma (see Stage1Step): by default the cognitive encoder in Stage II, the decoder in
         Stage III -- a frozen network has no average.
@@ -667,6 +673,7 @@ class CognitiveStep(_GanStepBase):
             raise ValueError("CognitiveStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
         self._init_rng(rng, feed)
         self._init_augment(augment)
+        self._init_fmri_augment(fmri_augment)
         self.mode = mode
         hp = self.hp
         self.opt_enc = _Optim(self.cog.group, "rmsprop", hp.lr, hp.alpha, hp.eps)
@@ -722,13 +729,16 @@ class CognitiveStep(_GanStepBase):
 
     def forward(self, fmri: torch.Tensor, image: torch.Tensor, eps: Optional[torch.Tensor] = None,
                 z_p: Optional[torch.Tensor] = None, eps_teacher: Optional[torch.Tensor] = None,
-                fmri16: Optional[torch.Tensor] = None, aug: Optional[torch.Tensor] = None):
+                fmri16: Optional[torch.Tensor] = None, aug: Optional[torch.Tensor] = None,
+                fmri_aug: Optional[torch.Tensor] = None):
         """``fmri16``: the fp16 [B, pad8(V)] rows of ``fmri`` where the caller already has them (a feed's gather pass
-        writes both); otherwise they are made here."""
+        writes both); otherwise they are made here.  With ``fmri_augment=`` the encoder reads the augmented rows instead
+        (``fmri_aug``: their fp32 [B, 8] table; left out, the ``rng`` draws it)."""
         require_gpu(fmri)
         cfg = self.cfg
         B, _, H, W = image.shape
         self._aug_begin(aug, B, H)
+        self._vox_begin(fmri_aug, fmri)
         wanted = [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)]
         if self.teacher_enc is not None:
             wanted.append(("eps_teacher", SID_EPS_TEACHER, eps_teacher))
@@ -741,7 +751,9 @@ class CognitiveStep(_GanStepBase):
         if self.mon is not None:
             self.mon.zero()
         disc_in = torch.empty(3 * B, H, W, 8, dtype=torch.float16, device=dev)
-        if fmri16 is None:
+        if self.fmri_augment is not None:
+            fmri16 = self._last_fmri16           # (made by _resolve_noise, in front of the generator's advance)
+        elif fmri16 is None:
             fmri16 = rows_to_f16(fmri)
         head32, cctx = self.cog.forward(fmri16)
         eps = eps.contiguous().float()
@@ -857,12 +869,12 @@ class CognitiveStep(_GanStepBase):
             self.opt_dec.step(self.flags[1:2], clamp=1.0, gdev=self._slot(S_GDEC))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))
 
-    def step(self, fmri=None, image=None, eps=None, z_p=None, eps_teacher=None, aug=None):
+    def step(self, fmri=None, image=None, eps=None, z_p=None, eps_teacher=None, aug=None, fmri_aug=None):
         fed = self._fed(fmri, image)
         fmri16 = None
         if fed is not None:
             image, fmri, fmri16 = fed
-        fw = self.forward(fmri, image, eps, z_p, eps_teacher, fmri16=fmri16, aug=aug)
+        fw = self.forward(fmri, image, eps, z_p, eps_teacher, fmri16=fmri16, aug=aug, fmri_aug=fmri_aug)
         self.gate(fw["B"] * self.dd.world)
         self.backward(fuse=True)
         self.apply()

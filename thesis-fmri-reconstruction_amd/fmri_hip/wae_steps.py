@@ -105,8 +105,10 @@ class WaeStep(_LatentDiscPhase, _StepBase):
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, checkpoints=None, ema=None):
-        """``ema``: a fmri_hip.ema.WeightEma (see steps.Stage1Step) over the networks this stage trains.
+                 schedule=None, log=None, checkpoints=None, ema=None, fmri_augment=None):
+        """``fmri_augment``: a fmri_hip.voxaug.VoxelAugment in front of the cognitive encoder (Stages II / III, needs
+        ``rng``; see steps.CognitiveStep); ``step(..., fmri_aug=table)`` pins the per-row parameters.
+        ``ema``: a fmri_hip.ema.WeightEma (see steps.Stage1Step) over the networks this stage trains.
         ``checkpoints``: a fmri_hip.state.StateRing (see steps.Stage1Step); Adam's moments and step counts are state.
         ``monitor``: record the step's numerics on the device (``numerics()``, fmri_hip/monitor.py).
         ``schedule``: a fmri_hip.schedule.EpochSchedule (needs ``feed``) -- the scripts' three ``StepLR(step_size, gamma)``
@@ -120,6 +122,8 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         assert stage in (1, 2, 3)
         if penalty not in ("gan", "mmd"):
             raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
+        if fmri_augment is not None and stage == 1:
+            raise ValueError("WaeStep: fmri_augment= needs stage 2 or 3 (Stage I reads no fMRI rows)")
         self.penalty = penalty
         self.cfg, self.stage, self.n_voxels = cfg, stage, n_voxels
         self.sc = Scales() if scales is None else scales
@@ -140,6 +144,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         if feed is not None and stage > 1 and (feed.fmri is None or feed.fmri.shape[1] != n_voxels):
             raise ValueError("WaeStep: feed needs a dataset with fp32 fMRI rows of n_voxels columns")
         self._init_rng(rng, feed)
+        self._init_fmri_augment(fmri_augment)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.wd)], 1)
         self._init_schedule(schedule)
@@ -174,11 +179,13 @@ class WaeStep(_LatentDiscPhase, _StepBase):
 
     # ---- the step --------------------------------------------------------------------------------------------
     def step(self, image: Optional[torch.Tensor] = None, z_fake_noise: Optional[torch.Tensor] = None,
-             fmri: Optional[torch.Tensor] = None):
+             fmri: Optional[torch.Tensor] = None, fmri_aug: Optional[torch.Tensor] = None):
         """(``capture()`` records it whole: Adam's step count and the learning rates live on the device, and the ~300
         launches of a few microseconds each are bound by the host when issued eagerly.)
         Stage I: step(x, z_fake_noise) with z_fake = 0.5 * noise (train_wae_stage1.py:276); step(x) draws the noise
-        with the step's ``rng``.  Stage II/III: step(image, fmri=fmri).  With a ``feed``: step() / step(None, noise)."""
+        with the step's ``rng``.  Stage II/III: step(image, fmri=fmri).  With a ``feed``: step() / step(None, noise).
+        ``fmri_aug`` (steps with ``fmri_augment=``): the fp32 [B, 8] table of this step's fMRI augmentation; left out,
+        the ``rng`` draws it."""
         st = self.stage
         fed = self._fed(image) if st == 1 else self._fed(image, fmri)
         fmri16 = None
@@ -190,7 +197,10 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         if st == 1:
             z_fake_noise, = self._resolve_noise(B, [("z_fake_noise", SID_ZFAKE, z_fake_noise)])
         else:
-            self._feed_advance()
+            self._vox_begin(fmri_aug, fmri)
+            self._feed_advance()                 # (covers the element draws of the fMRI augmentation)
+            if self.fmri_augment is not None:
+                fmri16 = self._last_fmri16
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         Bg = B * self.dd.world

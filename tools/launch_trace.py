@@ -189,6 +189,13 @@ def main():
         for mode in ("vae-gan", "vae"):
             run(f"cognitive stage{stage} {mode}", lambda: CognitiveStep(cfg, V2, DEV, stage, mode=mode),
                 eager(fm, xc, nzc[0], nzc[1], nzc[2]))
+    # fmri_augment=: the table and the apply launch in place of the fp32 -> fp16 conversion of the rows (new rows: the
+    # rows above are the steps built without the keyword)
+    from fmri_hip.rng import DeviceRng
+    from fmri_hip.voxaug import VoxelAugment
+    run("cognitive stage2 vae-gan fmri_augment",
+        lambda: CognitiveStep(cfg, V2, DEV, 2, rng=DeviceRng(5, DEV), fmri_augment=VoxelAugment()),
+        eager(fm, xc, nzc[0], nzc[1], nzc[2]))
     xw, fw_, _ = batch(VW)
     for pen in ("gan", "mmd"):
         run(f"wae stage1 {pen}", lambda: WaeStep(cfg, DEV, 1, penalty=pen), eager(x, nz[2]))
