@@ -125,6 +125,110 @@ def test_bad_geometry_is_refused_on_the_host():
     assert lib.fmri_rng_advance(z, -1, None) == -1
 
 
+class _RecordingRng:
+    """Stands in for a DeviceRng on the host: records the draws and advances a StepDraws issues, in order."""
+    device = "cpu"
+
+    def __init__(self):
+        self.calls = []
+
+    def normal(self, rows, cols, sid, row0=0, scale=1.0, out=None):
+        self.calls.append(("normal", rows, cols, sid, row0, out.data_ptr()))
+        return out
+
+    def advance(self, nblocks):
+        self.calls.append(("advance", nblocks))
+
+
+def test_step_draws_given_tensors_pass_through():
+    """What the caller passed comes back as the same objects, in order; nothing is drawn, nothing advanced -- with a
+    generator and without one."""
+    import torch
+    from fmri_hip.rng import StepDraws
+    a, b = torch.zeros(4, 8), torch.ones(4, 8)
+    for g in (None, _RecordingRng()):
+        d = StepDraws(g, "SomeStep")
+        with d:
+            got = list(d.noise(4, 8, 0, 1, ("eps", 0, a), ("z_p", 1, b)))
+        assert got[0] is a and got[1] is b
+        assert list(d.last.items()) == [("eps", a), ("z_p", b)] and d.last["eps"] is a
+        d.close()
+        assert d.noted == 0 and (g is None or g.calls == [])
+
+
+def test_step_draws_missing_noise_without_a_generator_names_every_argument():
+    import torch
+    from fmri_hip.rng import StepDraws
+    d = StepDraws(None, "SomeStep")
+    with pytest.raises(ValueError) as e:
+        d.noise(4, 8, 0, 1, ("eps", 0, None), ("z_p", 1, torch.zeros(4, 8)), ("z_fake_noise", 3, None))
+    assert str(e.value) == ("SomeStep: eps, z_fake_noise not given and the step has no rng "
+                            "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
+
+
+@pytest.mark.parametrize("largest", ["feed", "table", "voxel", "noise"])
+def test_step_draws_one_advance_by_the_largest_behind_the_last_draw(largest):
+    """A round with all four consumers -- a shared feed's blocks, an augmentation table's, the fMRI rows' and two drawn
+    noise tensors (B = 4 rows of a global batch of 8, Z = 8: blocks(8 * 8) = 16) -- with each of them the largest in
+    turn: exactly one advance, by the maximum, after the last draw; the next round starts from zero."""
+    import torch
+    from fmri_hip.rng import StepDraws, blocks
+    B, Z, rank, world = 4, 8, 1, 2
+    noise = blocks(B * world * Z)
+    assert noise == 16
+    n = {"feed": 3, "table": 5, "voxel": 7, "noise": noise}
+    if largest != "noise":
+        n[largest] = 40
+    g = _RecordingRng()
+    d = StepDraws(g, "SomeStep")
+    given = torch.zeros(B, Z)
+    d.note(n["feed"])
+    with d:
+        d.note(n["table"])
+        d.note(n["voxel"])
+        eps, z_p, z_t = d.noise(B, Z, rank, world, ("eps", 0, None), ("z_p", 1, given), ("eps_teacher", 2, None))
+        assert g.calls == [("normal", B, Z, 0, rank * B, eps.data_ptr()), ("normal", B, Z, 2, rank * B, z_t.data_ptr())]
+    assert z_p is given and eps.shape == z_t.shape == (B, Z) and eps.dtype == torch.float32
+    assert eps.data_ptr() != z_t.data_ptr()
+    assert g.calls[2:] == [("advance", max(n.values()))] and d.noted == 0
+    assert list(d.last) == ["eps", "z_p", "eps_teacher"]             # argument order, given and drawn alike
+    # a second round starts from zero: the smallest draw alone is advanced by itself, into the same buffers
+    del g.calls[:]
+    with d:
+        d.note(2)
+    assert g.calls == [("advance", 2)]
+    del g.calls[:]
+    with d:
+        eps2, = d.noise(B, Z, rank, world, ("eps", 0, None))
+    assert eps2 is eps and g.calls == [("normal", B, Z, 0, rank * B, eps.data_ptr()), ("advance", noise)]
+    assert list(d.last) == ["eps"]
+
+
+def test_step_draws_close_with_nothing_noted_issues_nothing():
+    from fmri_hip.rng import StepDraws
+    g = _RecordingRng()
+    d = StepDraws(g, "SomeStep")
+    d.close()
+    with d:
+        d.note(0)
+    StepDraws(None, "SomeStep").close()
+    assert g.calls == []
+
+
+def test_step_draws_a_failed_round_leaves_nothing_pending():
+    """A step that raises between its draws and the end of the round advances nothing, then or in the next round."""
+    from fmri_hip.rng import StepDraws
+    g = _RecordingRng()
+    d = StepDraws(g, "SomeStep")
+    with pytest.raises(RuntimeError):
+        with d:
+            d.note(9)
+            raise RuntimeError("a bad table")
+    assert d.noted == 0
+    d.close()
+    assert g.calls == []
+
+
 def test_step_constructors_take_an_rng_and_noise_is_optional():
     """The four fused steps gain ``rng=None`` and their noise arguments default to None (signatures only: no GPU)."""
     import inspect

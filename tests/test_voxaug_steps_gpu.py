@@ -178,6 +178,47 @@ def test_offset_and_reproducibility(deterministic, kind):
     assert c.rng.offset() == B * V // 4
 
 
+def test_every_consumer_of_the_generator_in_one_step(deterministic, golden_dir):
+    """Stage II with all four things a step draws from its generator at once -- a feed that flips and shifts on it,
+    ``augment=``, ``fmri_augment=`` and drawn noise (V of the ``stage2_b4`` golden): after one ``step()`` the offset has
+    moved once, by the largest of the four draws, and every draw is bit for bit the lone draw a second generator with
+    the same seed makes at the offset the step started from."""
+    import os
+    from fmri_hip import augment, rng as R, voxaug
+    from fmri_hip.augment import DiffAugment
+    from fmri_hip.feed import DeviceDataset, DeviceFeed
+    from fmri_hip.steps import CognitiveStep
+    _, _, cfg = _cfgs()
+    Vg, Z, start = int(np.load(os.path.join(golden_dir, "stage2_b4.npz"))["meta/V"]), cfg.latent_dim, 1000
+    rs = np.random.RandomState(7)
+    pool = torch.from_numpy(rs.randint(0, 256, (16, H, H, 3), dtype=np.uint8)).to(DEV)
+    fmri = torch.from_numpy(rs.standard_normal((16, Vg)).astype(np.float32)).to(DEV)
+    g, lone = R.DeviceRng(SEED, DEV), R.DeviceRng(SEED, DEV)
+    g.seed(SEED, start)
+    lone.seed(SEED, start)
+    feed = DeviceFeed(DeviceDataset(pool, fmri), B, 77, rng=g, flip=True, max_shift=2)
+    da, va = DiffAugment(), _va()
+    st = CognitiveStep(cfg, Vg, DEV, 2, rng=g, feed=feed, augment=da, fmri_augment=va)
+    st.load_recipe(3, True)
+    st.step()
+    _finish()
+    moved = [R.blocks(B * Z), R.blocks(2 * B), augment.blocks(B), voxaug.blocks(B, Vg)]
+    print("blocks: noise, feed, augment, voxaug =", moved)
+    assert g.offset() == start + max(moved)
+    assert lone.offset() == start
+    noise = st.last_noise()
+    assert list(noise) == ["eps", "z_p", "eps_teacher"]
+    for name, sid in (("eps", R.SID_EPS), ("z_p", R.SID_ZP), ("eps_teacher", R.SID_EPS_TEACHER)):
+        assert torch.equal(noise[name], lone.normal(B, Z, sid)), name
+    assert torch.equal(st.last_augment(), da.table(lone, B, H))
+    table = va.table(lone, B, Vg)
+    assert torch.equal(st.last_fmri_augment(), table)
+    assert torch.equal(feed.flip, lone.flips(B)) and torch.equal(feed.shift, lone.shifts(B, 2))
+    # (and the rows the encoder read are the feed's clean rows under that table and the generator's element draws)
+    assert torch.equal(feed.fmri, fmri[feed.last_indices().long()])
+    assert torch.equal(st.last_fmri16().view(torch.int16), va.apply(feed.fmri, table, lone).view(torch.int16))
+
+
 def _fed(seed=SEED):
     from fmri_hip.feed import DeviceDataset, DeviceFeed
     from fmri_hip.rng import DeviceRng

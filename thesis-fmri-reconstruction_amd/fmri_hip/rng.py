@@ -114,28 +114,61 @@ class DeviceRng:
         return self.integers(2 * n, -int(max_shift), int(max_shift), SID_SHIFT, out=out, start=2 * start).view(n, 2)
 
 
-class StepNoise:
-    """The noise buffers a fused step fills for itself: persistent fp32 [B, Z] tensors (so that a recorded step writes
-    and reads the same memory at every replay), drawn at global rows rank * B .. and followed by ONE advance per step
-    by the block count of the largest draw at the global batch."""
+class StepDraws:
+    """The ledger of what a fused step draws from its generator, and the only place a step advances it.  The rule:
+    draws never move the offset, so everything a step draws -- a shared feed's flips and shifts, the augmentation tables,
+    the fMRI rows' element draws, the latent noise -- is drawn at ONE offset under different stream ids; every draw is
+    noted here with the Philox blocks it consumes at the global batch, and ``close`` issues ONE advance, behind the last
+    draw, by the largest.  A recorded step then draws fresh numbers at every replay and a restored one the same again.
 
-    def __init__(self, rng: DeviceRng):
-        self.rng = rng
-        self.bufs = {}
-        self.last = {}
+        with step.draws:                       # leaving it closes the round; an exception drops it unadvanced
+            ...draw with step.rng...; step.draws.note(blocks)
+            eps, z_p = step.draws.noise(B, Z, rank, world, ("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p))
 
-    def begin(self):
-        self.last = {}
+    ``rng`` None (a step that is handed everything): nothing can be noted and ``close`` does nothing."""
 
-    def draw(self, name: str, sid: int, B: int, Z: int, rank: int) -> torch.Tensor:
-        buf = self.bufs.get(name)
-        if buf is None or buf.shape != (B, Z):
-            buf = self.bufs[name] = torch.empty(B, Z, dtype=torch.float32, device=self.rng.device)
-        self.rng.normal(B, Z, sid, row0=rank * B, out=buf)
-        self.last[name] = buf
-        return buf
+    def __init__(self, rng: Optional[DeviceRng], owner: str = "step"):
+        self.rng, self.owner = rng, owner
+        self.bufs = {}           # argument name -> persistent fp32 [B, Z]: a recorded step rewrites the same memory
+        self.last = {}           # argument name -> the tensor the last round used, in argument order (last_noise())
+        self.noted = 0           # blocks of the largest draw of the round in progress
 
-    def end(self, B_global: int, Z: int, at_least: int = 0):
-        """``at_least``: blocks of other draws made at the same offset (the augmentation draws of a feed that shares
-        the generator): the one advance covers the largest."""
-        self.rng.advance(max(blocks(B_global * Z), int(at_least)))
+    def note(self, nblocks: int):
+        """A draw of ``nblocks`` Philox blocks was made at the current offset."""
+        if nblocks > self.noted:
+            self.noted = int(nblocks)
+
+    def noise(self, B: int, Z: int, rank: int, world: int, *wanted):
+        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
+        the caller passed is used as it is; a missing one is drawn into the persistent [B, Z] buffer of its name at
+        global rows rank * B .. and noted as a [B * world, Z] draw.  Returns the tensors in the order asked for."""
+        last = self.last = {}
+        for name, sid, t in wanted:
+            if t is None:
+                if self.rng is None:
+                    missing = ", ".join(n for n, _, g in wanted if g is None)
+                    raise ValueError(f"{self.owner}: {missing} not given and the step has no rng "
+                                     "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
+                t = self.bufs.get(name)
+                if t is None or t.shape != (B, Z):
+                    t = self.bufs[name] = torch.empty(B, Z, dtype=torch.float32, device=self.rng.device)
+                self.rng.normal(B, Z, sid, row0=rank * B, out=t)
+                self.note(blocks(B * world * Z))
+            last[name] = t
+        return last.values()
+
+    def close(self):
+        """The round's one advance, by the largest draw noted; nothing where nothing was."""
+        n, self.noted = self.noted, 0
+        if n:
+            self.rng.advance(n)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.noted = 0       # a step that failed half-way leaves nothing for the next one to advance by
+        return False

@@ -1,5 +1,5 @@
 """What every fused step is built on (steps.py, wae_steps.py): the fused optimizers, the data-parallel glue with its
-graph-segment recorder, and ``_StepBase`` -- scalar block, device RNG and feed, noise resolution, the unit-RMS
+graph-segment recorder, and ``_StepBase`` -- scalar block, device RNG and feed, the ledger of a step's draws, the unit-RMS
 re-normalisation of the encoder cotangent, HIP-graph capture and replay.  Nothing here knows a loss."""
 from __future__ import annotations
 
@@ -13,7 +13,7 @@ from .augment import _check_table, blocks as aug_blocks
 from .voxaug import _check_table as _check_vox_table, blocks as vox_blocks
 from .monitor import Monitored
 from .nets import refresh_net
-from .rng import DeviceRng, StepNoise
+from .rng import DeviceRng, StepDraws
 from .schedule import EpochSchedule, TrainLog, lr_columns
 from .state import StateRing, TrainState, _Segment
 
@@ -166,6 +166,7 @@ class _Dist:
         force = os.environ.get("FMRI_FORCE_DIST") == "1"
         self.on = enabled and dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or force)
         self.world = dist.get_world_size() if self.on else 1
+        self.rank = dist.get_rank() if self.on else 0
         self.sync_bn = sync_bn
         self.pending = []
         # A communicator of its own for the SMALL collectives of the main stream (loss scalars, the stream-norm scalar,
@@ -245,24 +246,19 @@ def _attach_reducers(nets, d: _Dist):
 
 
 class _StepBase(Monitored):
-    """What every step uses; a subclass sets ``cfg``, builds its networks, calls ``_init_step`` and ``_init_rng``,
-    registers its optimizers in ``optims``, calls ``_init_schedule`` / ``_init_log`` and defines ``step`` (which starts
-    with ``_fed`` and ends with ``_log_append``)."""
+    """What every step uses; a subclass sets ``cfg``, builds its networks, calls ``_init_step`` and ``_init_rng``
+    (``_init_augment`` / ``_init_fmri_augment`` where it has the keyword), registers its optimizers in ``optims``, ends its
+    constructor with ``_init_extras`` and defines ``step`` (which starts with ``_fed`` and ends with ``_log_append``).
+
+    Whatever a step draws from its generator goes through ``self.draws`` (rng.StepDraws): the draw is issued where the
+    step wants it and noted with its block count -- ``_fed`` does so for a feed on the step's generator, ``_aug_table``
+    and ``_fmri_rows`` for the augmentations, ``_noise`` for the latent noise -- inside ONE ``with self.draws:`` per step,
+    whose end is the generator's one advance.  Nothing else in the step classes advances the generator."""
 
     schedule: Optional[EpochSchedule] = None
     log: Optional[TrainLog] = None
     checkpoints: Optional[StateRing] = None
     ema = None                                   # fmri_hip.ema.WeightEma or None
-    augment = None                               # fmri_hip.augment.DiffAugment or None
-    _aug_req = None                              # (caller's table or None, B, H) of the forward pass being issued
-    _aug_buf: Optional[torch.Tensor] = None      # the persistent table a step draws into
-    _last_aug: Optional[torch.Tensor] = None
-    fmri_augment = None                          # fmri_hip.voxaug.VoxelAugment or None
-    _vox_req = None                              # (caller's table or None, fp32 fMRI rows) of the step being issued
-    _vox_tab: Optional[torch.Tensor] = None      # the persistent table a step draws into
-    _vox16: Optional[torch.Tensor] = None        # the persistent fp16 rows the encoder reads
-    _last_vox: Optional[torch.Tensor] = None
-    _last_fmri16: Optional[torch.Tensor] = None
     _epoch_dev: Optional[torch.Tensor] = None
 
     def _init_step(self, device, nets, distributed: bool, sync_bn: bool):
@@ -277,47 +273,49 @@ class _StepBase(Monitored):
 
     def _init_rng(self, rng: Optional[DeviceRng], feed=None):
         self.rng = rng
-        self._noise = StepNoise(rng) if rng is not None else None
-        self._last_noise: Dict[str, torch.Tensor] = {}
+        self.draws = StepDraws(rng, type(self).__name__)
         self.feed = feed             # fmri_hip.feed.DeviceFeed or None
-        self._feed_blocks = 0        # blocks of the shared generator the feed's draws of this step consumed
+
+    def _noise(self, B: int, *wanted):
+        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step, each
+        fp32 [B, latent_dim]: as passed, or drawn by the step's generator (StepDraws.noise)."""
+        return self.draws.noise(B, self.cfg.latent_dim, self.dd.rank, self.dd.world, *wanted)
+
+    def last_noise(self) -> Dict[str, torch.Tensor]:
+        """The noise tensors the last step used, by argument name in the order ``step`` takes them (the step's own
+        buffers where it drew them: clone what has to outlive the next step)."""
+        return dict(self.draws.last)
 
     # ---- differentiable augmentation of the discriminator's inputs (fmri_hip/augment.py) ------------------------------
+    augment = None                               # fmri_hip.augment.DiffAugment or None
+    _aug_buf: Optional[torch.Tensor] = None      # the persistent table a step draws into
+    _last_aug: Optional[torch.Tensor] = None
+
     def _init_augment(self, augment):
         """``augment=`` of the step classes that have an image discriminator.  None: nothing is added -- the step issues
         the launches it always did."""
         self.augment = augment
 
-    def _aug_begin(self, aug, B: int, H: int):
-        """In front of ``_resolve_noise``: what the forward pass about to be issued wants for its table -- ``aug`` as it
-        is, or, left out, a draw by the step's generator at the offset of the noise draws."""
+    def _aug_table(self, aug, B: int, H: int):
+        """The table of the forward pass about to be issued: ``aug`` as it is, or, left out, a draw by the step's
+        generator into the step's own buffer, noted in ``draws``; None for a step without ``augment=``."""
         if self.augment is None:
             if aug is not None:
                 raise ValueError(f"{type(self).__name__}: aug= given, but the step was constructed without "
                                  "augment=DiffAugment(...)")
-            return
-        self._aug_req = (aug, B, H)
-
-    def _aug_resolve(self) -> int:
-        """The table of the pending request into ``_last_aug``; returns the blocks of the generator the step's ONE advance
-        has to cover for it (0 for a table the caller passed)."""
-        req, self._aug_req = self._aug_req, None
-        if req is None:
-            return 0
-        aug, B, H = req
+            return None
         if aug is not None:
             _check_table(aug, B)
-            self._last_aug = aug
-            return 0
-        if self.rng is None:
+        elif self.rng is None:
             raise ValueError(f"{type(self).__name__}: aug not given and the step has no rng (pass the table, or "
                              "construct the step with rng=DeviceRng(seed, device))")
-        dd = self.dd
-        rank = dd.dist.get_rank() if dd.on else 0
-        if self._aug_buf is None or self._aug_buf.shape[0] != 2 * B:
-            self._aug_buf = torch.empty(2 * B, 8, dtype=torch.float32, device=self.device)
-        self._last_aug = self.augment.table(self.rng, B, H, row0=rank * B, out=self._aug_buf)
-        return aug_blocks(B * dd.world)
+        else:
+            if self._aug_buf is None or self._aug_buf.shape[0] != 2 * B:
+                self._aug_buf = torch.empty(2 * B, 8, dtype=torch.float32, device=self.device)
+            aug = self.augment.table(self.rng, B, H, row0=self.dd.rank * B, out=self._aug_buf)
+            self.draws.note(aug_blocks(B * self.dd.world))
+        self._last_aug = aug
+        return aug
 
     def last_augment(self) -> Optional[torch.Tensor]:
         """The fp32 [2B, 8] augmentation table the last step used (the step's own buffer where it drew it: clone what
@@ -332,6 +330,12 @@ class _StepBase(Monitored):
         return self.augment.adjoint((dimg_a, dimg_b), self.fw["aug"], self.fw["B"], rows)
 
     # ---- augmentation of the fMRI rows (fmri_hip/voxaug.py) -----------------------------------------------------------
+    fmri_augment = None                          # fmri_hip.voxaug.VoxelAugment or None
+    _vox_tab: Optional[torch.Tensor] = None      # the persistent table a step draws into
+    _vox16: Optional[torch.Tensor] = None        # the persistent fp16 rows the encoder reads
+    _last_vox: Optional[torch.Tensor] = None
+    _last_fmri16: Optional[torch.Tensor] = None
+
     def _init_fmri_augment(self, fmri_augment):
         """``fmri_augment=`` of the step classes that have a cognitive encoder, after ``_init_rng``.  None: nothing is
         added -- the step issues the launches it always did."""
@@ -340,29 +344,19 @@ class _StepBase(Monitored):
                              "are drawn per element by the step's generator, under a table the caller passes too")
         self.fmri_augment = fmri_augment
 
-    def _vox_begin(self, fmri_aug, fmri: torch.Tensor):
-        """In front of ``_resolve_noise`` / ``_feed_advance``: what the step about to be issued wants for the rows its
-        encoder reads -- ``fmri`` (fp32 [B, V]) under the table ``fmri_aug``, or, left out, under a draw by the step's
-        generator at the offset of the noise draws."""
+    def _fmri_rows(self, fmri_aug, fmri: torch.Tensor):
+        """The rows the encoder of the step about to be issued reads: ``fmri`` (fp32 [B, V]) under the table ``fmri_aug``
+        or, left out, under a draw by the step's generator -- the table's launch (unless passed) and the transform's, noted
+        in ``draws``.  Returns (table, fp16 [B, pad8(V)] rows), the step's own buffers; (None, None) for a step without
+        ``fmri_augment=``."""
         if self.fmri_augment is None:
             if fmri_aug is not None:
                 raise ValueError(f"{type(self).__name__}: fmri_aug= given, but the step was constructed without "
                                  "fmri_augment=VoxelAugment(...)")
-            return
-        self._vox_req = (fmri_aug, fmri)
-
-    def _vox_resolve(self) -> int:
-        """The two launches of the pending request -- the table (unless the caller passed it) into ``_last_vox``, the
-        augmented fp16 rows into ``_last_fmri16`` -- at the offset of the noise draws; returns the blocks of the generator
-        the step's ONE advance has to cover for them."""
-        req, self._vox_req = self._vox_req, None
-        if req is None:
-            return 0
-        table, fmri = req
-        fmri = fmri.contiguous().float()
+            return None, None
+        table, fmri = fmri_aug, fmri.contiguous().float()
         B, V = fmri.shape
-        dd = self.dd
-        row0 = (dd.dist.get_rank() if dd.on else 0) * B
+        row0 = self.dd.rank * B
         if table is None:
             if self._vox_tab is None or self._vox_tab.shape[0] != B:
                 self._vox_tab = torch.empty(B, 8, dtype=torch.float32, device=self.device)
@@ -373,7 +367,8 @@ class _StepBase(Monitored):
             self._vox16 = torch.empty(B, ops.pad8(V), dtype=torch.float16, device=self.device)
         self._last_vox = table
         self._last_fmri16 = self.fmri_augment.apply(fmri, table, self.rng, row0=row0, out16=self._vox16)
-        return vox_blocks(B * dd.world, V)
+        self.draws.note(vox_blocks(B * self.dd.world, V))
+        return table, self._last_fmri16
 
     def last_fmri_augment(self) -> Optional[torch.Tensor]:
         """The fp32 [B, 8] table of the fMRI rows' augmentation the last step used (the step's own buffer where it drew
@@ -577,6 +572,14 @@ class _StepBase(Monitored):
                     self.log.counter if self.log is not None else None,
                     self._host_state if self.ema is None else self._host_meta)
 
+    def _init_extras(self, schedule, log, checkpoints=None, ema=None, lr_mask=None, hp=None, hp_dev=None):
+        """The tail of every constructor -- ``schedule=`` / ``log=`` / ``ema=`` / ``checkpoints=``, in the order they depend
+        on each other -- once ``optims`` is complete; ``lr_mask`` / ``hp`` / ``hp_dev``: see ``_init_schedule``."""
+        self._init_schedule(schedule, lr_mask, hp, hp_dev)
+        self._init_log(log)
+        self._init_ema(ema)
+        self._init_checkpoints(checkpoints)
+
     def _state_ready(self, between_steps: bool = False):
         """In front of a snapshot launch: the optimizer updates of the eager two-stream mode run on the side stream, so the
         step must have joined; the engine-order BatchNorm statistics must be the loaded ones (a host check; they are after
@@ -655,9 +658,9 @@ class _StepBase(Monitored):
         """The batch of a step.  Without a feed: ``given`` (the caller's batch tensors) must all be there; returns None.
         With a feed: none may be; the feed enqueues its next batch (fmri_hip/feed.py) -- the first launches of the step,
         so they sit in the one graph of a recording, or in the first segment of a data-parallel one -- and its buffers
-        (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that draws its augmentation from the step's own
-        generator leaves the advance to the step: ``_resolve_noise`` / ``_feed_advance`` make ONE advance that covers
-        the noise and the augmentation draws.  A schedule / log puts ONE launch in front of the feed's (``_epoch_begin``)."""
+        (x fp32 NCHW, fmri fp32 [B,V] or None, the same rows as zero-padded fp16 or None) are returned.  A feed that
+        draws its augmentation from the step's own generator leaves the advance to the step: its blocks are noted in
+        ``draws``, whose one advance at the end of the step's round covers them.  A schedule / log puts ONE launch in front of the feed's (``_epoch_begin``)."""
         if self.ema is not None:
             self.ema.prime()                     # host check: weights loaded from outside since the last step
         feed = self.feed
@@ -672,51 +675,9 @@ class _StepBase(Monitored):
         shared = feed.rng is not None and feed.rng is self.rng
         self._epoch_begin()
         x, fm, _ = feed.next(advance_rng=not shared)
-        self._feed_blocks = feed.rng_blocks() if shared else 0
+        if shared:
+            self.draws.note(feed.rng_blocks())
         return x, fm, feed.fmri16
-
-    def _feed_advance(self, at_least: int = 0):
-        """The shared generator's advance for a step that drew no noise after its feed drew augmentation, or after it
-        drew its own augmentation table (``at_least`` blocks) or augmented its fMRI rows (``_vox_begin``)."""
-        n = max(self._feed_blocks, int(at_least), self._vox_resolve())
-        if n:
-            self.rng.advance(n)
-            self._feed_blocks = 0
-
-    def _resolve_noise(self, B: int, wanted):
-        """``wanted``: (argument name, stream id, the caller's tensor or None) of every noise input of the step.  A tensor
-        the caller passed is used as it is; a missing one is drawn by the step's DeviceRng into a persistent fp32 buffer
-        [B, latent_dim] at global rows rank * B .. (fmri_hip/rng.py), and the generator is advanced ONCE, behind the
-        draws, by the block count of a [global batch, latent_dim] draw -- or of the augmentation draws a feed made from
-        the same generator in this step, or of the augmentation table the step draws (``_aug_begin``), or of the element
-        draws of its fMRI augmentation (``_vox_begin``), if that is larger.
-        Returns the tensors in the order asked for."""
-        missing = [name for name, _, t in wanted if t is None]
-        if missing and self._noise is None:
-            raise ValueError(f"{type(self).__name__}: {', '.join(missing)} not given and the step has no rng "
-                             "(pass the noise, or construct the step with rng=DeviceRng(seed, device))")
-        # at the offset of the noise draws: nothing has advanced yet
-        aug_drawn = max(self._aug_resolve(), self._vox_resolve())
-        Z = self.cfg.latent_dim
-        dd = self.dd
-        rank = dd.dist.get_rank() if dd.on else 0
-        if missing:
-            self._noise.begin()
-        out = {}
-        for name, sid, t in wanted:
-            out[name] = self._noise.draw(name, sid, B, Z, rank) if t is None else t
-        if missing:
-            self._noise.end(B * dd.world, Z, at_least=max(self._feed_blocks, aug_drawn))
-            self._feed_blocks = 0
-        else:
-            self._feed_advance(aug_drawn)
-        self._last_noise = out
-        return list(out.values())
-
-    def last_noise(self) -> Dict[str, torch.Tensor]:
-        """The noise tensors the last step used, by argument name in the order ``step`` takes them (the step's own
-        buffers where it drew them: clone what has to outlive the next step)."""
-        return dict(self._last_noise)
 
     def _reduce_async(self, group, part=None):
         """Data parallel: the sub-network's deferred weight gradients -> reference layout (one launch), then the

@@ -120,13 +120,12 @@ class _GanStepBase(_StepBase):
                 setattr(hp, name, float(v))
         self.hp_dev.copy_(torch.tensor([hp.lambda_mse, hp.equilibrium, hp.margin, hp.beta], dtype=torch.float32))
 
-    def _discriminate(self, disc_in, B):
+    def _discriminate(self, disc_in, B, table):
         """The discriminator's forward pass on the 3B images ``[orig | pred | sampled]`` -- with ``augment=`` on their
-        transforms under the table of this pass (``disc_in`` itself stays what it is for the pixel term and the
+        transforms under ``table`` (``_aug_table``; ``disc_in`` itself stays what it is for the pixel term and the
         views).  Returns (feat, logit32, ctx, what ``fw`` notes about the augmentation)."""
         if self.augment is None:
             return (*self.dis.forward(disc_in), {})
-        table = self._last_aug
         disc_aug = self.augment.forward(disc_in, table, B)
         return (*self.dis.forward(disc_aug), dict(disc_aug=disc_aug, aug=table))
 
@@ -211,12 +210,9 @@ class _GanStepBase(_StepBase):
         return cols + [("train_dis", self.flags, 0), ("train_dec", self.flags, 1)], LOG_KEYS
 
     def _init_extras(self, schedule, log, checkpoints=None, ema=None):
-        """``schedule=`` / ``log=`` / ``ema=`` / ``checkpoints=`` once ``optims`` is complete.  lr: encoder, decoder,
-        discriminator, as ``set_hyper``."""
-        self._init_schedule(schedule, [i < 3 for i in range(len(self.optims))], self.hp, self.hp_dev)
-        self._init_log(log)
-        self._init_ema(ema)
-        self._init_checkpoints(checkpoints)
+        """lr: encoder, decoder, discriminator, as ``set_hyper``."""
+        super()._init_extras(schedule, log, checkpoints, ema, [i < 3 for i in range(len(self.optims))], self.hp,
+                             self.hp_dev)
 
     def _state_tensors(self):
         out = super()._state_tensors()
@@ -239,6 +235,43 @@ class _GanStepBase(_StepBase):
         out = {k: v[i] for i, k in enumerate(LOG_KEYS)}
         f = self.flags.tolist()
         out["train_dis"], out["train_dec"] = bool(f[0]), bool(f[1])
+        return out
+
+    def _monitor_tail(self):
+        if self.mon is not None:
+            self.mon.tail(self.fw["head32"], self.cfg.latent_dim, self._monitor_losses(), self.zs)
+
+    def _monitor_losses(self):
+        return [self.scal[:len(LOG_KEYS)]]
+
+    # ---- reference-shaped views of the last forward (API / parity tests) -----------------------------
+    outputs_gt_x = False         # whether ``outputs()`` has the ground-truth image (the steps that are not handed it as x)
+
+    def outputs(self):
+        fw, cfg = self.fw, self.cfg
+        B, Z = fw["B"], cfg.latent_dim
+        d = fw["disc_in"]
+        feat = fw["feat"]
+        n3, h, w, c = feat.shape
+        out = dict(gt_x=nhwc_to_images(d[:B], 3)) if self.outputs_gt_x else {}
+        out.update(
+            x_tilde=nhwc_to_images(d[B:2 * B], 3), x_p=nhwc_to_images(d[2 * B:], 3),
+            disc_class=fw["prob"].reshape(3 * B, 1).clone(),
+            disc_layer=nhwc_to_images(feat, c).reshape(n3, -1),
+            mus=fw["head32"][:, :Z].clone(), log_variances=fw["head32"][:, Z:].clone())
+        return out
+
+    def named_grads(self):
+        """True-scale gradients (the device normalisation factors divided out) of the sub-networks the step trains --
+        syncs; tests/API only.  After ``backward()``; ``step()`` does not leave any (FlatGroup.check_grads_readable)."""
+        s = self.scal.tolist()
+        out = {}
+        for pre, n, slot in self._subnets():
+            if slot is None:
+                continue
+            n.group.check_grads_readable()
+            for k, v in n.group.grads.items():
+                out[pre + k] = v / s[slot]
         return out
 
 
@@ -338,10 +371,17 @@ class Stage1Step(_GanStepBase):
     def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, z_p: Optional[torch.Tensor] = None,
                 aug: Optional[torch.Tensor] = None):
         require_gpu(x)
+        B, _, H, W = x.shape
+        with self.draws:
+            table = self._aug_table(aug, B, H)
+            eps, z_p = self._noise(B, ("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p))
+        return self._forward(x, eps, z_p, table)
+
+    def _forward(self, x, eps, z_p, table):
+        """The launches of ``forward`` behind the draws: on noise that is there and the augmentation table of
+        ``_aug_table`` (DualStage1Step.step draws a third noise input in the same round and enters here)."""
         cfg = self.cfg
         B, _, H, W = x.shape
-        self._aug_begin(aug, B, H)
-        eps, z_p = self._resolve_noise(B, [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)])
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = x.device
         self.scal.zero_()
@@ -360,7 +400,7 @@ class Stage1Step(_GanStepBase):
         if G == 3:
             lib.call("fmri_latent_fwd", _P(head32), None, B, Z, zp, _P(z16[2 * B:]), None, None, 0)
         _, dctx = self.dec.forward(z16, G, out=dec_out[B:], zscale=self.zs)
-        feat, logit32, sctx, seen = self._discriminate(disc_in, B)
+        feat, logit32, sctx, seen = self._discriminate(disc_in, B, table)
         prob, F = self._gan_losses(feat, logit32, B, disc_in[:B], disc_in[B:2 * B], H, W)
         self.fw = dict(B=B, H=H, W=W, F=F, disc_in=disc_in, head32=head32, eps=eps, ectx=ectx, dctx=dctx, sctx=sctx,
                        feat=feat, logit32=logit32, prob=prob, **seen)
@@ -511,13 +551,6 @@ class Stage1Step(_GanStepBase):
         opt.step(flag, gdev=self._slot(slot))
         refresh_net(net)
 
-    def _monitor_tail(self):
-        if self.mon is not None:
-            self.mon.tail(self.fw["head32"], self.cfg.latent_dim, self._monitor_losses(), self.zs)
-
-    def _monitor_losses(self):
-        return [self.scal[:len(LOG_KEYS)]]
-
     def apply(self):
         self._monitor_tail()
         if self.mode != "dcgan":                         # 'dcgan': train_enc = False (train_vgan_stage1.py:376)
@@ -594,30 +627,6 @@ class Stage1Step(_GanStepBase):
         self._log_append()
         return self.scal
 
-    # ---- reference-shaped views of the last forward (API / parity tests) -----------------------------
-    def outputs(self):
-        fw, cfg = self.fw, self.cfg
-        B, Z = fw["B"], cfg.latent_dim
-        d = fw["disc_in"]
-        feat = fw["feat"]
-        n3, h, w, c = feat.shape
-        return dict(
-            x_tilde=nhwc_to_images(d[B:2 * B], 3), x_p=nhwc_to_images(d[2 * B:], 3),
-            disc_class=fw["prob"].reshape(3 * B, 1).clone(),
-            disc_layer=nhwc_to_images(feat, c).reshape(n3, -1),
-            mus=fw["head32"][:, :Z].clone(), log_variances=fw["head32"][:, Z:].clone())
-
-    def named_grads(self):
-        """True-scale gradients (the device normalisation factors divided out) -- syncs; tests/API only.  After
-        ``backward()``; ``step()`` does not leave any (FlatGroup.check_grads_readable)."""
-        s = self.scal.tolist()
-        out = {}
-        for pre, n, slot in self._subnets():
-            n.group.check_grads_readable()
-            for k, v in n.group.grads.items():
-                out[pre + k] = v / s[slot]
-        return out
-
 
 class CognitiveStep(_GanStepBase):
     """Stage-II / Stage-III steps of the Dual-VAE/GAN (fMRI -> image), `VaeGanCognitive` wiring
@@ -684,6 +693,8 @@ class CognitiveStep(_GanStepBase):
                                      ("discriminator", self.opt_dis, self.dis)], 1)
         self._init_extras(schedule, log, checkpoints, ema)
 
+    outputs_gt_x = True
+
     def _trained(self):
         return ["encoder", "discriminator"] if self.stage == 2 else ["decoder", "discriminator"]
 
@@ -737,22 +748,22 @@ class CognitiveStep(_GanStepBase):
         require_gpu(fmri)
         cfg = self.cfg
         B, _, H, W = image.shape
-        self._aug_begin(aug, B, H)
-        self._vox_begin(fmri_aug, fmri)
-        wanted = [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p)]
-        if self.teacher_enc is not None:
-            wanted.append(("eps_teacher", SID_EPS_TEACHER, eps_teacher))
-        eps, z_p, *rest = self._resolve_noise(B, wanted)
-        if rest:
-            eps_teacher = rest[0]
+        with self.draws:
+            table = self._aug_table(aug, B, H)
+            _, rows16 = self._fmri_rows(fmri_aug, fmri)
+            if self.teacher_enc is not None:
+                eps, z_p, eps_teacher = self._noise(B, ("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
+                                                    ("eps_teacher", SID_EPS_TEACHER, eps_teacher))
+            else:
+                eps, z_p = self._noise(B, ("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p))
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         self.scal.zero_()
         if self.mon is not None:
             self.mon.zero()
         disc_in = torch.empty(3 * B, H, W, 8, dtype=torch.float16, device=dev)
-        if self.fmri_augment is not None:
-            fmri16 = self._last_fmri16           # (made by _resolve_noise, in front of the generator's advance)
+        if rows16 is not None:
+            fmri16 = rows16
         elif fmri16 is None:
             fmri16 = rows_to_f16(fmri)
         head32, cctx = self.cog.forward(fmri16)
@@ -775,7 +786,7 @@ class CognitiveStep(_GanStepBase):
             lib.call("fmri_rows_f32_to_f16", _P(z_p.contiguous().float()), _P(z16[B:]), B, Z, zp, 1.0)
             _, dctx = self.dec.forward(z16, 2, out=disc_in[B:], zscale=self.zs)
             g_tilde, g_p = 0, 1
-        feat, logit32, sctx, seen = self._discriminate(disc_in, B)
+        feat, logit32, sctx, seen = self._discriminate(disc_in, B, table)
         prob, F = self._gan_losses(feat, logit32, B, disc_in[:B], disc_in[B:2 * B], H, W)
         self.fw = dict(B=B, H=H, W=W, F=F, disc_in=disc_in, head32=head32, eps=eps, cctx=cctx, dctx=dctx, sctx=sctx,
                        feat=feat, logit32=logit32, prob=prob, g_tilde=g_tilde, g_p=g_p, **seen)
@@ -859,8 +870,7 @@ class CognitiveStep(_GanStepBase):
         self.dd.wait_all()
 
     def apply(self):
-        if self.mon is not None:
-            self.mon.tail(self.fw["head32"], self.cfg.latent_dim, [self.scal[:len(LOG_KEYS)]], self.zs)
+        self._monitor_tail()
         if self.stage == 2:
             self.opt_enc.step(None, clamp=1.0, gdev=self._slot(S_NE))
             self.opt_dis.step(self.flags[0:1], clamp=1.0, gdev=self._slot(S_NA))
@@ -880,25 +890,3 @@ class CognitiveStep(_GanStepBase):
         self.apply()
         self._log_append()
         return self.scal
-
-    def outputs(self):
-        fw, cfg = self.fw, self.cfg
-        B, Z = fw["B"], cfg.latent_dim
-        d = fw["disc_in"]
-        feat = fw["feat"]
-        n3, h, w, c = feat.shape
-        return dict(gt_x=nhwc_to_images(d[:B], 3), x_tilde=nhwc_to_images(d[B:2 * B], 3),
-                    x_p=nhwc_to_images(d[2 * B:], 3), disc_class=fw["prob"].reshape(3 * B, 1).clone(),
-                    disc_layer=nhwc_to_images(feat, c).reshape(n3, -1),
-                    mus=fw["head32"][:, :Z].clone(), log_variances=fw["head32"][:, Z:].clone())
-
-    def named_grads(self):
-        s = self.scal.tolist()
-        out = {}
-        for pre, n, slot in self._subnets():
-            if slot is None:
-                continue
-            n.group.check_grads_readable()
-            for k, v in n.group.grads.items():
-                out[pre + k] = v / s[slot]
-        return out

@@ -147,10 +147,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         self._init_fmri_augment(fmri_augment)
         self._init_monitor(monitor, [("encoder", self.opt_enc, self.enc), ("decoder", self.opt_dec, self.dec),
                                      ("discriminator", self.opt_dis, self.wd)], 1)
-        self._init_schedule(schedule)
-        self._init_log(log)
-        self._init_ema(ema)
-        self._init_checkpoints(checkpoints)
+        self._init_extras(schedule, log, checkpoints, ema)
 
     def _trained(self):
         """Stage II freezes the decoder, Stage III the cognitive encoder; the latent discriminator trains under the GAN
@@ -194,13 +191,13 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         require_gpu(image)
         cfg, hp, sc = self.cfg, self.hp, self.sc
         B, _, H, W = image.shape
-        if st == 1:
-            z_fake_noise, = self._resolve_noise(B, [("z_fake_noise", SID_ZFAKE, z_fake_noise)])
-        else:
-            self._vox_begin(fmri_aug, fmri)
-            self._feed_advance()                 # (covers the element draws of the fMRI augmentation)
-            if self.fmri_augment is not None:
-                fmri16 = self._last_fmri16
+        with self.draws:                         # (Stages II / III draw no noise: the round is the feed's and the rows')
+            if st == 1:
+                z_fake_noise, = self._noise(B, ("z_fake_noise", SID_ZFAKE, z_fake_noise))
+            else:
+                _, rows16 = self._fmri_rows(fmri_aug, fmri)
+                if rows16 is not None:
+                    fmri16 = rows16
         Z, zp = cfg.latent_dim, pad8(cfg.latent_dim)
         dev = image.device
         Bg = B * self.dd.world
@@ -298,8 +295,7 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         both sides, every rank evaluates the same global statistic (only rank 0 adds it to the slot, which the loss
         all-reduce then sums) and keeps the gradient rows of its own samples."""
         B, Z = head32.shape[0], self.cfg.latent_dim
-        dd = self.dd
-        rank = dd.dist.get_rank() if dd.on else 0
+        dd, rank = self.dd, self.dd.rank
         if dd.on:
             buf = torch.zeros(2, B * dd.world, Z, dtype=torch.float32, device=head32.device)
             buf[0, rank * B:(rank + 1) * B] = head32[:, :Z]
@@ -407,12 +403,12 @@ class DualStage1Step(Stage1Step, _LatentDiscPhase):
         fed = self._fed(x)
         if fed is not None:
             x = fed[0]
-        self._aug_begin(aug, x.shape[0], x.shape[2])     # drawn with the noise: the one advance covers it
-        eps, z_p, z_fake_noise = self._resolve_noise(x.shape[0], [("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
-                                                                  ("z_fake_noise", SID_ZFAKE, z_fake_noise)])
-        noise = self._last_noise
-        fw = self.forward(x, eps, z_p, self._last_aug if self.augment is not None else None)
-        self._last_noise = noise             # (forward records its two)
+        require_gpu(x)
+        with self.draws:
+            table = self._aug_table(aug, x.shape[0], x.shape[2])
+            eps, z_p, z_fake_noise = self._noise(x.shape[0], ("eps", SID_EPS, eps), ("z_p", SID_ZP, z_p),
+                                                 ("z_fake_noise", SID_ZFAKE, z_fake_noise))
+        fw = self._forward(x, eps, z_p, table)
         self.gate(fw["B"] * self.dd.world)
         B, Z = fw["B"], self.cfg.latent_dim
         zp = pad8(Z)

@@ -6,7 +6,10 @@ Wraps ``fmri_hip.lib.call`` and records per launch the entry point, every argume
 a float (pointers only as null / non-null: addresses differ between runs) and the stream (0, 1, ... in order of first
 appearance).  Under FMRI_DETERMINISTIC=1, with recipe weights and the oracle's synthetic batch (B = 4, 64 px, the voxel
 counts of the ``*_b4`` goldens) it runs every step class and launch mode and prints per configuration the number of
-launches, a SHA-256 of the trace and a SHA-256 of the state the steps left (scalar blocks, parameters, optimizer state).
+launches, a SHA-256 of the trace and a SHA-256 of the state the steps left (scalar blocks, parameters, optimizer state,
+the device state of the step's generator, of its feed and of a generator the feed has to itself).  The ``draws`` rows
+are the steps that draw from a generator -- noise, a feed's flips and shifts, the augmentation tables, the fMRI rows --
+eager and, where a recording is what training runs, as ``capture()`` + two replays.
 It also runs recon_level 1 and 2, an eval-mode forward and the drop-in module API (one Stage-I loop body, lone
 Encoder / Decoder blocks), hashing their outputs and parameter gradients in place of a state.
 Nothing is asserted about the hardware."""
@@ -72,6 +75,13 @@ def state_tensors(st):
         o = getattr(st, n, None)
         if o is not None:
             tensors += [t for t in (o.s1, o.s2, o.lr_dev, o.t_dev) if t is not None]
+    rng, feed = getattr(st, "rng", None), getattr(st, "feed", None)
+    if rng is not None:
+        tensors.append(rng._state)           # a wrong advance shows here even where the step's numbers agree
+    if feed is not None:
+        tensors.append(feed._state)
+        if feed.rng is not None and feed.rng is not rng:
+            tensors.append(feed.rng._state)
     return tensors
 
 
@@ -101,6 +111,61 @@ def run(name, make, drive):
     print(f"{name:34s} launches {n:5d}  trace {th[:24]}  {what} {tensors_hash(hashed)[:24]}", flush=True)
 
 
+def draws(cfg, x, nz, xc, fm, nzc, V2, xw, fmw, VW):
+    """The steps that draw from a generator: everything that goes through the step's one advance per step."""
+    from fmri_hip.augment import DiffAugment
+    from fmri_hip.feed import DeviceDataset, DeviceFeed
+    from fmri_hip.rng import DeviceRng
+    from fmri_hip.voxaug import VoxelAugment
+    rs = np.random.RandomState(7)
+    pool = torch.from_numpy(rs.randint(0, 256, (16, 64, 64, 3), dtype=np.uint8)).to(DEV)
+    rows = {V: torch.from_numpy(rs.standard_normal((16, V)).astype(np.float32)).to(DEV) for V in (V2, VW)}
+    handed = DiffAugment().table(DeviceRng(9, DEV), B, 64)
+
+    def rng():
+        return DeviceRng(5, DEV)
+
+    def fed(cls, *a, V=0, shared=True, **kw):
+        """A step on a feed that flips and shifts on the step's generator, or on one of its own."""
+        g = rng()
+        ds = DeviceDataset(pool, rows[V] if V else None)
+        return cls(cfg, *a, rng=g, feed=DeviceFeed(ds, B, 77, rng=g if shared else DeviceRng(6, DEV), flip=True,
+                                                   max_shift=2), **kw)
+
+    def both(name, make, *a):
+        run(f"draws {name}", make, steps(*a))
+        run(f"draws {name} capture", make, recorded(*a))
+
+    both("stage1 rng", lambda: Stage1Step(cfg, DEV, rng=rng()), x)
+    both("stage1 rng augment", lambda: Stage1Step(cfg, DEV, rng=rng(), augment=DiffAugment()), x)
+    both("stage1 fed", lambda: fed(Stage1Step, DEV))
+    run("draws stage1 fed own rng", lambda: fed(Stage1Step, DEV, shared=False), steps())
+    both("cognitive stage2 fed all", lambda: fed(CognitiveStep, V2, DEV, 2, V=V2, augment=DiffAugment(),
+                                                 fmri_augment=VoxelAugment()))
+    run("draws cognitive stage3 handed aug", lambda: CognitiveStep(cfg, V2, DEV, 3, augment=DiffAugment()),
+        steps(fm, xc, nzc[0], nzc[1], aug=handed))
+    run("draws wae stage1 rng", lambda: WaeStep(cfg, DEV, 1, rng=rng()), steps(x))
+    run("draws wae stage2 rng fmri_augment",
+        lambda: WaeStep(cfg, DEV, 2, VW, rng=rng(), fmri_augment=VoxelAugment()), steps(xw, fmri=fmw))
+    run("draws wae stage2 fed", lambda: fed(WaeStep, DEV, 2, VW, V=VW), steps())
+    both("dual1 rng augment", lambda: DualStage1Step(cfg, DEV, rng=rng(), augment=DiffAugment()), x)
+
+
+def steps(*a, **k):
+    def drive(st):
+        for _ in range(2):
+            st.step(*a, **k)
+    return drive
+
+
+def recorded(*a):
+    def drive(st):
+        replay = st.capture(*a)          # the trace holds the warm-up steps and the recording
+        replay()
+        replay()
+    return drive
+
+
 def main():
     cfg_o, cfg = O.ArchCfg.px64(), ArchConfig.px64()
     V2, VW = golden_v("stage2_b4.npz"), golden_v("wae2_b4.npz")
@@ -112,18 +177,7 @@ def main():
 
     x, _, nz = batch()
 
-    def eager(*a, **k):
-        def drive(st):
-            for _ in range(2):
-                st.step(*a, **k)
-        return drive
-
-    def recorded(*a):
-        def drive(st):
-            replay = st.capture(*a)          # the trace holds the warm-up steps and the recording
-            replay()
-            replay()
-        return drive
+    eager = steps
 
     def hybrid(st):
         step = st.capture_forward(x, nz[0], nz[1])
@@ -197,6 +251,7 @@ def main():
         lambda: CognitiveStep(cfg, V2, DEV, 2, rng=DeviceRng(5, DEV), fmri_augment=VoxelAugment()),
         eager(fm, xc, nzc[0], nzc[1], nzc[2]))
     xw, fw_, _ = batch(VW)
+    draws(cfg, x, nz, xc, fm, nzc, V2, xw, fw_, VW)
     for pen in ("gan", "mmd"):
         run(f"wae stage1 {pen}", lambda: WaeStep(cfg, DEV, 1, penalty=pen), eager(x, nz[2]))
         for stage in (2, 3):
