@@ -223,14 +223,23 @@ def _q(t: Tensor, tag: str = None) -> Tensor:
 # RELU_MASKS (tests only): a list of 0/1 tensors consumed in call order by every ReLU below -- the masks of another
 # run of the same network (the HIP engine's stored activations > 0).  With the masks pinned the gradients are a smooth
 # function of the activations, so two implementations can be compared at rounding level instead of at the level of
-# "which pre-activations within fp16 rounding of zero fell on which side".
+# "which pre-activations within fp16 rounding of zero fell on which side".  A ``None`` entry means "this ReLU uses its
+# own mask": for passes the other run has no counterpart of, or whose output feeds no gradient (the Dual step's
+# decoder(z_real2) under no_grad, which only moves running statistics).
 RELU_MASKS = None
+# RELU_RECORD (tests only): when it is a list and no masks are pinned, every ReLU below appends its own (x > 0) mask to
+# it -- the call order of a step function's ReLUs, and the masks that replay it bit for bit (tests/test_relu_masks_host.py).
+RELU_RECORD = None
 
 
 def _relu(x: Tensor) -> Tensor:
     if RELU_MASKS is None:
+        if RELU_RECORD is not None:
+            RELU_RECORD.append((x.detach() > 0).to(x.dtype))
         return F.relu(x)
     m = RELU_MASKS.pop(0)
+    if m is None:
+        return F.relu(x)
     assert m.shape == x.shape, (tuple(m.shape), tuple(x.shape))
     return x * m
 

@@ -82,12 +82,16 @@ def test_literal_reference_loop_body_runs_on_engine():
         model.discriminator.parameters())
     x = data["x"].to(dev)
     eps, z_p = data["noise"][0, 0].to(dev), data["noise"][0, 1].to(dev).requires_grad_(True)
+    import gradcheck
+    rec = gradcheck.Recorder(None, enc=model.encoder._engine(), dec=model.decoder._engine(),
+                             dis=model.discriminator._engine())
     # forward with explicit noise (sub-modules in the order of VaeGan.forward)
     mus, lv = model.encoder(x)
     x_tilde = model.decoder(eps * torch.exp(0.5 * lv) + mus)
     x_p = model.decoder(z_p)
     disc_layer = model.discriminator(x, x_tilde, x_p, "REC")
     disc_class = model.discriminator(x, x_tilde, x_p, "GAN")
+    masks = gradcheck.literal_masks(rec, B)
     nle, kld, mse, bo, bp, bs = vg.VaeGan.loss(x, x_tilde, disc_layer[:B], disc_layer[B:-B], disc_layer[-B:],
                                                disc_class[:B], disc_class[B:-B], disc_class[-B:], mus, lv)
     lam = 1e-6
@@ -120,14 +124,13 @@ def test_literal_reference_loop_body_runs_on_engine():
     def rel(a, b):
         a, b = a.float().cpu().reshape(-1), b.float().reshape(-1)
         return ((a - b).norm() / (b.norm() + 1e-30)).item()
-    import gradcheck
     got_g = {pre + k: v for pre, gd in (("encoder.", g_enc), ("decoder.", g_dec), ("discriminator.", g_dis))
              for k, v in gd.items()}
     P16 = O.fill_state(O.vaegan_spec(cfg), 0, True)
     o16 = {n: O.OptState(kind="rmsprop", lr=lr) for n in ("encoder", "decoder", "discriminator")}
-    with gradcheck.storage16(O):
+    with gradcheck.pinned(O, masks):
         ref16 = O.stage1_step(P16, o16, data["x"], data["noise"][0, 0], data["noise"][0, 1], cfg, keep_grads=True)
-    gradcheck.check(got_g, ref["grads"], ref16["grads"], "api stage1", tol16=None)
+    gradcheck.check(got_g, ref["grads"], ref16["grads"], "api stage1")
     # parameters after the three optimizer steps and BN bookkeeping
     sd = model.state_dict()
     for k, v in P.items():
@@ -209,6 +212,8 @@ def test_literal_stage2_loop_body_runs_on_engine():
     fmri, image = data["fmri"].to(dev), data["x"].to(dev)
     nz = data["noise"][0]
     eps, z_p, eps_t = nz[0].to(dev), nz[1].to(dev).requires_grad_(True), nz[2].to(dev)
+    rec = gradcheck.Recorder(None, cog=model.encoder._engine(), dec=model.decoder._engine(),
+                             dis=model.discriminator._engine(), teacher_enc=model.teacher_net.encoder._engine())
     mus, lv = model.encoder(fmri)
     x_tilde = model.decoder(eps * torch.exp(0.5 * lv) + mus)
     for param in model.teacher_net.encoder.parameters():
@@ -218,6 +223,7 @@ def test_literal_stage2_loop_body_runs_on_engine():
     x_p = model.decoder(z_p)
     disc_layer = model.discriminator(gt_x, x_tilde, x_p, "REC")
     disc_class = model.discriminator(gt_x, x_tilde, x_p, "GAN")
+    masks = gradcheck.literal_masks(rec, B)
     nle, kld, mse, bo, bp, bs = vg.VaeGanCognitive.loss(gt_x, x_tilde, disc_layer[:B], disc_layer[B:-B], disc_layer[-B:],
                                                         disc_class[:B], disc_class[B:-B], disc_class[-B:], mus, lv)
     loss_encoder = torch.sum(kld) + torch.sum(mse)
@@ -248,7 +254,16 @@ def test_literal_stage2_loop_body_runs_on_engine():
     # gradients BEFORE the clamp are what the oracle returns; the clamp only touches elements beyond +-1
     grads = {**g_enc, **g_dis}
     refg = {k: v.clamp(-1, 1) for k, v in ref["grads"].items() if v is not None}
-    gradcheck.check(grads, refg, refg, "api stage2", tol16=None)
+    # second reference: the oracle under its 16-bit storage model with the engine's ReLU masks pinned (tests/gradcheck.py)
+    t16 = O.fill_state(O.vaegan_spec(cfg), seed, True)
+    P16 = dict(O.fill_state(O.cognitive_encoder_spec(cfg, V), seed + 100, True))
+    P16.update({k: v for k, v in t16.items() if k.startswith(("decoder.", "discriminator."))})
+    for k, v in t16.items():
+        P16["teacher_net." + k] = P16[k] if k.startswith(("decoder.", "discriminator.")) else v
+    with gradcheck.pinned(O, masks):
+        ref16 = O.stage2_step(P16, {n: O.OptState(kind="rmsprop", lr=lr) for n in opts}, data["fmri"], data["x"], nz,
+                              cfg, V, keep_grads=True)
+    gradcheck.check(grads, refg, {k: ref16["grads"][k].clamp(-1, 1) for k in refg}, "api stage2")
     # the two optimizer steps moved the same parameters the same way: RMSprop's first update is +-3.16 lr per element
     # (sign-like), so compare the UPDATE vectors -- a few % of the signs differ under fp16 noise at B = 4
     sd = model.state_dict()

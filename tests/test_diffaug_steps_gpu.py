@@ -112,7 +112,6 @@ def _stage1_case(table):
     """One Stage-I step of the engine (``table`` None: built without the keyword) and of the oracle as it stands -- fp32,
     and under its 16-bit storage model with the engine's ReLU masks pinned -> (engine logs, engine gradients, fp32 run,
     16-bit run)."""
-    import test_stage1_gpu as S1
     from fmri_hip.augment import DiffAugment
     O, cfg_o, _ = _cfgs()
     d = _data()
@@ -123,7 +122,7 @@ def _stage1_case(table):
         st = _make("vae-gan", augment=DiffAugment())
         st.forward(d["xd"], d["nd"][0, 0], d["nd"][0, 1], aug=torch.tensor(table, dtype=torch.float32, device=DEV))
         assert not torch.equal(st.fw["disc_aug"], st.fw["disc_in"])
-    masks = S1._engine_relu_masks(st)
+    masks = gradcheck._engine_relu_masks(st)
     st.gate(B)
     st.backward()
     grads = {k: v.detach().cpu().clone() for k, v in st.named_grads().items()}
@@ -132,14 +131,9 @@ def _stage1_case(table):
     new_opts = lambda: {n: O.OptState(kind="rmsprop", lr=1e-4) for n in ("encoder", "decoder", "discriminator")}
     ref = O.stage1_step(O.fill_state(O.vaegan_spec(cfg_o), 3, True), new_opts(), d["x"], d["noise"][0, 0],
                         d["noise"][0, 1], cfg_o, keep_grads=True)
-    with gradcheck.storage16(O):
-        O.RELU_MASKS = list(masks)
-        try:
-            ref16 = O.stage1_step(O.fill_state(O.vaegan_spec(cfg_o), 3, True), new_opts(), d["x"], d["noise"][0, 0],
-                                  d["noise"][0, 1], cfg_o, keep_grads=True)
-        finally:
-            left, O.RELU_MASKS = len(O.RELU_MASKS), None
-    assert left == 0, left
+    with gradcheck.pinned(O, masks):
+        ref16 = O.stage1_step(O.fill_state(O.vaegan_spec(cfg_o), 3, True), new_opts(), d["x"], d["noise"][0, 0],
+                              d["noise"][0, 1], cfg_o, keep_grads=True)
     return logs, grads, ref, ref16
 
 
@@ -176,8 +170,10 @@ def test_stage3_step_with_augmentation_matches_the_oracle(deterministic, monkeyp
     d = _data()
     table = _drawn_table(22)
     st = _make("stage3", augment=DiffAugment())
+    rec = gradcheck.Recorder(st)
     nz = d["nd"][0]
     st.forward(d["fd"], d["xd"], nz[0], nz[1], nz[2], aug=torch.tensor(table, dtype=torch.float32, device=DEV))
+    masks = gradcheck.cognitive_masks(rec, B, False)       # (the discriminator's are those of the transformed images)
     st.gate(B)
     st.backward()
     grads = {k: v.cpu() for k, v in st.named_grads().items()}
@@ -190,12 +186,12 @@ def test_stage3_step_with_augmentation_matches_the_oracle(deterministic, monkeyp
     for k in LOSS_KEYS:
         print("stage3+aug", k, logs[k], ref["logs"][k], _rel(logs[k], ref["logs"][k]))
     P16, _ = S23._oracle_state(O, cfg_o, V, 3, True, 3)
-    with gradcheck.storage16(O):
+    with gradcheck.pinned(O, masks):
         ref16 = O.stage3_step(P16, new_opts(), d["fmri"], d["x"], d["noise"][0], cfg_o, V, keep_grads=True)
     assert logs["train_dis"] == ref["logs"]["train_dis"] and logs["train_dec"] == ref["logs"]["train_dec"]
     for k in LOSS_KEYS:
         assert _rel(logs[k], ref["logs"][k]) < LOSS_RTOL, (k, logs[k], ref["logs"][k])
-    gradcheck.check(grads, ref["grads"], ref16["grads"], "stage3 + diffaug", tol16=None)
+    gradcheck.check(grads, ref["grads"], ref16["grads"], "stage3 + diffaug")
 
 
 def _drawing_step(seed=5, **kw):

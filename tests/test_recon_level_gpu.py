@@ -99,6 +99,7 @@ def test_stage1_levels_match_oracle_and_golden(golden_dir, name, level, mode, be
     st.load_recipe(seed, perturb)
     st.forward(data["x"].to(DEV), data["noise"][0, 0].to(DEV), data["noise"][0, 1].to(DEV))
     assert tuple(st.fw["feat"].shape) == (3 * B,) + FEAT_SHAPE[level]
+    masks = gradcheck._engine_relu_masks(st)           # (17 + level: the 'REC' pass ends at block ``level``)
     st.gate(B)
     st.backward()
     grads = {k: v.detach().cpu().clone() for k, v in st.named_grads().items()}
@@ -115,7 +116,11 @@ def test_stage1_levels_match_oracle_and_golden(golden_dir, name, level, mode, be
     for k in GAN_KEYS:
         assert _rel(logs[k], ref["logs"][k]) < LOSS_RTOL, (k, logs[k], ref["logs"][k])
         assert _rel(logs[k], float(g[f"step0/logs/{k}"])) < LOSS_RTOL, (k, "golden")
-    gradcheck.check(grads, ref["grads"], ref["grads"], f"stage1 level {level} {mode}", tol16=None)
+    with gradcheck.pinned(O, masks):
+        ref16 = RO.stage1_step_level(level, O.fill_state(O.vaegan_spec(cfg_o), seed, perturb),
+                                     _opts("encoder", "decoder", "discriminator"), data["x"], data["noise"][0, 0],
+                                     data["noise"][0, 1], cfg_o, keep_grads=True, mode=mode, beta=beta)
+    gradcheck.check(grads, ref["grads"], ref16["grads"], f"stage1 level {level} {mode}")
     _check_state_against_golden({k: v.cpu() for k, v in st.state_dict().items()}, g, level)
 
 
@@ -130,6 +135,7 @@ def test_stage1_level2_ragged_batch_matches_oracle():
     st = Stage1Step(ArchConfig.px64(), DEV, recon_level=level)
     st.load_recipe(seed, True)
     st.forward(data["x"].to(DEV), data["noise"][0, 0].to(DEV), data["noise"][0, 1].to(DEV))
+    masks = gradcheck._engine_relu_masks(st)
     st.gate(B)
     st.backward()
     grads = {k: v.detach().cpu().clone() for k, v in st.named_grads().items()}
@@ -142,7 +148,11 @@ def test_stage1_level2_ragged_batch_matches_oracle():
     for k in GAN_KEYS:
         print("B=5", k, logs[k], ref["logs"][k], _rel(logs[k], ref["logs"][k]))
         assert _rel(logs[k], ref["logs"][k]) < LOSS_RTOL, (k, logs[k], ref["logs"][k])
-    gradcheck.check(grads, ref["grads"], ref["grads"], "stage1 level 2 B=5", tol16=None)
+    with gradcheck.pinned(O, masks):
+        ref16 = RO.stage1_step_level(level, O.fill_state(O.vaegan_spec(cfg_o), seed, True),
+                                     _opts("encoder", "decoder", "discriminator"), data["x"], data["noise"][0, 0],
+                                     data["noise"][0, 1], cfg_o, keep_grads=True)
+    gradcheck.check(grads, ref["grads"], ref16["grads"], "stage1 level 2 B=5")
 
 
 def test_dual_stage1_level2_matches_oracle_and_golden(golden_dir):
@@ -157,6 +167,7 @@ def test_dual_stage1_level2_matches_oracle_and_golden(golden_dir):
     data = O.synth_batch(B, cfg_o, seed=1234, steps=int(g["meta/steps"]))
     st = DualStage1Step(ArchConfig.px64(), DEV, lam=lam, recon_level=level)
     st.load_recipe(seed, perturb)
+    rec = gradcheck.Recorder(st)
     nz = data["noise"][0]
     st.step(data["x"].to(DEV), nz[0].to(DEV), nz[1].to(DEV), nz[2].to(DEV))
     logs = st.logs()
@@ -175,11 +186,11 @@ def test_dual_stage1_level2_matches_oracle_and_golden(golden_dir):
         assert _rel(logs[k], ref["logs"][k]) < LOSS_RTOL, (k, logs[k], ref["logs"][k])
         assert _rel(logs[k], float(g[f"step0/logs/{k}"])) < LOSS_RTOL, (k, "golden")
     P16, o16 = state()
-    with gradcheck.storage16(O):
+    with gradcheck.pinned(O, gradcheck.dual_masks(rec, B, level)):
         ref16 = RO.dual_stage1_step_level(level, P16, o16, data["x"], nz, cfg_o, lam=lam, keep_grads=True)
     # (the latent discriminator's two passes cancel, tests/test_wae_gpu.py: plain bound)
     latent_d = [k for k in ref["grads"] if k.startswith("wae_discriminator.")]
-    gradcheck.check(grads, ref["grads"], ref16["grads"], "dual1 level 2", skip=latent_d, tol16=None)
+    gradcheck.check(grads, ref["grads"], ref16["grads"], "dual1 level 2", skip=latent_d)
     for k in latent_d:
         assert _terr(grads[k], ref["grads"][k]) < 0.1, k
     _check_state_against_golden({k: v.cpu() for k, v in st.state_dict().items()}, g, level)

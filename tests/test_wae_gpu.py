@@ -54,18 +54,17 @@ def _wae_state(O, cfg, stage, V, seed):
     return P
 
 
-@pytest.mark.parametrize("stage", [1, 2, 3])
-def test_wae_step_matches_oracle_and_golden(golden_dir, stage):
+def _wae_case(stage, B, V, seed, steps, g=None):
+    """``steps`` steps of the fused WAE step against the oracle (and, with ``g``, the reference's golden numbers); the
+    first step's gradients also against the oracle under its 16-bit storage model with the engine's ReLU masks pinned."""
     from oracle import vaegan_oracle as O
     from fmri_hip.params import ArchConfig
     from fmri_hip.wae_steps import WaeStep
-    g = np.load(os.path.join(golden_dir, f"wae{stage}_b4.npz"))
-    B, seed, steps = int(g["meta/B"]), int(g["meta/seed"]), int(g["meta/steps"])
-    V = int(g["meta/V"]) if stage > 1 else 0
     cfg_o = O.ArchCfg.px64()
     data = O.synth_batch(B, cfg_o, n_voxels=V, seed=1234, steps=steps)
     st = WaeStep(ArchConfig.px64(), DEV, stage, V)
     st.load_recipe(seed, False)
+    rec = gradcheck.Recorder(st)
     P = _wae_state(O, cfg_o, stage, V, seed)
     if stage == 1:
         opts = {"encoder": O.OptState(kind="adam", lr=1e-4), "decoder": O.OptState(kind="adam", lr=1e-4),
@@ -75,6 +74,7 @@ def test_wae_step_matches_oracle_and_golden(golden_dir, stage):
                 "discriminator": O.OptState(kind="adam", lr=5e-4)}
     x = data["x"].to(DEV)
     for s in range(steps):
+        rec.clear()
         if stage == 1:
             st.step(x, data["noise"][s, 2].to(DEV))
             ref = O.wae_stage1_step(P, opts, data["x"], data["noise"][s, 2], cfg_o, keep_grads=True)
@@ -90,7 +90,8 @@ def test_wae_step_matches_oracle_and_golden(golden_dir, stage):
                 # the D-phase losses and the reconstruction are taken at the initial weights; the penalty is scored
                 # by the discriminator after its first (sign-like) Adam update
                 assert r < (1e-3 if k != "loss_penalty" else 5e-3), (k, logs[k], ref["logs"][k])
-                assert _rel(logs[k], float(g[f"step0/logs/{k}"])) < (1e-3 if k != "loss_penalty" else 5e-3), k
+                if g is not None:
+                    assert _rel(logs[k], float(g[f"step0/logs/{k}"])) < (1e-3 if k != "loss_penalty" else 5e-3), k
             else:
                 assert r < 5e-2, (s, k, logs[k], ref["logs"][k])
         if s == 0:
@@ -130,21 +131,35 @@ def test_wae_step_matches_oracle_and_golden(golden_dir, stage):
                 else:
                     worst = max(worst, e)
             print(stage, "worst grad err", worst)
-            # everything without such a cancellation: tight against the 16-bit-storage oracle, direction / length
-            # against the fp32 oracle (tests/gradcheck.py)
+            # everything without such a cancellation: tight against the 16-bit-storage oracle with the engine's ReLU masks
+            # pinned, direction / length against the fp32 oracle (tests/gradcheck.py)
             P16 = _wae_state(O, cfg_o, stage, V, seed)
             o16 = {k: O.OptState(kind="adam", lr=v.lr) for k, v in opts.items()}
-            with gradcheck.storage16(O):
+            with gradcheck.pinned(O, gradcheck.wae_masks(rec, B, stage)):
                 if stage == 1:
                     ref16 = O.wae_stage1_step(P16, o16, data["x"], data["noise"][s, 2], cfg_o, keep_grads=True)
                 else:
                     ref16 = fn(P16, o16, data["fmri"], data["x"], cfg_o, V, keep_grads=True)
             special = [k for k in ref["grads"] if k.startswith("discriminator.") or k.endswith("l_mu.bias")]
-            gradcheck.check(grads, ref["grads"], ref16["grads"], f"wae{stage}", skip=special, tol16=None)
+            gradcheck.check(grads, ref["grads"], ref16["grads"], f"wae{stage} B={B}", skip=special)
         # running statistics after the first (sign-like) parameter update follow the 5e-2 "next forward" bound; after the
         # second update the B = 4 BatchNorm1d variance (4 samples per feature) is chaotic: decoder.fc.1.running_var moved
         # 0.2 % ... 5.6 % with nothing but the choice of convolution kernel (FMRI_C5W / FMRI_TC5 / FMRI_C5 on / off)
-        _check_counters(st, g, f"step{s}", 2e-2 if s == 0 else (5e-2 if s == 1 else 1e-1))
+        if g is not None:
+            _check_counters(st, g, f"step{s}", 2e-2 if s == 0 else (5e-2 if s == 1 else 1e-1))
+
+
+@pytest.mark.parametrize("stage", [1, 2, 3])
+def test_wae_step_matches_oracle_and_golden(golden_dir, stage):
+    g = np.load(os.path.join(golden_dir, f"wae{stage}_b4.npz"))
+    B, seed, steps = int(g["meta/B"]), int(g["meta/seed"]), int(g["meta/steps"])
+    _wae_case(stage, B, int(g["meta/V"]) if stage > 1 else 0, seed, steps, g)
+
+
+def test_wae_stage2_ragged_batch_matches_oracle():
+    """B = 5 (V = 100: fMRI rows padded to 104 columns): 10 rows in the decoder's stacked (z_teacher, z) batch and in the
+    latent discriminator's [real ; fake] pass, neither a multiple of a tile.  No golden file: the oracle comparison only."""
+    _wae_case(2, 5, 100, 3, 1)
 
 
 @pytest.mark.parametrize("mode", ["vae-gan", "beta-vae", "dcgan", "vae"])
@@ -163,6 +178,7 @@ def test_dual_stage1_matches_oracle_and_golden(golden_dir, mode):
     data = O.synth_batch(B, cfg_o, seed=1234, steps=steps)
     st = DualStage1Step(ArchConfig.px64(), DEV, lam=lam, mode=mode, hp=GanHyper(beta=beta))
     st.load_recipe(seed, perturb)
+    rec = gradcheck.Recorder(st)
     P = O.fill_state(O.vaegan_spec(cfg_o), seed, perturb)
     P.update(O.fill_state(O.wae_discriminator_spec(cfg_o, pre="wae_discriminator."), seed + 200, perturb))
     opts = {n: O.OptState(kind="rmsprop", lr=1e-4) for n in ("encoder", "decoder", "discriminator",
@@ -170,6 +186,7 @@ def test_dual_stage1_matches_oracle_and_golden(golden_dir, mode):
     x = data["x"].to(DEV)
     for s in range(steps):
         nz = data["noise"][s]
+        rec.clear()
         st.step(x, nz[0].to(DEV), nz[1].to(DEV), nz[2].to(DEV))
         logs = st.logs()
         ref = O.dual_stage1_step(P, opts, data["x"], nz, cfg_o, lam=lam, keep_grads=True, mode=mode, beta=beta)
@@ -188,12 +205,12 @@ def test_dual_stage1_matches_oracle_and_golden(golden_dir, mode):
             P16.update(O.fill_state(O.wae_discriminator_spec(cfg_o, pre="wae_discriminator."), seed + 200, perturb))
             o16 = {n: O.OptState(kind="rmsprop", lr=1e-4) for n in ("encoder", "decoder", "discriminator",
                                                                        "wae_discriminator")}
-            with gradcheck.storage16(O):
+            with gradcheck.pinned(O, gradcheck.dual_masks(rec, B)):
                 ref16 = O.dual_stage1_step(P16, o16, data["x"], nz, cfg_o, lam=lam, keep_grads=True, mode=mode, beta=beta)
             # (the latent discriminator's two passes cancel, see test_wae_step_matches_oracle_and_golden: plain bound)
             latent_d = [k for k in ref["grads"] if k.startswith("wae_discriminator.")]
             skip = latent_d + ([k for k in ref["grads"] if k.startswith("encoder.")] if mode == "dcgan" else [])
-            gradcheck.check(grads, ref["grads"], ref16["grads"], "dual1", skip=skip, tol16=None)
+            gradcheck.check(grads, ref["grads"], ref16["grads"], f"dual1 {mode}", skip=skip)
             for k in latent_d:
                 assert _terr(grads[k], ref["grads"][k]) < 0.1, k
         # running statistics after the first (sign-like) parameter update follow the 5e-2 "next forward" bound; after the
