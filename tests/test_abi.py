@@ -28,6 +28,104 @@ def test_library_exports_every_declared_symbol(lib):
     assert set(L.EXPORTS) == declared
 
 
+def _header():
+    """include/fmri_hip.h without its comments (a parameter list may hold one)."""
+    hdr = open(os.path.join(ROOT, "include", "fmri_hip.h")).read()
+    return hdr, re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+
+
+def test_every_declared_entry_point_has_a_derived_prototype():
+    """fmri_hip.lib reads its ctypes prototypes from the header: every declared name has one, with one type per declared
+    parameter, and every launch entry point ends in the stream."""
+    from fmri_hip import lib as L
+    hdr, code = _header()
+    declared = set(re.findall(r"\b(fmri_[a-z0-9_]+)\s*\(", hdr)) - {"fmri_err", "fmri_act", "fmri_mode"}
+    assert len(declared) == len(L._SIGS) == len(L._RET) == 133
+    launches = 0
+    for name in sorted(declared):
+        m = re.search(r"([\w*]+)\s+" + name + r"\s*\(([^)]*)\)\s*;", code)
+        assert m, name
+        params = " ".join(m.group(2).split())
+        assert len(L._SIGS[name]) == (0 if params == "void" else params.count(",") + 1), name
+        if m.group(1) == "int" and params.endswith("void* stream"):
+            assert L._SIGS[name][-1] is ctypes.c_void_p and L._RET[name] is ctypes.c_int, name
+            launches += 1
+    assert launches > 50                                         # the branch above saw the launches
+
+
+def test_derived_prototypes_literal_pins():
+    """Full signatures written out, together one for every row of the type mapping."""
+    from fmri_hip import lib as L
+    i, l, f, p, s = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p
+    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    pins = {
+        "fmri_igemm_ep": (i, [p] * 5 + [i] * 15 + [l, i, l, p, p, p]),
+        "fmri_state_copy": (i, [p, p, i, p, l, l, i, p, i, i, u64, p, p]),
+        "fmri_test_fastdiv": (u32, [u32, u32]),
+        "fmri_latent_range_scale": (f, [f, f]),
+        "fmri_pcc_matrix_ws_bytes": (l, [i, i, l]),
+        "fmri_last_error_string": (s, [i]),
+        "fmri_igemm_route": (i, [i] * 16 + [l] + [i] * 6 + [s, i]),
+        "fmri_pcc": (i, [p, p, l, p, p, p]),                      # double* ws5
+        "fmri_ema_decay_at": (f, [i, i, f, i]),
+        "fmri_tconv_class": (i, [i] * 6 + [p] * 6),
+        "fmri_version": (i, []),
+    }
+    for name, (ret, args) in pins.items():
+        assert L._RET[name] is ret, name
+        assert L._SIGS[name] == args, name
+    assert L.read_header("double fmri_d(double a, const char* b, int32_t c, const int* d);")[:2] == (
+        {"fmri_d": [ctypes.c_double, s, i, p]}, {"fmri_d": ctypes.c_double})
+
+
+@pytest.mark.parametrize("text", ["int fmri_x(size_t n);", "struct foo fmri_x(int a);",
+                                  "int fmri_x(void (*)(int), int n);"])
+def test_header_reader_refuses_what_it_does_not_understand(text):
+    from fmri_hip import lib as L
+    with pytest.raises(RuntimeError, match="fmri_x"):
+        L.read_header("int fmri_ok(int a);\n" + text + "\nint fmri_after(void);\n")
+
+
+def test_struct_mirrors_match_the_header():
+    """The hand-written ctypes.Structure mirrors against the header's structs: field names in order, array lengths, the
+    element type of every field (any pointer is a c_void_p) and the size."""
+    from fmri_hip import lib as L
+    hdr, code = _header()
+    mirrors = {"fmri_epilogue": (L.Epilogue, 160), "fmri_wgrad_plan": (L.WgradPlan, 104), "fmri_stat_seg": (L.StatSeg, 64),
+               "fmri_state_seg": (L.StateSeg, 32), "fmri_ema_seg": (L.EmaSeg, 32), "fmri_schedule": (L.Schedule, 160)}
+    scalar = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+              "char": ctypes.c_char}
+    stated = {n: int(b) for n, b in re.findall(r"\}\s*(fmri_\w+);\s*/\*\s*(\d+) bytes\s*\*/", hdr)}
+    assert set(stated) & set(mirrors) == {"fmri_stat_seg", "fmri_state_seg", "fmri_ema_seg", "fmri_schedule"}
+    bodies = {n: b for b, n in re.findall(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(fmri_\w+)\s*;", code)}
+    for name, (mirror, size) in mirrors.items():
+        want = []
+        for decl in filter(None, (" ".join(d.split()) for d in bodies[name].split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            ctype, first = re.fullmatch(r"(.*[ *])(\w+(?:\[\w+\])?)", first).groups()
+            elem = ctypes.c_void_p if "*" in ctype else scalar[ctype.replace("const", "").strip()]
+            for d in [first] + more:
+                field, n = re.fullmatch(r"(\w+)(?:\[(\w+)\])?", d).groups()
+                want.append((field, elem, None if n is None else int(n) if n.isdigit() else L.CONST[n]))
+        got = [(fn, getattr(ft, "_type_", ft) if hasattr(ft, "_length_") else ft, getattr(ft, "_length_", None))
+               for fn, ft in mirror._fields_]
+        assert got == want, name
+        assert ctypes.sizeof(mirror) == size == stated.get(name, size), name
+
+
+def test_constants_come_from_the_header_unchanged():
+    from fmri_hip import lib as L
+    from fmri_hip import ops
+    assert (L.SCHED_MAX_LR, L.STATE_HEADER, L.STATE_CHUNK, L.EMA_CHUNK, L.STAT_MAX_SEGS) == (4, 64, 16384, 4096, 8)
+    assert L.STATE_MAGIC == 0x31544154534d4621
+    assert (L.EP_ACT_APPLIED, L.EP_AFFINE_APPLIED) == (0x40000000, 0x20000000)
+    assert L.STAT_BYTES == 32
+    assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_TANH, ops.ACT_SIGMOID) == (0, 1, 2, 3)
+    assert (ops.MODE_CONV, ops.MODE_TCONV2, ops.MODE_CONV_FLIP) == (0, 1, 2)
+    assert L.read_header("#define FMRI_A 0x10u\n#define FMRI_B 7ll /* c */\nenum e { FMRI_C = -2, FMRI_D = 3 };")[2] == {
+        "FMRI_A": 16, "FMRI_B": 7, "FMRI_C": -2, "FMRI_D": 3}
+
+
 def test_version_and_error_strings(lib):
     assert lib.fmri_version() >= 100
     assert lib.fmri_last_error_string(0) == b"ok"

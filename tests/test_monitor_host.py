@@ -36,11 +36,9 @@ def test_bindings_pass_every_declared_parameter():
     from fmri_hip import lib as L
     hdr = open(os.path.join(ROOT, "include", "fmri_hip.h")).read()
     for name in NEW:
-        if name not in L._SIGS:
-            continue
-        m = re.search(r"\b" + name + r"\s*\(([^)]*)\)", hdr)
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)      # the declaration, not a mention in a comment
         assert m, name
-        assert m.group(1).rstrip().endswith("void* stream"), name
+        assert m.group(1).rstrip().endswith("void* stream") or name == "fmri_tensor_stats_ws_bytes", name   # host only
         assert len(L._SIGS[name]) == m.group(1).count(",") + 1, name
 
 

@@ -6,136 +6,61 @@ torch.cuda.current_stream()).
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# FMRI_LIB_PATH: another build of the same library (A/B timing of two builds in one gpurun call)
+# FMRI_LIB_PATH: another build of the same library (A/B timing of two builds in one job)
 LIB_PATH = os.environ.get("FMRI_LIB_PATH") or os.path.join(_HERE, "libfmri_hip.so")
 
-_i, _f, _l, _p = C.c_int, C.c_float, C.c_int64, C.c_void_p
+HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "..", "include", "fmri_hip.h"))
 
-# name -> argtypes (restype is int unless noted)
-_SIGS = {
-    "fmri_tconv_class": [_i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
-                         C.POINTER(_i), C.POINTER(_l)],
-    "fmri_kpad": [_i, _i],
-    "fmri_pack_weight": [_p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "fmri_pack_entry_bytes": [],
-    "fmri_apply_entry_bytes": [],
-    "fmri_transpose_entry_bytes": [],
-    "fmri_transpose_entry_fill": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i],
-    "fmri_transpose_f16_batch": [_p, _i, _i, _p],
-    "fmri_pack_entry_fill": [_p, _p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
-    "fmri_pack_weight_batch": [_p, _i, _i, _p],
-    "fmri_apply_entry_fill": [_p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l,
-                              _i, _f, _l, _i],
-    "fmri_transpose_f16": [_p, _p, _i, _i, _i, _i, _i, _p],
-    "fmri_apply_batch": [_p, _i, _i, _i, _p, _f, _f, _f, _p, _f, _p, _i, _p],
-    "fmri_ingest_u8": [_p, _i, _i, _i, _i, _p, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p],
-    "fmri_ingest_u8_gather": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p],
-    "fmri_gather_rows_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p],
-    "fmri_crop_resize_u8": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p],
-    "fmri_pcc": [_p, _p, _l, _p, _p, _p],
-    "fmri_ssim": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
-    "fmri_pcc_matrix": [_p, _p, _i, _i, _l, _p, _i, _p, _l, _p],
-    "fmri_ssim_pairs": [_p, _p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _l, _p],
-    "fmri_image_metrics": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p, _i, _p],
-    "fmri_nway_scores": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _p],
-    "fmri_images_u8": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _l, _i, _p, _p],
-    "fmri_images_u8_open": [_p, _i, _p, _p, _l, _i, _p],
-    "fmri_unpack_grad": [_p, _p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _l, _p],
-    "fmri_igemm": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p],
-    "fmri_igemm_ep": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _l, _p, _p,
-                      _p],
-    "fmri_igemm_route": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _i, _i, _i, _i, _i,
-                         C.c_char_p, _i],
-    "fmri_wgrad_slabs": [_i, _i, _i, _i, _i, _i],
-    "fmri_wgrad_narrow_blocks": [_i, _i, _i],
-    "fmri_wgrad_route": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],       # _p: WgradPlan*
-    "fmri_set_deterministic": [_i],
-    "fmri_get_deterministic": [],
-    "fmri_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "fmri_wgrad_if": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "fmri_nchw_to_nhwc": [_p, _p, _i, _i, _i, _i, _p],
-    "fmri_nhwc_to_nchw": [_p, _p, _i, _i, _i, _i, _f, _p],
-    "fmri_rows_f32_to_f16": [_p, _p, _i, _i, _i, _f, _p],
-    "fmri_rows_f16_to_f32": [_p, _p, _i, _i, _i, _f, _p],
-    "fmri_reduce_slabs": [_p, _i, _l, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p],
-    "fmri_permute_chw": [_p, _p, _i, _i, _i, _f, _i, _p],
-    "fmri_bn_stats": [_p, _i, _i, _p, _p, _l, _p],
-    "fmri_bn_finalize": [_p, _i, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fmri_bn_stats_finalize": [_p, _i, _i, _p, _p, _l, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fmri_bn_cols_fwd": [_p, _p, _i, _i, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
-    "fmri_bn_cols_fwd_s": [_p, _p, _i, _i, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p],
-    "fmri_bn_finalize_s": [_p, _i, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fmri_latent_fwd_ranged": [_p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _f, _i, _p],
-    "fmri_rows_absmax": [_p, _l, _p, _p],
-    "fmri_bn_cols_bwd": [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p, _f, _i, _p],
-    "fmri_bn_fold_finalize": [_p, _i, _i, _p, _p, _f, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fmri_bn_fold": [_p, _i, _i, _p, _p, _p],
-    "fmri_bn_bwd_fold": [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _i, _p],
-    "fmri_bn_apply": [_p, _p, _i, _i, _p, _p, _i, _p],
-    "fmri_bn_bwd_reduce": [_p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _l, _p, _p, _f, _p],
-    "fmri_bn_bwd_apply": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p],
-    "fmri_bn_bwd_reduce2": [_p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _l, _p, _p, _f, _i, _p],
-    "fmri_bn_bwd_apply2": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p],
-    "fmri_act_bwd": [_p, _p, _p, _i, _i, _i, _p, _p, _l, _p, _i, _f, _p],
-    "fmri_colsum_acc": [_p, _i, _i, _i, _l, _l, _f, _p, _p],
-    "fmri_colsum_rows": [_p, _i, _i, _p, _p, _l, _p, _i, _f, _p],
-    "fmri_latent_fwd": [_p, _p, _i, _i, _i, _p, _p, _p, _i, _p],
-    "fmri_latent_bwd": [_p, _p, _p, _i, _f, _f, _p, _i, _i, _f, _p, _p, _i, _p],
-    "fmri_feat_mse": [_p, _i, _i, _p, _p, _p],
-    "fmri_feat_mse_bwd": [_p, _i, _i, _p, _f, _p, _p],
-    "fmri_feat_mse_wide": [_p, _i, _i, _p, _p, _p, _l, _p],
-    "fmri_feat_mse_bwd_wide": [_p, _i, _i, _p, _f, _p, _i, _p],
-    "fmri_pixel_sq": [_p, _p, _l, _i, _i, _p, _p, _f, _p],
-    "fmri_gan_head": [_p, _i, _i, _p, _p, _p],
-    "fmri_gan_head_bwd": [_p, _i, _i, _p, _i, _f, _p, _p],
-    "fmri_gan_head_parts": [_p, _i, _i, _p, _p, _i, _p],
-    "fmri_gan_head_bwd_parts": [_p, _i, _i, _p, _i, _f, _p, _i, _p],
-    "fmri_wae_logloss": [_p, _i, _i, _i, _f, _p, _p, _p, _i, _f, _p],
-    "fmri_mmd_imq": [_p, _i, _p, _i, _i, _i, _f, _p, _i, _f, _p, _p, _i, _f, _p, _l, _p],
-    "fmri_mlp_fwd": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
-    "fmri_mlp_bwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _p],
-    "fmri_compose_gate": [_p, _p, _f, _f, _f, _f, _f, _i, _i, _i, _p],
-    "fmri_axpby_f16": [_p, _p, _p, _l, _f, _f, _p, _p],
-    "fmri_axpby2_f16": [_p, _p, _p, _l, _f, _f, _p, _p, _p],
-    "fmri_compose_gate_dev": [_p, _p, _f, _f, _f, _p, _i, _i, _i, _i, _p],
-    "fmri_counter_inc": [_p, _p],
-    "fmri_rng_normal": [_p, _p, _i, _i, _i, _l, _i, _f, _p],
-    "fmri_rng_u32": [_p, _p, _l, _i, _i, _i, _p],
-    "fmri_rng_u32_at": [_p, _p, _l, _l, _i, _i, _i, _p],
-    "fmri_rng_advance": [_p, _l, _p],
-    "fmri_sampler_indices": [_p, _i, _i, _l, _p, _p],
-    "fmri_sampler_advance": [_p, _i, _i, _p],
-    "fmri_diffaug_params": [_p, _p, _i, _l, _i, _i, _i, _i, _i, _p],
-    "fmri_diffaug_fwd": [_p, _p, _i, _i, _i, _p, _i, _i, _p],
-    "fmri_diffaug_bwd": [_p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p],
-    "fmri_voxaug_params": [_p, _p, _i, _l, _i, _i, _f, _f, _f, _i, _i, _f, _p],
-    "fmri_voxaug_apply": [_p, _i, _i, _p, _p, _l, _i, _i, _p, _p, _p],
-    "fmri_schedule_seek_host": [_p, _l, _p],
-    "fmri_epoch_begin": [_p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fmri_trainlog_append": [_p, _p, _i, _p, _l, _p, _p],
-    "fmri_state_nontemporal": [_i],
-    "fmri_state_copy": [_p, _p, _i, _p, _l, _l, _i, _p, _i, _i, C.c_uint64, _p, _p],
-    "fmri_ema_update": [_p, _p, _i, _p, _p],
-    "fmri_ema_swap": [_p, _p, _i, _p],
-    "fmri_rmsprop_dev": [_p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _p],
-    "fmri_adam_dev": [_p, _p, _p, _p, _l, _p, _f, _f, _f, _p, _f, _p, _f, _p, _p],
-    "fmri_sumsq": [_p, _l, _p, _p],
-    "fmri_renorm": [_p, _p, _l, _f, _p, _f, _p, _p, _p],
-    "fmri_sumsq_f64": [_p, _l, _p, _i, _p],
-    "fmri_renorm_f64": [_p, _p, _l, _f, _p, _f, _p, _p, _p],
-    "fmri_rmsprop": [_p, _p, _p, _l, _f, _f, _f, _f, _p, _f, _p, _p],
-    "fmri_adam": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p, _f, _p, _p],
-    "fmri_tensor_stats": [_p, _i, _p, _p],
-    "fmri_apply_batch_stats": [_p, _i, _i, _i, _p, _f, _f, _f, _p, _f, _p, _i, _p, _p],
-    "fmri_stat_fold": [_p, _i, _p, _p, _p],
-    "fmri_bn_bwd_apply_cnt": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p],
-    "fmri_bn_bwd_apply2_cnt": [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p],
-    "fmri_bn_cols_bwd_cnt": [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _p, _p, _p, _f, _i, _p, _p],
-}
+_CTYPES = {"int": C.c_int, "int32_t": C.c_int, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+           "float": C.c_float, "double": C.c_double}
+_INT = r"(-?(?:0[xX][0-9a-fA-F]+|\d+))"
+
+
+def _ctype(decl):
+    """ctypes type of a C return type or parameter ('int64_t', 'const float* x'); None when the table has no row."""
+    if "*" in decl:
+        return C.c_char_p if re.fullmatch(r"(?:const\s+)?char\s*\*\s*\w*", decl) else C.c_void_p
+    m = re.fullmatch(r"(?:const\s+)?(\w+)(?:\s+\w+)?", decl)
+    return _CTYPES.get(m[1]) if m else None
+
+
+def read_header(text):
+    """The C ABI as include/fmri_hip.h states it: (name -> argtypes, name -> restype, FMRI_* constant -> int).
+    Every file-scope ``RET fmri_name(ARGS);`` is an entry point (the ``static inline`` helpers are not); a declaration
+    whose shape or types are not understood raises -- a guessed prototype would hand a kernel shifted arguments."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    const = {m[1]: int(m[2], 0) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(FMRI_\w+)[ \t]+" + _INT +
+                                                     r"[uUlL]*[ \t]*$", text, re.M)}
+    const.update((m[1], int(m[2], 0)) for m in re.finditer(r"\b(FMRI_\w+)\s*=\s*" + _INT + r"\s*[,}]", text))
+    sigs, ret = {}, {}
+    for stmt in re.split(r"[;{}]", re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+        found = re.search(r"\bfmri_[a-z0-9_]+(?=\s*\()", stmt)
+        if not found or stmt.lstrip().startswith("static"):
+            continue
+        name, stmt = found[0], " ".join(stmt.split())
+        m = re.fullmatch(r"([\w *]+?)\b(fmri_[a-z0-9_]+) ?\(([^()]*)\)", stmt)
+        if not m or m[2] != name or name in sigs:
+            raise RuntimeError(f"include/fmri_hip.h: cannot read the declaration of {name} (or it is a second one): `{stmt}`")
+        decls = [m[1].strip()] + ([] if m[3].strip() == "void" else [a.strip() for a in m[3].split(",")])
+        types = [_ctype(d) for d in decls]
+        if None in types:
+            raise RuntimeError(f"include/fmri_hip.h: no ctypes type for `{decls[types.index(None)]}` in the declaration "
+                               f"of {name}: `{stmt}`")
+        ret[name], sigs[name] = types[0], types[1:]
+    return sigs, ret, const
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes prototypes of libfmri_hip.so are read from it.")
+with open(HEADER_PATH) as _f:
+    _SIGS, _RET, CONST = read_header(_f.read())     # name -> argtypes, name -> restype, FMRI_* -> int
+EXPORTS = sorted(_SIGS)
+
 
 class Epilogue(C.Structure):
     """``fmri_epilogue`` of include/fmri_hip.h (BatchNorm statistics out of a contraction's epilogue)."""
@@ -177,25 +102,15 @@ class Schedule(C.Structure):
                 ("lr_step", C.c_int64), ("applied_epoch", C.c_int64)]
 
 
-SCHED_MAX_LR = 4         # FMRI_SCHED_MAX_LR
-STATE_MAGIC = 0x31544154534d4621     # FMRI_STATE_MAGIC
-STATE_HEADER = 64        # FMRI_STATE_HEADER
-STATE_CHUNK = 16384      # FMRI_STATE_CHUNK
-EMA_CHUNK = 4096         # FMRI_EMA_CHUNK (floats)
-STAT_BYTES = 32          # sizeof(fmri_stat)
-STAT_MAX_SEGS = 8        # FMRI_STAT_MAX_SEGS
-
-
-EP_ACT_APPLIED = 0x40000000
-EP_AFFINE_APPLIED = 0x20000000
-
-
-EXPORTS = sorted(list(_SIGS) + ["fmri_version", "fmri_last_error_string", "fmri_test_fastdiv", "fmri_bn_ws_floats",
-                             "fmri_bn_fold_scratch_floats", "fmri_resize_coeffs", "fmri_latent_range_scale",
-                             "fmri_mmd_imq_ws_bytes", "fmri_pcc_matrix_ws_bytes", "fmri_ssim_pairs_ws_bytes",
-                             "fmri_image_metrics_ws_bytes", "fmri_nway_ws_bytes", "fmri_images_u8_ws_bytes",
-                             "fmri_images_u8_out_bytes", "fmri_state_layout", "fmri_ema_decay_at",
-                             "fmri_tensor_stats_ws_bytes", "fmri_feat_mse_wide_chunk", "fmri_feat_mse_wide_ws_floats"])
+SCHED_MAX_LR = CONST["FMRI_SCHED_MAX_LR"]
+STATE_MAGIC = CONST["FMRI_STATE_MAGIC"]
+STATE_HEADER = CONST["FMRI_STATE_HEADER"]
+STATE_CHUNK = CONST["FMRI_STATE_CHUNK"]
+EMA_CHUNK = CONST["FMRI_EMA_CHUNK"]            # floats
+STAT_BYTES = 32                                # sizeof(fmri_stat): the header has no macro for it
+STAT_MAX_SEGS = CONST["FMRI_STAT_MAX_SEGS"]
+EP_ACT_APPLIED = CONST["FMRI_EP_ACT_APPLIED"]
+EP_AFFINE_APPLIED = CONST["FMRI_EP_AFFINE_APPLIED"]
 
 _lib = None
 
@@ -212,45 +127,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, args in _SIGS.items():
         fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = _i
-    lib.fmri_version.restype = _i
-    lib.fmri_last_error_string.restype = C.c_char_p
-    lib.fmri_last_error_string.argtypes = [_i]
-    lib.fmri_test_fastdiv.restype = C.c_uint32
-    lib.fmri_test_fastdiv.argtypes = [C.c_uint32, C.c_uint32]
-    lib.fmri_bn_ws_floats.restype = _l
-    lib.fmri_bn_ws_floats.argtypes = [_i, _i]
-    lib.fmri_bn_fold_scratch_floats.restype = _i
-    lib.fmri_bn_fold_scratch_floats.argtypes = [_i]
-    lib.fmri_resize_coeffs.restype = _i
-    lib.fmri_resize_coeffs.argtypes = [_i, _i, _p, _p, _i]
-    lib.fmri_latent_range_scale.restype = _f
-    lib.fmri_latent_range_scale.argtypes = [_f, _f]
-    lib.fmri_mmd_imq_ws_bytes.restype = _l
-    lib.fmri_mmd_imq_ws_bytes.argtypes = [_i, _i]
-    lib.fmri_pcc_matrix_ws_bytes.restype = _l
-    lib.fmri_pcc_matrix_ws_bytes.argtypes = [_i, _i, _l]
-    lib.fmri_ssim_pairs_ws_bytes.restype = _l
-    lib.fmri_ssim_pairs_ws_bytes.argtypes = [_i, _i, _i, _i, _i]
-    lib.fmri_image_metrics_ws_bytes.restype = _l
-    lib.fmri_image_metrics_ws_bytes.argtypes = [_i, _i, _i]
-    lib.fmri_nway_ws_bytes.restype = _l
-    lib.fmri_nway_ws_bytes.argtypes = [_i, _i, _i]
-    lib.fmri_images_u8_ws_bytes.restype = _l
-    lib.fmri_images_u8_ws_bytes.argtypes = [_i]
-    lib.fmri_images_u8_out_bytes.restype = _l
-    lib.fmri_images_u8_out_bytes.argtypes = [_i, _i, _i, _i, _i, _i, _i]
-    lib.fmri_state_layout.restype = _l
-    lib.fmri_state_layout.argtypes = [_p, _i, _p]
-    lib.fmri_ema_decay_at.restype = _f
-    lib.fmri_ema_decay_at.argtypes = [C.c_int32, C.c_int32, _f, C.c_int32]
-    lib.fmri_tensor_stats_ws_bytes.restype = _i
-    lib.fmri_tensor_stats_ws_bytes.argtypes = [_i]
-    lib.fmri_feat_mse_wide_chunk.restype = _i
-    lib.fmri_feat_mse_wide_chunk.argtypes = []
-    lib.fmri_feat_mse_wide_ws_floats.restype = _l
-    lib.fmri_feat_mse_wide_ws_floats.argtypes = [_i, _i]
+        fn.argtypes, fn.restype = args, _RET[name]
     _lib = lib
     return lib
 
@@ -312,9 +189,10 @@ def call(name, *args):
 
 def tconv_class(k, pad, cy, cx, ci, rows_pad):
     lib = load()
-    py, px, th, tw, kpad = _i(), _i(), _i(), _i(), _i()
-    woff = _l()
-    check(lib.fmri_tconv_class(k, pad, cy, cx, ci, rows_pad, py, px, th, tw, kpad, woff), "fmri_tconv_class")
+    py, px, th, tw, kpad = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    woff = C.c_int64()
+    check(lib.fmri_tconv_class(k, pad, cy, cx, ci, rows_pad, *map(C.byref, (py, px, th, tw, kpad, woff))),
+          "fmri_tconv_class")
     return dict(py=py.value, px=px.value, th=th.value, tw=tw.value, kpad=kpad.value, w_off=woff.value)
 
 

@@ -18,8 +18,8 @@ import torch
 
 from . import lib
 
-ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
-MODE_CONV, MODE_TCONV2, MODE_CONV_FLIP = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = (lib.CONST["FMRI_ACT_" + n] for n in ("NONE", "RELU", "TANH", "SIGMOID"))
+MODE_CONV, MODE_TCONV2, MODE_CONV_FLIP = (lib.CONST["FMRI_" + n] for n in ("CONV", "TCONV2", "CONV_FLIP"))
 
 _P = lib.ptr
 
