@@ -19,6 +19,7 @@
 #ifndef FMRI_HIP_H
 #define FMRI_HIP_H
 #include <stdint.h>
+#include "fmri_hip_contrast.h"   /* contrastive latent alignment: its two entry points are declared there */
 #ifdef __cplusplus
 extern "C" {
 #endif

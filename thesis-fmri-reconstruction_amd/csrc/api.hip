@@ -1255,6 +1255,19 @@ int fmri_mmd_imq(const float* q, int ldq, const float* p, int ldp, int n, int d,
     return mmd_imq_launch(q, ldq, p, ldp, n, d, sigma2, scales, nscales, w, total, dq, ldd, gscale, ws, ws_bytes,
                           S(stream));
 }
+int64_t fmri_latent_nce_ws_bytes(int n, int d) { return latent_nce_ws_bytes(n, d); }
+int fmri_latent_nce(const float* q, int ldq, const float* t, int ldt, int n, int d, float tau, int symmetric, float w,
+                    float* total, float* top1, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
+                    void* stream) {
+    if (!q || !t || !ws || n < 2 || d < 1 || ldq < d || ldt < d || !(tau >= 0.01f && tau <= 1.f))
+        return FMRI_E_BADARG;
+    if (dq && ldd < d) return FMRI_E_BADARG;
+    if (latent_nce_ws_bytes(n, d) < 0) return FMRI_E_UNSUPPORTED;
+    // float4 loads of the q / t rows
+    if (((uintptr_t)q | (uintptr_t)t) % 16 || ldq % 4 || ldt % 4) return FMRI_E_BADARG;
+    return latent_nce_launch(q, ldq, t, ldt, n, d, tau, symmetric, w, total, top1, dq, ldd, gscale, ws, ws_bytes,
+                             S(stream));
+}
 int fmri_mlp_fwd(const void* z16, int M, int Zp, int H, const void* const* w5, const int* kp5, const float* const* bias5,
                  void* const* hs4, float* logit, void* stream) {
     if (!z16 || !w5 || !kp5 || !bias5 || !hs4 || !logit || M < 1) return FMRI_E_BADARG;

@@ -268,6 +268,10 @@ int64_t mmd_imq_ws_bytes(int n, int d);
 int mmd_imq_launch(const float* q, int ldq, const float* p, int ldp, int n, int d, float sigma2, const float* scales,
                    int nscales, float w, float* total, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
                    hipStream_t st);
+int64_t latent_nce_ws_bytes(int n, int d);
+int latent_nce_launch(const float* q, int ldq, const float* t, int ldt, int n, int d, float tau, int symmetric, float w,
+                      float* total, float* top1, float* dq, int ldd, float gscale, void* ws, int64_t ws_bytes,
+                      hipStream_t st);
 int compose_gate_launch(float* scal, int* flags, float batch, float nfeat, float npix, float lambda_mse,
                         float equilibrium, float margin, float beta, const float* hp_dev, int mode, int gate_on,
                         int force_dis, int force_dec, hipStream_t st);

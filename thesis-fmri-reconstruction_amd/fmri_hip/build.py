@@ -10,8 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.abspath(os.path.join(HERE, "..", "csrc"))
 LIB = os.path.join(HERE, "libfmri_hip.so")
-SOURCES = ["igemm.hip", "igemm_narrow.hip", "igemm_tc32.hip", "igemm_tc5.hip", "igemm_tc5w.hip", "igemm_c5.hip", "igemm_c5w.hip", "wgrad.hip", "wgrad_win.hip", "wgrad_narrow.hip", "layout.hip", "norm.hip", "loss.hip", "featloss.hip", "mlp.hip", "metrics.hip", "evalmetrics.hip", "ingest.hip", "mmd.hip", "ident.hip", "nway.hip", "egress.hip", "monitor.hip", "rng.hip", "schedule.hip", "state.hip", "ema.hip", "diffaug.hip", "voxaug.hip", "api.hip"]
-HEADERS = ["common.h", "kernels.h", "pipe.h", "philox.h", "ssim_window.h", os.path.join("..", "..", "include", "fmri_hip.h")]
+SOURCES = ["igemm.hip", "igemm_narrow.hip", "igemm_tc32.hip", "igemm_tc5.hip", "igemm_tc5w.hip", "igemm_c5.hip", "igemm_c5w.hip", "wgrad.hip", "wgrad_win.hip", "wgrad_narrow.hip", "layout.hip", "norm.hip", "loss.hip", "featloss.hip", "mlp.hip", "metrics.hip", "evalmetrics.hip", "ingest.hip", "mmd.hip", "contrast.hip", "ident.hip", "nway.hip", "egress.hip", "monitor.hip", "rng.hip", "schedule.hip", "state.hip", "ema.hip", "diffaug.hip", "voxaug.hip", "api.hip"]
+HEADERS = ["common.h", "kernels.h", "pipe.h", "philox.h", "ssim_window.h", os.path.join("..", "..", "include", "fmri_hip.h"),
+           os.path.join("..", "..", "include", "fmri_hip_contrast.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wno-unused-result"]
 
 

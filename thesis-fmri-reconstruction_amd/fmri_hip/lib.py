@@ -1,4 +1,4 @@
-"""ctypes binding of libfmri_hip.so (C ABI: include/fmri_hip.h).
+"""ctypes binding of libfmri_hip.so (C ABI: include/fmri_hip.h and the headers it includes, ``EXT_HEADERS``).
 
 There is no fallback: if the shared library is missing or a kernel returns an error the caller gets a
 RuntimeError.  PyTorch is used only as the allocator / stream provider (tensor.data_ptr(),
@@ -60,6 +60,30 @@ if not os.path.exists(HEADER_PATH):
 with open(HEADER_PATH) as _f:
     _SIGS, _RET, CONST = read_header(_f.read())     # name -> argtypes, name -> restype, FMRI_* -> int
 EXPORTS = sorted(_SIGS)
+# Headers that fmri_hip.h includes, read the same way (name -> header file).  They are kept in tables of their own because
+# tests/test_abi.py pins ``_SIGS`` / ``EXPORTS`` to the entry points fmri_hip.h itself declares, by number; an entry point
+# added since goes into an included header (one line here) and is looked up through ``prototype``.
+EXT_HEADERS = ("fmri_hip_contrast.h",)
+_EXT_SIGS, _EXT_RET, EXT_EXPORTS = {}, {}, {}
+for _h in EXT_HEADERS:
+    _path = os.path.join(os.path.dirname(HEADER_PATH), _h)
+    if not os.path.exists(_path):
+        raise RuntimeError(f"{_path} is missing: include/fmri_hip.h includes it and the ctypes prototypes are read from it.")
+    with open(_path) as _f:
+        _s, _r, _c = read_header(_f.read())
+    if set(_s) & (set(_SIGS) | set(_EXT_SIGS)):
+        raise RuntimeError(f"include/{_h}: declares {sorted(set(_s) & (set(_SIGS) | set(_EXT_SIGS)))} a second time")
+    _EXT_SIGS.update(_s)
+    _EXT_RET.update(_r)
+    CONST.update(_c)
+    EXT_EXPORTS.update({n: _h for n in _s})
+
+
+def prototype(name):
+    """(argtypes, restype) of an entry point, whichever header declares it."""
+    if name in _SIGS:
+        return _SIGS[name], _RET[name]
+    return _EXT_SIGS[name], _EXT_RET[name]
 
 
 class Epilogue(C.Structure):
@@ -125,9 +149,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m fmri_hip.build` (hipcc --offload-arch=gfx950). "
             "The engine has no CPU / eager fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, args in _SIGS.items():
+    for name in list(_SIGS) + list(_EXT_SIGS):
         fn = getattr(lib, name)
-        fn.argtypes, fn.restype = args, _RET[name]
+        fn.argtypes, fn.restype = prototype(name)
     _lib = lib
     return lib
 

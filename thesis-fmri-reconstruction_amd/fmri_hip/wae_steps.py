@@ -29,6 +29,7 @@ import torch
 
 from . import lib
 from .nets import CognitiveEncoderNet, DecoderNet, EncoderNet, WaeDiscriminatorNet
+from .contrast import N_MAX, LatentContrast, latent_nce
 from .mmd import mmd_imq
 from .ops import images_to_nhwc, nhwc_to_images, pad8, require_gpu, rows_to_f16
 from .params import ArchConfig
@@ -41,6 +42,10 @@ _P = lib.ptr
 # slots of the scalar block used by the WAE steps (sums over the global batch; [0, 4) are all-reduced)
 W_REC, W_PEN, W_DFAKE, W_DREAL = 0, 1, 2, 3
 W_LOG_KEYS = ("loss_reconstruction", "loss_penalty", "loss_discriminator_fake", "loss_discriminator_real")
+# contrast= only: two of the block's free slots [26, 32), all-reduced with the four above (the slots between them are
+# still zero at that point of a WAE step)
+W_CON, W_TOP1 = 26, 27
+W_CON_KEYS = ("loss_contrast", "latent_top1")
 
 
 @dataclass
@@ -100,12 +105,20 @@ class WaeStep(_LatentDiscPhase, _StepBase):
     II / III the Stage-I teacher's means -- with the statistic over the GLOBAL batch (data parallel: q and p gathered by
     one SUM all-reduce of a zero-padded buffer).  loss_penalty is lam_mmd * n * MMD_u in Stage I, lam_mmd * MMD_u in
     Stages II / III (the "sum" / "mean" conventions of the GAN penalty); Stage III logs it without back-propagating it;
-    the two discriminator losses log 0."""
+    the two discriminator losses log 0.
+
+    ``contrast``: a fmri_hip.contrast.LatentContrast (Stages II / III) adds weight * InfoNCE(q, t) (csrc/contrast.hip)
+    between the cognitive means q = head[:, :Z] and the teacher's means t, beside either penalty: row i of the fMRI batch
+    is told to retrieve row i of the image batch, which neither penalty says.  A batch mean over the GLOBAL batch (q and
+    t gathered as for the MMD); Stage II back-propagates it into the cognitive encoder, Stage III logs it only.  The logs
+    gain ``loss_contrast`` and ``latent_top1`` (the in-batch top-1 retrieval rate).  Without the keyword the step issues
+    the launches and logs the four values it always did."""
 
     def __init__(self, cfg: ArchConfig, device, stage: int = 1, n_voxels: int = 0, hp: Optional[WaeHyper] = None,
                  scales: Optional[Scales] = None, distributed: bool = False, sync_bn: bool = True,
                  penalty: str = "gan", monitor: bool = False, rng: Optional[DeviceRng] = None, feed=None,
-                 schedule=None, log=None, checkpoints=None, ema=None, fmri_augment=None):
+                 schedule=None, log=None, checkpoints=None, ema=None, fmri_augment=None,
+                 contrast: Optional[LatentContrast] = None):
         """``fmri_augment``: a fmri_hip.voxaug.VoxelAugment in front of the cognitive encoder (Stages II / III, needs
         ``rng``; see steps.CognitiveStep); ``step(..., fmri_aug=table)`` pins the per-row parameters.
         ``ema``: a fmri_hip.ema.WeightEma (see steps.Stage1Step) over the networks this stage trains.
@@ -124,7 +137,14 @@ class WaeStep(_LatentDiscPhase, _StepBase):
             raise ValueError(f"WaeStep: penalty must be 'gan' or 'mmd', got {penalty!r}")
         if fmri_augment is not None and stage == 1:
             raise ValueError("WaeStep: fmri_augment= needs stage 2 or 3 (Stage I reads no fMRI rows)")
-        self.penalty = penalty
+        if contrast is not None and stage == 1:
+            raise ValueError("WaeStep: contrast= needs stage 2 or 3 (Stage I has no second modality to align with)")
+        if contrast is not None and not isinstance(contrast, LatentContrast):
+            raise ValueError(f"WaeStep: contrast must be a fmri_hip.contrast.LatentContrast, got {type(contrast).__name__}")
+        if contrast is not None and (cfg.latent_dim % 64 or not 64 <= cfg.latent_dim <= 1024):
+            raise ValueError(f"WaeStep: contrast= needs a latent size that is a multiple of 64, at most 1024 (csrc/contrast.hip); "
+                             f"latent_dim is {cfg.latent_dim}")
+        self.penalty, self.contrast = penalty, contrast
         self.cfg, self.stage, self.n_voxels = cfg, stage, n_voxels
         self.sc = Scales() if scales is None else scales
         self.hp = hp if hp is not None else (WaeHyper() if stage == 1 else WaeHyper.stage23())
@@ -191,6 +211,9 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         require_gpu(image)
         cfg, hp, sc = self.cfg, self.hp, self.sc
         B, _, H, W = image.shape
+        if self.contrast is not None and not 2 <= B * self.dd.world <= N_MAX:     # (before the step draws anything)
+            raise ValueError(f"WaeStep: contrast= needs a global batch of 2 to {N_MAX} rows (in-batch negatives; "
+                             f"csrc/contrast.hip), got {B} x {self.dd.world} ranks")
         with self.draws:                         # (Stages II / III draw no noise: the round is the feed's and the rows')
             if st == 1:
                 z_fake_noise, = self._noise(B, ("z_fake_noise", SID_ZFAKE, z_fake_noise))
@@ -259,8 +282,14 @@ class WaeStep(_LatentDiscPhase, _StepBase):
             dz_pen = self._penalty(self.wd, z16, pen_w, pen_scale, self.scal, need_dz=train_enc)
         else:
             mmd_w = hp.lam_mmd * Bg if st == 1 else hp.lam_mmd
-            dz_pen = self._mmd_penalty(head32, p32, mmd_w, need_dz=train_enc)
-        self.dd.all_reduce(self.scal[:4])
+            rows = self._global_rows(head32, p32)
+            dz_pen = self._mmd_penalty(rows, B, mmd_w, need_dz=train_enc)
+        if self.contrast is not None:
+            # (Stages II / III: the MMD's other side is the teacher's means too -- one gather serves both terms)
+            dz_con = self._contrast_term(rows if not gan else self._global_rows(head32, head_t), B, need_dz=train_enc)
+            if dz_con is not None:
+                dz_pen = dz_pen[:, :Z] + dz_con
+        self.dd.all_reduce(self.scal[:4] if self.contrast is None else self.scal[:W_TOP1 + 1])
 
         train_dec = st != 2
         if train_dec:
@@ -283,44 +312,76 @@ class WaeStep(_LatentDiscPhase, _StepBase):
         if train_dec:
             self.opt_dec.step()
         self.fw = dict(B=B, y=y, x16=x16, head32=head32, Z=Z)      # (x16: what Evaluator.train_batch compares y with)
+        if self.contrast is not None:
+            self.fw["head_t"] = head_t
         if self.mon is not None:
             self.mon.tail(head32, Z, [self.scal[:len(W_LOG_KEYS)]], None)
         self._log_append()
         return self.scal
 
-    def _mmd_penalty(self, head32, p32, w: float, need_dz: bool):
-        """w * MMD_u(q, p) into the penalty slot and, with need_dz, d/dq of it for this rank's rows (fp32 [B, Z], true
-        scale).  q = head32[:, :Z] (the trained encoder's means), p = p32[:, :Z]; the statistic is over the global batch:
-        with data parallelism every rank fills its slice of a zero buffer [2, n_global, Z], one SUM all-reduce gathers
-        both sides, every rank evaluates the same global statistic (only rank 0 adds it to the slot, which the loss
-        all-reduce then sums) and keeps the gradient rows of its own samples."""
+    def _global_rows(self, head32, other32):
+        """(q, p): the first Z columns of this rank's two [B, >= Z] fp32 blocks over the GLOBAL batch -- views without data
+        parallelism; with it every rank fills its slice of a zero buffer [2, n_global, Z] and one SUM all-reduce gathers
+        both sides."""
         B, Z = head32.shape[0], self.cfg.latent_dim
         dd, rank = self.dd, self.dd.rank
-        if dd.on:
-            buf = torch.zeros(2, B * dd.world, Z, dtype=torch.float32, device=head32.device)
-            buf[0, rank * B:(rank + 1) * B] = head32[:, :Z]
-            buf[1, rank * B:(rank + 1) * B] = p32[:, :Z]
-            dd.all_reduce(buf)
-            q, p = buf[0], buf[1]
-        else:
-            q, p = head32[:, :Z], p32[:, :Z]
+        if not dd.on:
+            return head32[:, :Z], other32[:, :Z]
+        buf = torch.zeros(2, B * dd.world, Z, dtype=torch.float32, device=head32.device)
+        buf[0, rank * B:(rank + 1) * B] = head32[:, :Z]
+        buf[1, rank * B:(rank + 1) * B] = other32[:, :Z]
+        dd.all_reduce(buf)
+        return buf[0], buf[1]
+
+    def _own_rows(self, dq, B: int):
+        """This rank's rows of a gradient over the global batch (None stays None)."""
+        if dq is None or not self.dd.on:
+            return dq
+        return dq[self.dd.rank * B:(self.dd.rank + 1) * B]
+
+    def _mmd_penalty(self, rows, B: int, w: float, need_dz: bool):
+        """w * MMD_u(q, p) into the penalty slot and, with need_dz, d/dq of it for this rank's B rows (fp32 [B, Z], true
+        scale).  ``rows`` = _global_rows(head32, p32): q the trained encoder's means, p the other side, over the global
+        batch -- every rank evaluates the same global statistic (only rank 0 adds it to the slot, which the loss
+        all-reduce then sums) and keeps the gradient rows of its own samples."""
+        q, p = rows
         dq = torch.empty(q.shape, dtype=torch.float32, device=q.device) if need_dz else None
-        mmd_imq(q, p, self.hp.mmd_sigma2, w=w, total=self.scal[W_PEN:W_PEN + 1] if rank == 0 else None, dq=dq)
-        if dq is None:
-            return None
-        return dq[rank * B:(rank + 1) * B] if dd.on else dq
+        mmd_imq(q, p, self.hp.mmd_sigma2, w=w, total=self.scal[W_PEN:W_PEN + 1] if self.dd.rank == 0 else None, dq=dq)
+        return self._own_rows(dq, B)
+
+    def _contrast_term(self, rows, B: int, need_dz: bool):
+        """weight * InfoNCE(q, t) into W_CON, the in-batch top-1 rate into W_TOP1 and, with need_dz, d/dq of the term for
+        this rank's B rows (fp32 [B, Z], true scale).  ``rows`` = _global_rows(head32, head_t), as for _mmd_penalty: every
+        rank evaluates the same statistic, only rank 0 adds the two values to the slots."""
+        (q, t), con, first = rows, self.contrast, self.dd.rank == 0
+        dq = torch.empty(q.shape, dtype=torch.float32, device=q.device) if need_dz else None
+        latent_nce(q, t, con.temperature, con.symmetric, w=con.weight,
+                   total=self.scal[W_CON:W_CON + 1] if first else None,
+                   top1=self.scal[W_TOP1:W_TOP1 + 1] if first else None, dq=dq)
+        return self._own_rows(dq, B)
 
     # ---- views for tests / API -----------------------------------------------------------------------------
+    def _log_slots(self):
+        slots = list(enumerate(W_LOG_KEYS))
+        if self.contrast is not None:
+            slots += [(W_CON, W_CON_KEYS[0]), (W_TOP1, W_CON_KEYS[1])]
+        return slots
+
     def _log_columns(self):
-        return [(k, self.scal, i) for i, k in enumerate(W_LOG_KEYS)], W_LOG_KEYS
+        # (latent_top1 is a rate, not a loss)
+        losses = W_LOG_KEYS if self.contrast is None else W_LOG_KEYS + W_CON_KEYS[:1]
+        return [(k, self.scal, i) for i, k in self._log_slots()], losses
 
     def logs(self):
         v = self.scal.tolist()
-        return {k: v[i] for i, k in enumerate(W_LOG_KEYS)}
+        return {k: v[i] for i, k in self._log_slots()}
 
     def outputs(self):
         fw = self.fw
-        return dict(x_recon=nhwc_to_images(fw["y"], 3), z_real=fw["head32"][:, :fw["Z"]].clone())
+        out = dict(x_recon=nhwc_to_images(fw["y"], 3), z_real=fw["head32"][:, :fw["Z"]].clone())
+        if "head_t" in fw:
+            out["z_teacher"] = fw["head_t"][:, :fw["Z"]].clone()       # (contrast= only: the other side of the term)
+        return out
 
     def named_grads(self):
         """True-scale gradients of the last step (syncs; tests only)."""

@@ -2,7 +2,7 @@
 
     python tools/launch_trace.py [--root CHECKOUT] > trace.txt        # one process; diff the files of two checkouts
 
-Wraps ``fmri_hip.lib.call`` and records per launch the entry point, every argument ``lib._SIGS`` types as an integer or
+Wraps ``fmri_hip.lib.call`` and records per launch the entry point, every argument ``lib.prototype`` types as an integer or
 a float (pointers only as null / non-null: addresses differ between runs) and the stream (0, 1, ... in order of first
 appearance).  Under FMRI_DETERMINISTIC=1, with recipe weights and the oracle's synthetic batch (B = 4, 64 px, the voxel
 counts of the ``*_b4`` goldens) it runs every step class and launch mode and prints per configuration the number of
@@ -46,7 +46,7 @@ _call = lib.call
 
 def traced_call(name, *a):
     rec = [name]
-    for t, v in zip(lib._SIGS[name], a):
+    for t, v in zip(lib.prototype(name)[0], a):
         if t is ctypes.c_void_p:
             rec.append("-" if v is None or (isinstance(v, int) and v == 0) else "p")
         else:
